@@ -184,3 +184,24 @@ def test_bench_gpus_n_launches_itself_as_a_child_process(monkeypatch):
     with pytest.raises(SystemExit) as e:
         bench.main()
     assert not seen and "WORLD_SIZE=1" in str(e.value.code)
+
+
+def test_bench_dump_outputs_samples_a_large_frame_at_fixed_positions(tmp_path):
+    """`bench.py --dump-outputs`: float32 files; a headline-size frame (24.9 M elements) is written as its values at a fixed, seeded,
+    sorted set of flat indices -- the same positions in every run -- and the dump stays within 64 MB; a small array is written whole."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    n = 2160 * 3840 * 3
+    frame = (torch.arange(n, dtype=torch.int32) % 2039).to(torch.float16).reshape(1, 2160, 3840, 3)     # (integers below 2048: exact in fp16)
+    small = torch.linspace(0, 1, 24, dtype=torch.float64).reshape(2, 3, 4)
+    info = bench.dump_outputs(str(tmp_path / "a"), dict(hr_frame=frame, small=small))
+    bench.dump_outputs(str(tmp_path / "b"), dict(hr_frame=frame + 1))
+    a, b, s = np.load(tmp_path / "a" / "hr_frame.npy"), np.load(tmp_path / "b" / "hr_frame.npy"), np.load(tmp_path / "a" / "small.npy")
+    assert sorted(os.listdir(tmp_path / "a")) == ["hr_frame.npy", "small.npy"]
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_MAX_ELEMS,) and a.nbytes + s.nbytes <= 64 << 20
+    assert info["hr_frame"]["elements"] == n and info["hr_frame"]["sampled"] == a.size and info["hr_frame"]["shape"] == [1, 2160, 3840, 3]
+    idx = np.sort(np.random.RandomState(0).choice(n, bench.DUMP_MAX_ELEMS, replace=False))
+    assert (np.diff(idx) > 0).all() and np.array_equal(a, (idx % 2039).astype(np.float32))
+    assert np.array_equal(b, a + 1)                      # the second dump read the same positions
+    assert s.dtype == np.float64 and np.array_equal(s, small.numpy()) and "sampled" not in info["small"]

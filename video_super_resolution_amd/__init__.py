@@ -16,6 +16,12 @@ _os.environ.setdefault("MIOPEN_FIND_MODE", "2")
 _os.environ.setdefault("MIOPEN_DEBUG_ENABLE_AI_IMMED_MODE_FALLBACK", "0")  # plain heuristic fallback (see bench.py)
 _os.environ.setdefault("MIOPEN_LOG_LEVEL", "2")  # errors only: the fallback heuristic is chatty at warning level
 
+# GraphedVSR on a host that allows a process fewer than four hardware queues (graph.py): the HIP runtime's replay of pre-recorded AQL
+# packets returned other values than the eager call there; its ordinary replay path does not.  The runtime reads the variable at its first
+# call, so like the ones above this only helps when the package is imported before that (bench.py sets it itself).
+if (_os.environ.get("GPU_MAX_HW_QUEUES") or "4").isdigit() and int(_os.environ.get("GPU_MAX_HW_QUEUES") or "4") < 4:
+    _os.environ.setdefault("DEBUG_CLR_GRAPH_PACKET_CAPTURE", "0")
+
 from .vsr import VSR  # noqa: F401,E402
 from .graph import GraphedVSR  # noqa: F401,E402
 from .sr import SRProjectionModule  # noqa: F401,E402

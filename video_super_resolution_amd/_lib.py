@@ -216,6 +216,24 @@ class route_batch:
         return False
 
 
+class serial_streams:
+    """`with _lib.serial_streams():` -- inside, the side streams the forward forks work onto (VSR._side_streams, the hourglass levels',
+    FlowNetSD's) ARE the current stream: the same launches with the same values in one stream's order.  GraphedVSR captures a
+    single-branch graph this way where the process may not open a hardware queue per branch (graph.py)."""
+    on = False
+
+    def __init__(self, enable: bool = True):
+        self.enable = bool(enable)
+
+    def __enter__(self):
+        self._old, serial_streams.on = serial_streams.on, serial_streams.on or self.enable
+        return self
+
+    def __exit__(self, *exc):
+        serial_streams.on = self._old
+        return False
+
+
 class EventTimer:
     """HIP-event timing of selected kernel launches on the current stream (used by bench.py for the roofline
     leg).  Disabled (no events, no overhead) unless `enabled` is set."""

@@ -167,6 +167,8 @@ class HourglassExec:
         raise ValueError(node)
 
     def _side(self, dev, level):
+        if L.serial_streams.on:
+            return torch.cuda.current_stream(dev)
         key = (dev.type, dev.index)
         if getattr(self, "_side_key", None) != key:
             self._side_streams, self._side_key = {}, key
@@ -471,6 +473,8 @@ class FlowNet2Exec:
         self.fusion = _FusionExec(net.flownetfusion)
 
     def _sd_stream(self, dev):
+        if L.serial_streams.on:
+            return torch.cuda.current_stream(dev)
         key = (dev.type, dev.index)
         if getattr(self, "_sd_key", None) != key:
             self._sd_side, self._sd_key = torch.cuda.Stream(device=dev), key

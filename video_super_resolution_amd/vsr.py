@@ -42,6 +42,7 @@ from .sr import SRProjectionModule
 from .trunk_exec import FlowNet2Exec, HourglassExec, OSVOSExec, TrunkExecCache
 from .vos import VOSProjectionModule
 from ._lib import on_device as _on_device
+from ._lib import serial_streams as _serial_streams
 
 
 def maskprocess(mask: torch.Tensor) -> torch.Tensor:
@@ -148,6 +149,8 @@ class VSR(nn.Module):
         return self.precision == "fp16"
 
     def _side_streams(self, dev):
+        if _serial_streams.on:
+            return [torch.cuda.current_stream(dev)] * 2
         key = (dev.type, dev.index)
         if getattr(self, "_streams_key", None) != key:
             # [0]: depth trunk; [1]: VOS trunk (pass 2 only) AND the shared planes' SR maps (pass 1 only) -- they never overlap, and with the main
