@@ -1,4 +1,5 @@
-"""ctypes binding of libvsr_hip.so (the C ABI declared in include/vsr_hip.h).
+"""ctypes binding of libvsr_hip.so (the C ABI declared in include/vsr_hip.h) and of libvsr_hip_grad.so (include/vsr_hip_grad.h:
+the backward of the three native flow operators).
 
 There is deliberately no CPU or eager-PyTorch fallback behind these entry points: if the
 shared library is missing, or an operator is handed a non-CUDA tensor, the call raises.
@@ -18,8 +19,11 @@ LIB_PATH = os.path.join(_PKG, "libvsr_hip.so")
 XLIB_PATH = os.path.join(_PKG, "libvsr_hip_xcheck.so")
 HEADER_PATH = os.path.join(_ROOT, "include", "vsr_hip.h")
 XHEADER_PATH = os.path.join(_ROOT, "include", "vsr_hip_xcheck.h")
+GLIB_PATH = os.path.join(_PKG, "libvsr_hip_grad.so")
+GHEADER_PATH = os.path.join(_ROOT, "include", "vsr_hip_grad.h")
 _lib = None
 _xlib = None
+_glib = None
 # the cross-check library instead of the shipping one for every call (set by `xcheck()`; the environment switch serves the
 # measurement tools, whose VSR_TUNING codes only that library understands)
 _use_x = os.environ.get("VSR_USE_XCHECK", "0") == "1" or bool(os.environ.get("VSR_TUNING", "").strip())
@@ -30,8 +34,8 @@ class VsrHipError(RuntimeError):
 
 
 def build(verbose: bool = False) -> str:
-    """Compile every HIP source for gfx950 into the in-tree libvsr_hip.so and libvsr_hip_xcheck.so (hipcc cross-compiles without
-    a GPU)."""
+    """Compile every HIP source for gfx950 into the in-tree libvsr_hip.so, libvsr_hip_xcheck.so and libvsr_hip_grad.so (hipcc
+    cross-compiles without a GPU)."""
     cmd = ["make", "-j4", "-C", os.path.join(_PKG, "csrc")]
     if not verbose:
         cmd.insert(1, "-s")
@@ -39,19 +43,24 @@ def build(verbose: bool = False) -> str:
     return LIB_PATH
 
 
-def declared_symbols(xcheck: bool = False) -> list:
-    """Entry points include/vsr_hip.h declares (xcheck: the ones include/vsr_hip_xcheck.h adds)."""
-    with open(XHEADER_PATH if xcheck else HEADER_PATH) as f:
+def declared_symbols(xcheck: bool = False, grad: bool = False) -> list:
+    """Entry points include/vsr_hip.h declares (xcheck: the ones include/vsr_hip_xcheck.h adds; grad: the ones of
+    include/vsr_hip_grad.h, a library of its own)."""
+    with open(GHEADER_PATH if grad else XHEADER_PATH if xcheck else HEADER_PATH) as f:
         text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
     return sorted(set(re.findall(r"\b(vsr_[a-z0-9_]+)\s*\(", text)))
 
 
-def _open(path: str) -> ctypes.CDLL:
+def _dlopen(path: str) -> ctypes.CDLL:
     if not os.path.exists(path):
         raise VsrHipError(
             f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(there is no CPU fallback for the device path)")
-    lib = ctypes.CDLL(path)
+    return ctypes.CDLL(path)
+
+
+def _open(path: str) -> ctypes.CDLL:
+    lib = _dlopen(path)
     lib.vsr_last_error.restype = ctypes.c_char_p
     lib.vsr_last_route.restype = ctypes.c_char_p
     for fn in ("vsr_sr_query", "vsr_train_corr_dw_ws_floats", "vsr_train_prelu_bwd_ws_floats"):
@@ -72,6 +81,20 @@ def load_xcheck() -> ctypes.CDLL:
                 lib.vsr_conv2d_tuning(int(t))
         _xlib = lib
     return _xlib
+
+
+def load_grad() -> ctypes.CDLL:
+    """libvsr_hip_grad.so (include/vsr_hip_grad.h): the backward kernels of Resample2d, ChannelNorm and Correlation.  Its own error
+    buffer: `check(rc, what, lib=load_grad())`."""
+    global _glib
+    if _glib is None:
+        lib = _dlopen(GLIB_PATH)
+        lib.vsr_grad_last_error.restype = ctypes.c_char_p
+        lib.vsr_last_error = lib.vsr_grad_last_error   # the name `check` reads a library's message under
+        if lib.vsr_grad_abi_version() != 1:
+            raise VsrHipError(f"{os.path.basename(GLIB_PATH)}: ABI version mismatch")
+        _glib = lib
+    return _glib
 
 
 def load() -> ctypes.CDLL:
