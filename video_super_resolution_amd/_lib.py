@@ -1,5 +1,5 @@
-"""ctypes binding of libvsr_hip.so (the C ABI declared in include/vsr_hip.h) and of libvsr_hip_grad.so (include/vsr_hip_grad.h:
-the backward of the three native flow operators).
+"""ctypes binding of libvsr_hip.so (the C ABI declared in include/vsr_hip.h), of libvsr_hip_grad.so (include/vsr_hip_grad.h:
+the backward of the three native flow operators) and of libvsr_hip_s3.so (include/vsr_hip_s3.h: the fused x3 stage of the SR net).
 
 There is deliberately no CPU or eager-PyTorch fallback behind these entry points: if the
 shared library is missing, or an operator is handed a non-CUDA tensor, the call raises.
@@ -21,9 +21,12 @@ HEADER_PATH = os.path.join(_ROOT, "include", "vsr_hip.h")
 XHEADER_PATH = os.path.join(_ROOT, "include", "vsr_hip_xcheck.h")
 GLIB_PATH = os.path.join(_PKG, "libvsr_hip_grad.so")
 GHEADER_PATH = os.path.join(_ROOT, "include", "vsr_hip_grad.h")
+S3LIB_PATH = os.path.join(_PKG, "libvsr_hip_s3.so")
+S3HEADER_PATH = os.path.join(_ROOT, "include", "vsr_hip_s3.h")
 _lib = None
 _xlib = None
 _glib = None
+_s3lib = None
 # the cross-check library instead of the shipping one for every call (set by `xcheck()`; the environment switch serves the
 # measurement tools, whose VSR_TUNING codes only that library understands)
 _use_x = os.environ.get("VSR_USE_XCHECK", "0") == "1" or bool(os.environ.get("VSR_TUNING", "").strip())
@@ -34,8 +37,8 @@ class VsrHipError(RuntimeError):
 
 
 def build(verbose: bool = False) -> str:
-    """Compile every HIP source for gfx950 into the in-tree libvsr_hip.so, libvsr_hip_xcheck.so and libvsr_hip_grad.so (hipcc
-    cross-compiles without a GPU)."""
+    """Compile every HIP source for gfx950 into the in-tree libvsr_hip.so, libvsr_hip_xcheck.so, libvsr_hip_grad.so and
+    libvsr_hip_s3.so (hipcc cross-compiles without a GPU)."""
     cmd = ["make", "-j4", "-C", os.path.join(_PKG, "csrc")]
     if not verbose:
         cmd.insert(1, "-s")
@@ -43,10 +46,10 @@ def build(verbose: bool = False) -> str:
     return LIB_PATH
 
 
-def declared_symbols(xcheck: bool = False, grad: bool = False) -> list:
-    """Entry points include/vsr_hip.h declares (xcheck: the ones include/vsr_hip_xcheck.h adds; grad: the ones of
-    include/vsr_hip_grad.h, a library of its own)."""
-    with open(GHEADER_PATH if grad else XHEADER_PATH if xcheck else HEADER_PATH) as f:
+def declared_symbols(xcheck: bool = False, grad: bool = False, s3: bool = False) -> list:
+    """Entry points include/vsr_hip.h declares (xcheck: the ones include/vsr_hip_xcheck.h adds; grad / s3: the ones of
+    include/vsr_hip_grad.h / include/vsr_hip_s3.h, libraries of their own)."""
+    with open(S3HEADER_PATH if s3 else GHEADER_PATH if grad else XHEADER_PATH if xcheck else HEADER_PATH) as f:
         text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
     return sorted(set(re.findall(r"\b(vsr_[a-z0-9_]+)\s*\(", text)))
 
@@ -97,6 +100,21 @@ def load_grad() -> ctypes.CDLL:
     return _glib
 
 
+def load_s3() -> ctypes.CDLL:
+    """libvsr_hip_s3.so (include/vsr_hip_s3.h): the fused FeedbackBlock stage of the x3 geometry (csrc/sr_utd_s3.hip).  Its own error
+    buffer: `check(rc, what, lib=load_s3())`."""
+    global _s3lib
+    if _s3lib is None:
+        lib = _dlopen(S3LIB_PATH)
+        lib.vsr_s3_last_error.restype = ctypes.c_char_p
+        lib.vsr_last_error = lib.vsr_s3_last_error   # the name `check` reads a library's message under
+        lib.vsr_s3_query.restype = ctypes.c_size_t
+        if lib.vsr_s3_abi_version() != 1:
+            raise VsrHipError(f"{os.path.basename(S3LIB_PATH)}: ABI version mismatch")
+        _s3lib = lib
+    return _s3lib
+
+
 def load() -> ctypes.CDLL:
     """The library every product call goes through: libvsr_hip.so, unless a test / tool asked for the cross-check library."""
     global _lib
@@ -124,6 +142,8 @@ class xcheck:
 
 # vsr_sr_query codes (include/vsr_hip.h)
 Q_UTD_BLOB_BYTES, Q_UTD_STRIP_WIDTH, Q_UTD_S2_BLOB_BYTES, Q_UTD_S2_STRIP_WIDTH, Q_TAIL_S2_BLOB_BYTES = range(5)
+# vsr_s3_query codes (include/vsr_hip_s3.h)
+Q_S3_BLOB_BYTES, Q_S3_STRIP_WIDTH = range(2)
 
 
 def check(rc: int, what: str = "", lib=None) -> None:

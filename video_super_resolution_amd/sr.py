@@ -197,13 +197,16 @@ class SRProjectionModule(nn.Module):
         P["slopes_le_one"] = all(a <= 1.0 for a in P["up_a"] + P["dn_a"] + P["dt_a"] + [P["out_a"]])
         P["tail_par"] = torch.cat((P["cv_b"], P["sub_s"], P["sub_b"], P["add_s"], P["add_b"])).contiguous()
         if self.upscale_factor != 4:
-            # scale extension: the stage as separate launches on the generic NHWC fp16 MFMA convolution (igemm.py)
+            # scale extension: the stage in one launch (x2: k_utd_s2, x3: k_utd_s3) or, with fused_s2 / fused_s3 off, as separate
+            # launches on the generic NHWC fp16 MFMA convolution (igemm.py)
             def stage(j):
                 args = (b.upBlocks[j + 1], P["dt_w"][j + 1], _NF * (j + 2), P["dt_b"][j + 1], P["dt_a"][j + 1], b.downBlocks[j + 2])
                 if self.upscale_factor == 2 and self.fused_s2:
                     # (with the next group's uptran slice when another stage follows: applied inside the launch, `fuse_uptran`)
                     post = (P["ut_w"][j + 3], _NF * (j + 4), P["ut_b"][j + 3], P["ut_a"][j + 3]) if j + 6 <= G else None
                     return _FusedStageS2(*args, slopes_le_one=P["slopes_le_one"], rows_fn=self._rows_per_segment, wide=self.utd_s2_build == 2, post=post)
+                if self.upscale_factor == 3 and self.fused_s3:
+                    return _FusedStageS3(*args, slopes_le_one=P["slopes_le_one"], rows_fn=self._rows_per_segment)
                 return _UnfusedStage(*args, self.upscale_factor)
             P["stage"] = {j: stage(j) for j in range(0, G - 2, 3)}
             P["out_deconv"] = _PhaseDeconv(self.out[0].weight, self.out[0].bias, P["out_a"], self.upscale_factor)
@@ -648,6 +651,8 @@ class SRProjectionModule(nn.Module):
     fold_tail = os.environ.get("VSR_FOLD_TAIL", "1") != "0"   # the last compress_out inside the tail kernel's LR path (k_tail3 / k_tail_s2; False: its own chain launch, the cross-check)
     fused_s2 = True    # scale 2: the stage on k_utd_s2 (csrc/sr_utd_s2.hip); False: the unfused launches (cross-check).
                        # (read when the weights are packed: change it before the first forward or bump a parameter)
+    fused_s3 = True    # scale 3: the stage on k_utd_s3 (csrc/sr_utd_s3.hip, libvsr_hip_s3.so); False: the unfused launches (cross-check).
+                       # (read when the weights are packed, as fused_s2; the x3 tail stays on _tail_unfused either way)
 
     utd_s2_build = int(os.environ.get("VSR_UTD_S2_BUILD", "1"))   # x2 stage: 1 = k_utd_s2 (default), 2 = k_utd_s2w (32x32x16 MFMA, one wave per SIMD: measured 5 % slower, LAB_NOTES R5.8)
     fuse_uptran = os.environ.get("VSR_UTD_POST", "1") != "0"   # the uptran 1x1 between the two stages of a step inside the first stage's launch
@@ -1173,6 +1178,95 @@ class _FusedStageS2:
             L.check(fn(L.dptr(a[n0:n0 + n], torch.float16), L.dptr(self.blob, torch.uint8),
                                                L.dptr(out[n0:n0 + n], torch.float16), n, h, w, rows, int(self.slopes_le_one), L.stream()),
                     "sr_utd_s2_f16")
+            L.TIMER.stop(tok)
+        return out
+
+
+# the x3 stage's waves own phase SETS of equal tap count (csrc/sr_utd_s3.hip): (HR row phase, HR column phase) per wave, in slot order
+_S3_PHASES = (((1, 1), (0, 0)), ((0, 1), (2, 1)), ((1, 0), (1, 2)), ((0, 2), (2, 0), (2, 2)))
+
+
+def _s3_taps(x):
+    """Kernel indices of phase x of the (7, 3, 2) geometry in slot order: k = x + 2 - 3 d for d = +1, 0, -1 where 0 <= k <= 6."""
+    return [x + 2 - 3 * d for d in (1, 0, -1) if 0 <= x + 2 - 3 * d <= 6]
+
+
+def pack_utd_s3_blob(up_w, up_b, up_a, tr_w, tr_col0, tr_b, tr_a, dn_w, dn_b, dn_a, layout: int = 1, post=None) -> torch.Tensor:
+    """Weights of one fused x3 stage in the per-wave MFMA fragment order of csrc/sr_utd_s3.hip (include/vsr_hip_s3.h).  A wave's
+    slots run over its phases (r, c) of _S3_PHASES, then the kernel rows ky of r, then the kernel columns kx of c (_s3_taps); slot
+    t of the deconvolution is element (ky, kx) of the ConvTranspose2d weight [32(in),32(out),7,7] and slot t of the convolution
+    the SAME element of the Conv2d weight [32(out),32(in),7,7] (the down-convolution mirrors the tap algebra).  13 slots per
+    wave; the unused ones stay zero.  `layout` and `post` exist for the argument list of pack_utd_s2_blob: one layout, no POST build."""
+    if layout != 1 or post is not None:
+        raise NotImplementedError("k_utd_s3 has one fragment layout and no in-launch uptran slice")
+    dev = up_w.device
+    nbytes = int(L.load_s3().vsr_s3_query(L.Q_S3_BLOB_BYTES))
+    lane = torch.arange(64, device=dev)
+    col_l, g = lane & 15, lane >> 4
+    j8 = torch.arange(8, device=dev)
+    perm = _chunk_channel_order(dev)
+    MT = torch.arange(2, device=dev).view(2, 1, 1)
+    co = 16 * MT + col_l.view(1, 64, 1)
+    # deconv: A[co][k = 8 g + j] in natural channel order (the B operand comes straight from the LR rows);
+    # conv / 1x1: A[co][k = (g, j)] in the accumulator-derived channel order of the operand tiles
+    co_n, ci_n = torch.broadcast_tensors(co, 8 * g.view(1, 64, 1) + j8.view(1, 1, 8))
+    co_p, ci_p = torch.broadcast_tensors(co, perm[g].view(1, 64, 8))
+    upw, dnw = up_w.detach().float(), dn_w.detach().float()
+    slots = 13
+    up_frag = torch.zeros((4, slots, 2, 64, 8), dtype=torch.float16, device=dev)
+    dn_frag = torch.zeros((4, slots, 2, 64, 8), dtype=torch.float16, device=dev)
+    for wv, phases in enumerate(_S3_PHASES):
+        t = 0
+        for r, c in phases:
+            for ky in _s3_taps(r):
+                for kx in _s3_taps(c):
+                    up_frag[wv, t] = upw[ci_n, co_n, ky, kx].to(torch.float16)
+                    dn_frag[wv, t] = dnw[co_p, ci_p, ky, kx].to(torch.float16)
+                    t += 1
+        assert t <= slots
+    dt_frag = tr_w.detach().float()[co_p, tr_col0 + ci_p].to(torch.float16).contiguous()
+    blob = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+    o_dn = 4 * slots * 2 * 1024
+    o_dt = 2 * o_dn
+    o_f = o_dt + 2 * 1024
+    assert nbytes == o_f + 512
+    blob[0:o_dn] = up_frag.contiguous().view(torch.uint8).reshape(-1)
+    blob[o_dn:o_dt] = dn_frag.contiguous().view(torch.uint8).reshape(-1)
+    blob[o_dt:o_f] = dt_frag.view(torch.uint8).reshape(-1)
+    fpar = torch.zeros(128, dtype=torch.float32, device=dev)
+    fpar[0:32], fpar[32:64], fpar[64:96] = up_b.detach().float(), tr_b.detach().float(), dn_b.detach().float()
+    fpar[96], fpar[97], fpar[98] = float(up_a), float(tr_a), float(dn_a)
+    blob[o_f:o_f + 512] = fpar.view(torch.uint8)
+    return blob
+
+
+class _FusedStageS3:
+    """up_i -> downtran slice -> down_j for upscale factor 3 in ONE launch (csrc/sr_utd_s3.hip: the x3 map stays in registers)."""
+
+    has_post = False   # (no in-launch uptran slice: the caller keeps its own chain launch between two stages)
+
+    def __init__(self, up, dt_w, dt_col, dt_b, dt_a, dn, slopes_le_one, rows_fn):
+        self.blob = pack_utd_s3_blob(up[0].weight, up[0].bias, float(up[1].weight.detach()), dt_w, dt_col, dt_b, dt_a,
+                                     dn[0].weight, dn[0].bias, float(dn[1].weight.detach()))
+        self.slopes_le_one = bool(slopes_le_one)
+        self.rows_fn = rows_fn
+
+    def __call__(self, a, chain, out=None, side=False, post=False):
+        """-> out [N,h,w,32] fp16."""
+        assert not post
+        N, h, w, _ = a.shape
+        if out is None:
+            out = torch.empty((N, h, w, _NF), dtype=torch.float16, device=a.device)
+        lib = L.load_s3()
+        nb = max(1, min(N, ((1 << 32) - 32) // (h * w * _NF * 2)))   # planes per launch: the kernel's 32-bit byte offsets
+        for n0 in range(0, N, nb):
+            n = min(nb, N - n0)
+            tok = L.TIMER.start(("sr_utd_s3_f16" if n == 8 else f"sr_utd_s3_f16_p{n}") + ("_side" if side else ""))
+            # k_utd_s3: one wave per SIMD (its weights fill the register file), one workgroup per CU
+            rows = self.rows_fn(n, h, w, cus=256, strip=int(lib.vsr_s3_query(L.Q_S3_STRIP_WIDTH)))
+            L.check(lib.vsr_s3_sr_utd_f16(L.dptr(a[n0:n0 + n], torch.float16), L.dptr(self.blob, torch.uint8),
+                                          L.dptr(out[n0:n0 + n], torch.float16), n, h, w, rows, int(self.slopes_le_one), L.stream()),
+                    "sr_utd_s3_f16", lib=lib)
             L.TIMER.stop(tok)
         return out
 
