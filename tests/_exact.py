@@ -1,0 +1,251 @@
+"""Exact-arithmetic test cases: operands on which every kernel route must equal a float64 evaluation BIT FOR BIT.
+
+If activations, weights and biases are small integers (or dyadic fractions: multiples of a power of two `g`), every product and
+every partial sum of a convolution is a multiple of g*g below 2^24 g*g and therefore a float32 value: the result does not depend
+on summation order, split-K, tile shape, MFMA shape or wave assignment.  If every value that a kernel stores as fp16 is an fp16
+value as well, fp16 storage does not round either.  Inside that budget a kernel equals the float64 CPU evaluation exactly, and one
+wrong element anywhere is a hard failure with coordinates instead of a fraction of a range-relative bar.
+
+This module holds
+  * seeded operand generators (`ints`, `sparse_weights`, `slopes`),
+  * float64 references on stock torch.nn.functional operators, each CHECKING its budget (`conv_ref`, `deconv_ref`, `stage_ref`,
+    `BudgetError` names the offending coordinate: a case outside its budget is a mistake in the test, never a reason for a tolerance),
+  * `assert_exact` / `diff_mask` / `bbox`, which report the number of differing elements, the first one and their bounding box.
+
+The sign of a zero is not compared (`-0.0 == +0.0`): `0 * negative` in a PReLU with slope 0 is -0.0 in one formulation and +0.0 in
+another, and no consumer can tell.  Everything else is compared as bits.
+
+What these cases cannot see: rounding behaviour (the Gaussian-operand tests keep covering it) and overflow to infinity.
+"""
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+MAX_THREADS = 16
+
+SLOPES_LE_ONE = (0.0, 0.25, 0.5, 1.0)   # the `max(v, a v)` builds
+SLOPES_SELECT = (2.0, -0.5)             # the select builds (`v < 0 ? a v : v`)
+
+
+class BudgetError(Exception):
+    """The case leaves the exact regime (a test-construction error)."""
+
+
+def _threads():
+    if torch.get_num_threads() > MAX_THREADS:
+        torch.set_num_threads(MAX_THREADS)
+
+
+# ---------------------------------------------------------------------------------------------------------------- operands
+def ints(rs, shape, lo=-3, hi=3, step=1.0):
+    """Values step * {lo..hi}, float64 tensor (step = 1: integers; step = 0.25: the dyadic regime)."""
+    return torch.from_numpy(rs.randint(lo, hi + 1, size=shape).astype(np.float64) * step)
+
+
+def sparse_weights(rs, shape, density=0.2, mag=2, step=1.0):
+    """Weights step * {-mag..mag} \\ {0} on a `density` share of the elements, zero elsewhere."""
+    v = rs.randint(1, mag + 1, size=shape) * (rs.randint(0, 2, size=shape) * 2 - 1)
+    keep = rs.random_sample(size=shape) < density
+    return torch.from_numpy((v * keep).astype(np.float64) * step)
+
+
+def slopes(rs, n, pool=SLOPES_LE_ONE):
+    return [float(pool[i]) for i in rs.randint(0, len(pool), size=n)]
+
+
+def granularity(*tensors):
+    """The largest power of two of which every element of every tensor is a multiple (1.0 for integers)."""
+    g = 1.0
+    for t in tensors:
+        if t is None:
+            continue
+        t = torch.as_tensor(t, dtype=torch.float64)
+        while g > 2.0 ** -40 and bool((torch.remainder(t, g) != 0).any()):
+            g /= 2
+    return g
+
+
+# ---------------------------------------------------------------------------------------------------------------- checks
+def _coord(mask):
+    idx = torch.nonzero(mask)
+    return tuple(int(i) for i in idx[0])
+
+
+def check_sum_budget(abs_sum, gran, what):
+    """abs_sum = sum |x| |w| + |b| per output; every partial sum in every order is a multiple of `gran` of magnitude <= abs_sum, so it is a
+    float32 value when abs_sum < 2^24 gran."""
+    bad = abs_sum >= (2.0 ** 24) * gran
+    if bool(bad.any()):
+        c = _coord(bad)
+        raise BudgetError(f"{what}: sum |x||w| + |b| = {float(abs_sum[c])} at {c} is not below 2^24 * {gran}: partial sums may round in float32")
+
+
+def check_storable(t, dtype, what):
+    """Every element survives float64 -> dtype -> float64."""
+    bad = t.to(dtype).to(torch.float64) != t
+    if bool(bad.any()):
+        c = _coord(bad)
+        raise BudgetError(f"{what}: {float(t[c])!r} at {c} is not a {str(dtype).replace('torch.', '')} value (stored it becomes "
+                          f"{float(t.to(dtype)[c])!r})")
+    return t
+
+
+def check_live(t, what, min_nonzero=0.5, min_distinct=200, both_signs=True):
+    """The case is not degenerate: a share of the values non-zero, both signs present, a few hundred distinct values."""
+    nz = float((t != 0).double().mean())
+    if nz < min_nonzero:
+        raise BudgetError(f"{what}: only {nz:.0%} of the values are non-zero (minimum {min_nonzero:.0%})")
+    if both_signs and not (bool((t > 0).any()) and bool((t < 0).any())):
+        raise BudgetError(f"{what}: one sign only")
+    nd = int(torch.unique(t).numel())
+    if nd < min(min_distinct, t.numel() // 8):
+        raise BudgetError(f"{what}: {nd} distinct values (minimum {min(min_distinct, t.numel() // 8)})")
+    return t
+
+
+# ---------------------------------------------------------------------------------------------------------------- references
+def conv_ref(x, w, b=None, stride=1, padding=0, what="conv", store=None):
+    """float64 conv2d of exact operands (all float64 tensors), its float32 budget checked; `store`: a dtype the result must fit."""
+    _threads()
+    y = F.conv2d(x, w, b, stride=stride, padding=padding)
+    a = F.conv2d(x.abs(), w.abs(), None if b is None else b.abs(), stride=stride, padding=padding)
+    check_sum_budget(a, granularity(x) * granularity(w) if b is None else min(granularity(x) * granularity(w), granularity(b)), what)
+    if store is not None:
+        check_storable(y, store, what)
+    return y
+
+
+def deconv_ref(x, w, b=None, stride=1, padding=0, what="deconv", store=None):
+    """float64 conv_transpose2d (w [Cin, Cout, k, k]) of exact operands, its float32 budget checked."""
+    _threads()
+    y = F.conv_transpose2d(x, w, b, stride=stride, padding=padding)
+    a = F.conv_transpose2d(x.abs(), w.abs(), None if b is None else b.abs(), stride=stride, padding=padding)
+    check_sum_budget(a, granularity(x) * granularity(w) if b is None else min(granularity(x) * granularity(w), granularity(b)), what)
+    if store is not None:
+        check_storable(y, store, what)
+    return y
+
+
+def prelu_ref(v, slope):
+    """v > 0 ? v : slope v, float64 (one slope for all channels, as every PReLU of the SR net)."""
+    return torch.where(v > 0, v, v * float(slope))
+
+
+def leaky_tenth_f16(v):
+    """LeakyReLU with the product's default slope 0.1, which is not dyadic: the reference restates the kernel's own operation
+    (csrc/conv_igemm.hip `fmaxf(x, 0) + nslope * fminf(x, 0)` / `t >= 0 ? t : t * p.slope`, csrc/conv_tile.hip:223, conv_patch.h:34;
+    csrc/flow_ops.hip k_corr_mfma `s > 0 ? s : 0.1f * s`): the exact sum (a float32 value by the budget), ONE float32 multiply by
+    float32(0.1) on the negative side -- for a negative x the other summand is +0, so a fused multiply-add gives the same --
+    and one round-to-nearest-even to fp16.  -> float64 tensor of fp16 values."""
+    x = check_storable(v, torch.float32, "leaky 0.1 input").to(torch.float32)
+    y = torch.where(x >= 0, x, x * torch.tensor(0.1, dtype=torch.float32))
+    return y.to(torch.float16).to(torch.float64)
+
+
+def leaky_tenth_f32(v):
+    """The float32 routes' LeakyReLU 0.1: one float32 multiply on the negative side (csrc/conv_f32_nchw.hip epilogue)."""
+    x = check_storable(v, torch.float32, "leaky 0.1 input").to(torch.float32)
+    return torch.where(x >= 0, x, x * torch.tensor(0.1, dtype=torch.float32)).to(torch.float64)
+
+
+def act_ref(v, act, slope=0.1, store=torch.float16):
+    """act: 0 none, 1 ReLU, 2 LeakyReLU(slope) as igemm.ACT_*; the result checked to fit `store`."""
+    if act == 0:
+        y = v
+    elif act == 1:
+        y = F.relu(v)
+    elif slope == 0.1:
+        return leaky_tenth_f16(v) if store == torch.float16 else leaky_tenth_f32(v)
+    else:
+        y = F.leaky_relu(v, slope)
+    return check_storable(y, store, f"activation {act} output")
+
+
+def stage_ref(a, up_w, up_b, up_a, dt_w, dt_b, dt_a, dn_w, dn_b, dn_a, S, live=True, min_distinct=200):
+    """One FeedbackBlock stage in float64: ConvTranspose2d(k S+4, s S, p 2) -> PReLU -> the live 32-column slice of the downtran 1x1
+    -> PReLU -> Conv2d(k S+4, s S, p 2) -> PReLU.  a [N,32,h,w]; up_w [32,32,k,k] (in, out); dt_w [32,32] (out, in: the slice);
+    dn_w [32,32,k,k] (out, in).  The fused kernels convert each sum to fp16 FIRST and apply PReLU on packed fp16 values with an fp16
+    slope (csrc/sr_f16_common.h), so each of the three sums and each of the three PReLU results is checked to be an fp16 value, and
+    the slopes too.  -> dict(hr, t, out) of float64 maps."""
+    for s in (up_a, dt_a, dn_a):
+        check_storable(torch.tensor([float(s)], dtype=torch.float64), torch.float16, "PReLU slope")
+    k = S + 4
+    hr0 = deconv_ref(a, up_w, up_b, stride=S, padding=2, what="stage deconvolution", store=torch.float16)
+    hr = check_storable(prelu_ref(hr0, up_a), torch.float16, "stage deconvolution after PReLU")
+    t0 = conv_ref(hr, dt_w.reshape(32, 32, 1, 1), dt_b, what="stage downtran 1x1", store=torch.float16)
+    t = check_storable(prelu_ref(t0, dt_a), torch.float16, "stage downtran after PReLU")
+    o0 = conv_ref(t, dn_w, dn_b, stride=S, padding=2, what="stage strided convolution", store=torch.float16)
+    out = check_storable(prelu_ref(o0, dn_a), torch.float16, "stage output after PReLU")
+    assert dn_w.shape[-1] == k and up_w.shape[-1] == k
+    if live:
+        check_live(hr0, "stage deconvolution sum", min_distinct=4)      # (the intermediates: both signs before every PReLU)
+        check_live(t0, "stage downtran sum", min_distinct=4)
+        check_live(o0, "stage strided-convolution sum", min_distinct=min_distinct)
+    return dict(hr=hr, t=t, out=out)
+
+
+# ---------------------------------------------------------------------------------------------------------------- comparison
+def _canon(t):
+    t = t.detach().cpu()
+    if t.is_floating_point():
+        t = t + 0.0   # -0.0 -> +0.0
+    return t.contiguous()
+
+
+_INT_OF = {torch.float16: torch.int16, torch.bfloat16: torch.int16, torch.float32: torch.int32, torch.float64: torch.int64}
+
+
+def diff_mask(got, want):
+    """Boolean tensor: where the bits of `got` differ from `want` converted to got's dtype (the conversion is exact by the budget; it is
+    checked here once more).  NaNs differ from everything, themselves included."""
+    got = _canon(got)
+    want = want.detach().cpu()
+    if tuple(got.shape) != tuple(want.shape):
+        raise AssertionError(f"shape {tuple(got.shape)} against {tuple(want.shape)}")
+    if want.dtype != got.dtype:
+        check_storable(want.to(torch.float64), got.dtype, "reference in the output dtype")
+    want = _canon(want.to(got.dtype))
+    it = _INT_OF.get(got.dtype)
+    m = (got.view(it) != want.view(it)) if it is not None else (got != want)
+    if got.is_floating_point():
+        m = m | torch.isnan(got) | torch.isnan(want)
+    return m
+
+
+def bbox(mask):
+    """[(first, last)] per dimension of the True elements; None when there is none."""
+    idx = torch.nonzero(mask)
+    if idx.numel() == 0:
+        return None
+    return [(int(idx[:, d].min()), int(idx[:, d].max())) for d in range(idx.shape[1])]
+
+
+def assert_exact(got, want, what, names="ncyx"):
+    """Equality of bits.  The failure message gives the number of differing elements, the first one with got / want, and the bounding
+    box of all of them per dimension (a tile seam, a strip edge or a channel chunk is visible from the message alone)."""
+    m = diff_mask(got, want)
+    n = int(m.sum())
+    if n == 0:
+        return
+    c = _coord(m)
+    g, w = _canon(got), want.detach().cpu()
+    names = names if len(names) == m.dim() else "".join(chr(ord("a") + i) for i in range(m.dim()))
+    box = ", ".join(f"{names[d]} {lo}..{hi}" for d, (lo, hi) in enumerate(bbox(m)))
+    at = ", ".join(f"{names[d]}={c[d]}" for d in range(m.dim()))
+    raise AssertionError(f"{what}: {n} of {m.numel()} elements differ from the float64 evaluation; first at ({at}): got {float(g[c])!r}, "
+                         f"want {float(w[c])!r}; all inside [{box}]")
+
+
+def nhwc(t, dtype=torch.float16, cp=None):
+    """[N,C,H,W] float64 -> [N,H,W,cp] of dtype, zero padded (CPU tensor; exact by construction, checked)."""
+    N, C, H, W = t.shape
+    check_storable(t, dtype, "NHWC operand")
+    out = torch.zeros((N, H, W, cp or C), dtype=dtype)
+    out[..., :C] = t.permute(0, 2, 3, 1).to(dtype)
+    return out
+
+
+def nchw64(t, c=None):
+    """[N,H,W,Cp] device tensor -> [N,c,H,W] CPU tensor of the same dtype."""
+    t = t.detach().cpu()
+    return t[..., :(c or t.shape[3])].permute(0, 3, 1, 2).contiguous()
