@@ -7,7 +7,8 @@ One "step" = one VSR.forward call per rank (one output frame of that rank's clip
 timed region; `value` = frames produced by all ranks / max-over-ranks wall time.  Ranks own independent clips (weak
 scaling, no data-path collective); the finished frames are gathered to rank 0 inside the timed region.
 
-    python bench.py                                   # C3-A on one GPU
+    python bench.py                                   # C3-A on one GPU: set-up, warm-up, the timed steps, the JSON line -- nothing else
+    python bench.py --full                            # + everything else this script measures or checks (below); minutes, not seconds
     python bench.py --config C2|C3B|C5                # the x2 configurations of BASELINE.json (scale extension)
     python bench.py --precision fp32                  # C3-A in exact float32
     python bench.py --steps K --dump-outputs DIR      # + DIR/hr_frame.npy: the frame the K-th timed step returned (build-to-build comparison)
@@ -20,6 +21,14 @@ scaling, no data-path collective); the finished frames are gathered to rank 0 in
   C2       540x960  -> 1080x1920    x2     fp32
   C5       2160x3840 -> 4320x7680   x2     fp16      depth + VOS guidance (always on), HBM stress
   (C1, the 128x128 CPU plumbing case, is `python -m video_super_resolution_amd.driver`; C4 = C3A with --clips 32 --gpus 8)
+
+--full adds, beside the headline value and never part of it (each leg has its own switch):
+  the extra loops `streaming`, `graph_replay`, `pcie_inclusive` on the resident model                   (--no-extras)
+  `cpu_baseline`: the CPU oracle timed on three small tiles, and `accuracy` against it on the first one (--no-cpu-baseline; --accuracy
+                  keeps the one-tile comparison without the timing, also when given without --full)
+  `configs`: short C3-B / C5 / C2 runs of this script in child processes, default C3-A invocation only  (--no-configs)
+The line's `roofline` object comes from HIP events inside the timed steps and committed profiles/ files: it takes no run of its own and
+is printed either way.
 """
 import argparse
 import json
@@ -277,14 +286,14 @@ def accuracy_vs_oracle(model, scale, precision, dev, first=None, lr=64):
 
 def other_configs(progress, names=("C3B", "C5", "C2"), steps=5, warmup=2, timeout_s=170):
     """The other single-GPU configurations of BASELINE.json, each as a SHORT run of this same script in a child process
-    (own model, own allocator; a failure there cannot cost the headline line), so that the driver's one default invocation
+    (own model, own allocator; a failure there cannot cost the headline line), so that one default `--full` invocation
     also times reading B of the headline ("1080p LR -> 4K", C3-B), C5 and C2.  -> {name: {value, ms_per_step, roofline, ...}}"""
     import subprocess
     torch.cuda.empty_cache()
     out = {}
     for name in names:
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--config", name, "--steps", str(steps), "--warmup", str(warmup),
-               "--no-extras", "--no-cpu-baseline", "--no-configs", "--accuracy"]
+               "--full", "--no-extras", "--no-cpu-baseline", "--no-configs", "--accuracy"]
         progress(f"config {name}: {steps} steps in a child process")
         t0 = time.time()
         try:
@@ -333,22 +342,29 @@ def main():
     ap.add_argument("--clips", type=int, default=0,
                     help="config C4: this many independent clips round-robin over the ranks (clip i -> rank i mod N), `steps` "
                          "frames each, one asynchronous gather per finished clip; 0 = one clip per rank")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything else this script measures or checks, reported beside the headline value: "
+                         "the extra loops, the CPU baseline with the accuracy against the oracle, the short runs of the other configurations "
+                         "(minutes; --no-extras / --no-cpu-baseline / --accuracy / --no-configs choose among them).  Without it a run sets "
+                         "up, warms up, times the steps and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle's timing (about a minute)")
     ap.add_argument("--accuracy", action="store_true",
-                    help="with --no-cpu-baseline: still evaluate the oracle on ONE LR 64x64 tile (a few CPU seconds) for the line's "
-                         "psnr_vs_oracle_db / max_rel_err fields (the default run takes them from the cpu_baseline's first tile)")
+                    help="--full with --no-cpu-baseline, or by itself: still evaluate the oracle on ONE LR 64x64 tile (a few CPU seconds) for the "
+                         "line's psnr_vs_oracle_db / max_rel_err fields (the --full run takes them from the cpu_baseline's first tile)")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise the RCCL process group and issue every collective (barrier, gathers, all_reduce) even with ONE "
                          "rank: lets a one-GPU box execute the N > 1 code path (tests/test_gpu_rccl_single_rank.py)")
     ap.add_argument("--no-configs", action="store_true",
-                    help="default C3-A line only: do not append the short C3-B / C5 / C2 runs under `configs`")
+                    help="--full, default C3-A line only: do not append the short C3-B / C5 / C2 runs under `configs`")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the LAST timed step returned to its caller -- VSR.forward's HR frame [1,H,W,3] -- "
                          "as DIR/hr_frame.npy (float32; a fixed seeded sample of the elements when the frame exceeds 32 MB).  Inputs and weights "
                          "are seeded: the same arguments give the same inputs in every run, so two builds compare output for output")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the separately-labelled extra loops (opt-in streaming mode; graph replay; PCIe-inclusive uint8 in / uint8 out)")
+                    help="--full without the separately-labelled extra loops (opt-in streaming mode; graph replay; PCIe-inclusive uint8 in / uint8 out)")
     args = ap.parse_args()
+    if not args.full:   # a plain run = the --full run with every one of its legs switched off (--accuracy, asked for by name, stays)
+        args.no_extras = args.no_cpu_baseline = args.no_configs = True
 
     h, w, scale, precision, label = CONFIGS[args.config]
     h, w = args.lr_h or h, args.lr_w or w
