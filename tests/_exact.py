@@ -8,7 +8,8 @@ wrong element anywhere is a hard failure with coordinates instead of a fraction 
 
 This module holds
   * seeded operand generators (`ints`, `sparse_weights`, `slopes`),
-  * float64 references on stock torch.nn.functional operators, each CHECKING its budget (`conv_ref`, `deconv_ref`, `stage_ref`,
+  * float64 references on stock torch.nn.functional operators, each CHECKING its budget (`conv_ref`, `deconv_ref`, `stage_ref`, and for
+    the two ends of the SR net `head_ref`, `chain_ref`, `fold_ref`, `tail_ref`, `bilinear_up_ref`, `fusion_ref`;
     `BudgetError` names the offending coordinate: a case outside its budget is a mistake in the test, never a reason for a tolerance),
   * `assert_exact` / `diff_mask` / `bbox`, which report the number of differing elements, the first one and their bounding box.
 
@@ -182,6 +183,160 @@ def stage_ref(a, up_w, up_b, up_a, dt_w, dt_b, dt_a, dn_w, dn_b, dn_a, S, live=T
         check_live(t0, "stage downtran sum", min_distinct=4)
         check_live(o0, "stage strided-convolution sum", min_distinct=min_distinct)
     return dict(hr=hr, t=t, out=out)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the SR net's two ends
+def _slope_ok(*slopes, dtype=torch.float16):
+    for s in slopes:
+        check_storable(torch.tensor([float(s)], dtype=torch.float64), dtype, "PReLU slope")
+
+
+def bilinear_up_ref(x, S, what="bilinear skip"):
+    """ATen upsample_bilinear2d with align_corners=False as the fusion kernels restate it (csrc/sr_scale.hip `bil`, `lerp4`): source
+    coordinate (dst + 0.5) / S - 0.5 clamped at 0, taps i0 = floor and i1 = min(i0 + 1, n - 1), weights (1 - l, l) with l = src - i0;
+    x [N,C,h,w] float64 -> [N,C,Sh,Sw].  For S = 2 and 4 the weights are k/4 and k/8: every product and sum of the kernel is a multiple
+    of gran(x) / (2S)^2 and exact in float32 when max|x| is below 2^24 of those (checked).  Any other S has no exact regime."""
+    if S not in (2, 4):
+        raise BudgetError(f"{what}: the bilinear weights of factor {S} are not dyadic; no exact regime (restate the kernel's float32 arithmetic instead)")
+    N, C, h, w = x.shape
+
+    def taps(n):
+        src = ((torch.arange(S * n, dtype=torch.float64) + 0.5) / S - 0.5).clamp(min=0.0)
+        i0 = src.floor().long()
+        return i0, torch.where(i0 < n - 1, i0 + 1, i0), src - i0.double()
+
+    y0, y1, ly = taps(h)
+    x0, x1, lx = taps(w)
+    g = granularity(x) / (2 * S) ** 2
+    if x.numel() and float(x.abs().max()) >= (2.0 ** 24) * g:
+        raise BudgetError(f"{what}: max |x| = {float(x.abs().max())} is not below 2^24 * {g}: a lerp may round in float32")
+    lx, ly = lx.view(1, 1, 1, -1), ly.view(1, 1, -1, 1)
+    rows0, rows1 = x[:, :, y0], x[:, :, y1]
+    top = lx * rows0[..., x1] + (1.0 - lx) * rows0[..., x0]
+    bot = lx * rows1[..., x1] + (1.0 - lx) * rows1[..., x0]
+    return check_storable(ly * bot + (1.0 - ly) * top, torch.float32, what)
+
+
+def tail_ref(hid, out_w, out_b, out_a, cv_w, cv_b, S, live=True):
+    """The tail in float64: `out` ConvTranspose2d(k S+4, s S, p 2) -> fp16 -> PReLU -> fp16 -> conv_out 3x3 (32 -> 3) + bias in float32.
+    hid [N,32,h,w]; out_w [32,32,k,k] (in, out); cv_w [3,32,3,3].  -> dict(hr, raw [N,3,Sh,Sw], dec = raw[..., ::S, ::S])."""
+    _slope_ok(out_a)
+    assert out_w.shape[-1] == S + 4 and tuple(cv_w.shape) == (3, 32, 3, 3)
+    check_storable(cv_w, torch.float16, "conv_out weight (fp16 fragments)")
+    hr0 = deconv_ref(hid, out_w, out_b, stride=S, padding=2, what="tail deconvolution", store=torch.float16)
+    hr = check_storable(prelu_ref(hr0, out_a), torch.float16, "tail deconvolution after PReLU")
+    raw = conv_ref(hr, cv_w, cv_b, padding=1, what="conv_out", store=torch.float32)
+    if live:
+        check_live(hr0, "tail deconvolution sum", min_distinct=4)
+        check_live(raw, "conv_out sum", min_distinct=50)
+    return dict(hr=hr, raw=raw, dec=raw[..., ::S, ::S].contiguous())
+
+
+def fold_ref(lr_a, lr_b, cmap, co_w, co_b, co_a, live=True):
+    """The FeedbackBlock's last compress_out as the FOLD tails apply it: 1x1 over two LR maps (co_w [32,64]: columns 0..31 read lr_a,
+    32..63 lr_b) + bias + the constant map cmap [32,h,w] (float32) -> fp16 -> PReLU -> fp16.  -> hid [N,32,h,w]."""
+    _slope_ok(co_a)
+    check_storable(cmap, torch.float32, "constant map")
+    x = torch.cat((lr_a, lr_b), 1)
+    s0 = conv_ref(x, co_w.reshape(32, 64, 1, 1), co_b, what="compress_out")
+    a = F.conv2d(x.abs(), co_w.abs().reshape(32, 64, 1, 1), co_b.abs()) + cmap.abs().unsqueeze(0)
+    check_sum_budget(a, min(granularity(x) * granularity(co_w), granularity(co_b), granularity(cmap)), "compress_out + constant map")
+    s0 = check_storable(s0 + cmap.unsqueeze(0), torch.float16, "compress_out sum")
+    if live:
+        check_live(s0, "compress_out sum", min_distinct=4)
+    return check_storable(prelu_ref(s0, co_a), torch.float16, "compress_out after PReLU")
+
+
+def chain_ref(stages, live=True):
+    """Up to three chained 32-channel 1x1 stages (csrc/sr_f16.hip k_chain1x1_h).  Each stage: dict(ins=[(x [N,32,P], w [32,32])...],
+    prev=w [32,32] or None (reads the previous stage's output), bias [32], cmap [32,P] float32 or None, slope).  The sum (float32) is
+    stored as fp16, PReLU is applied on fp16 values, the result is an fp16 value.  -> list of outputs [N,32,P]."""
+    _threads()
+    outs, last = [], None
+    for s, st in enumerate(stages):
+        _slope_ok(st["slope"])
+        terms = list(st["ins"]) + ([(last, st["prev"])] if st.get("prev") is not None else [])
+        if not terms or (st.get("prev") is not None and last is None):
+            raise ValueError(f"stage {s} has no input")
+        acc = st["bias"].view(1, 32, 1).clone()
+        mag = st["bias"].abs().view(1, 32, 1).clone()
+        gran = granularity(st["bias"])
+        if st.get("cmap") is not None:
+            check_storable(st["cmap"], torch.float32, f"stage {s} constant map")
+            acc, mag, gran = acc + st["cmap"].unsqueeze(0), mag + st["cmap"].abs().unsqueeze(0), min(gran, granularity(st["cmap"]))
+        for x, w in terms:
+            check_storable(w, torch.float16, f"stage {s} weight (fp16 fragments)")
+            check_storable(x, torch.float16, f"stage {s} input")
+            acc = acc + torch.einsum("oc,ncp->nop", w, x)
+            mag = mag + torch.einsum("oc,ncp->nop", w.abs(), x.abs())
+            gran = min(gran, granularity(x) * granularity(w))
+        check_sum_budget(mag, gran, f"chain stage {s}")
+        check_storable(acc, torch.float16, f"chain stage {s} sum")
+        if live:
+            check_live(acc, f"chain stage {s} sum", min_distinct=4)
+        last = check_storable(prelu_ref(acc, st["slope"]), torch.float16, f"chain stage {s} after PReLU")
+        outs.append(last)
+    return outs
+
+
+def head_ref(x, sub, w_in, b_in, a_in, w_feat, b_feat, a_feat, store=torch.float16, live=True):
+    """The head in float64: sub_mean (x * scale + bias per channel, sub = (scale [3], bias [3])) -> zero padding -> conv_in 3x3
+    (3 -> 128) + bias -> PReLU -> feat_in 1x1 (128 -> 32) + bias -> PReLU.  k_head_h (store = fp16) converts the mean-shifted
+    pixels and both weight tensors to fp16 for the matrix cores, and each of the two sums to fp16 BEFORE its PReLU (act_pack /
+    prelu_h2 on packed fp16 with an fp16 slope): the shifted pixels, both sums and both PReLU results must be values of `store`.
+    The float32 head (store = float32) keeps float32 throughout.  x [N,3,h,w], w_in [128,3,3,3], w_feat [32,128] -> [N,32,h,w]."""
+    _slope_ok(a_in, a_feat, dtype=store)
+    s, b = sub
+    t = check_storable(x * s.view(1, 3, 1, 1) + b.view(1, 3, 1, 1), store, "mean-shifted pixels")
+    if store == torch.float16:
+        check_storable(w_in, store, "conv_in weight (fp16 fragments)")
+        check_storable(w_feat, store, "feat_in weight (fp16 fragments)")
+    m0 = conv_ref(t, w_in, b_in, padding=1, what="conv_in", store=store)
+    mid = check_storable(prelu_ref(m0, a_in), store, "conv_in after PReLU")
+    f0 = conv_ref(mid, w_feat.reshape(32, -1, 1, 1), b_feat, what="feat_in", store=store)
+    if live:
+        check_live(m0, "conv_in sum", min_distinct=4)
+        check_live(f0, "feat_in sum", min_distinct=50)
+    return check_storable(prelu_ref(f0, a_feat), store, "feat_in after PReLU")
+
+
+def planes_ref(raw, x, sub, add, S, decimate=False):
+    """What the fusion MLP reads: (bilinear xS of sub_mean(x) + raw) * add_scale + add_bias per plane and channel, every float32
+    operation of it exact.  raw [N,3,Sh,Sw] (or [N,3,h,w] with `decimate`: the pixels (S i, S j)); x [N,3,h,w].  -> like raw."""
+    (ss, sb), (as_, ab) = sub, add
+    t = check_storable(x * ss.view(1, 3, 1, 1) + sb.view(1, 3, 1, 1), torch.float32, "mean-shifted pixels")
+    skip = bilinear_up_ref(t, S)
+    if decimate:
+        skip = skip[..., ::S, ::S]
+    v = check_storable(skip + raw, torch.float32, "skip + raw")
+    check_storable(v * as_.view(1, 3, 1, 1), torch.float32, "(skip + raw) * add_scale")
+    return check_storable(v * as_.view(1, 3, 1, 1) + ab.view(1, 3, 1, 1), torch.float32, "plane after add_mean")
+
+
+def mlp_ref(planes, fc, live=True):
+    """The fusion MLP over the plane axis: relu(w2 . relu(W1 v + b1) + b2), v = planes[:, c, y, x].  fc = (w1 [hidden, n], b1, w2 [hidden],
+    b2 [1]); both sums inside the float32 budget in any order.  planes [n,3,H,W] -> [1,3,H,W]."""
+    _threads()
+    w1, b1, w2, b2 = fc
+    h0 = torch.einsum("jn,ncyx->jcyx", w1, planes) + b1.view(-1, 1, 1, 1)
+    a0 = torch.einsum("jn,ncyx->jcyx", w1.abs(), planes.abs()) + b1.abs().view(-1, 1, 1, 1)
+    g1 = min(granularity(w1) * granularity(planes), granularity(b1))
+    check_sum_budget(a0, g1, "fusion MLP layer 1")
+    hid = F.relu(h0)
+    o0 = torch.einsum("j,jcyx->cyx", w2, hid) + b2.view(1, 1, 1)
+    a1 = torch.einsum("j,jcyx->cyx", w2.abs(), hid) + b2.abs().view(1, 1, 1)
+    check_sum_budget(a1, min(granularity(w2) * g1, granularity(b2)), "fusion MLP layer 2")
+    if live:
+        check_live(h0, "fusion MLP hidden sum", min_distinct=50)
+        check_live(o0, "fusion MLP output sum", min_distinct=50)
+    return check_storable(F.relu(o0), torch.float32, "fused frame").unsqueeze(0)
+
+
+def fusion_ref(raw, x, sub, add, fc, S, decimate=False, live=True):
+    """Skip + add_mean + fusion MLP on the raw planes (vsr_sr_fc_planes_skip_f32 and its siblings): `planes_ref` then `mlp_ref`.
+    Choose the MeanShift values dyadic (mean (0.5, 0.25, 0.375), std 1: 255 * mean is a multiple of 1/8) and the MLP's weights small
+    integers or eighths, so that every float32 product and sum is exact in any order."""
+    return mlp_ref(planes_ref(raw, x, sub, add, S, decimate), fc, live=live)
 
 
 # ---------------------------------------------------------------------------------------------------------------- comparison

@@ -258,3 +258,187 @@ def test_planted_bias_slope_and_pixel_defects():
     pred[:, :, 3:6, 0:2] = True
     got = E.conv_ref(x2, w, b, padding=1)
     _expect_footprint(got.to(torch.float32), pre, pred)
+
+
+# ------------------------------------------------------------------------------------------------ the SR net's two ends
+@pytest.mark.parametrize("S", [2, 4])
+@pytest.mark.parametrize("shape", [(1, 1), (1, 2), (2, 1), (3, 5), (7, 4)])
+def test_bilinear_up_ref_is_atens_upsample(S, shape):
+    x = E.ints(np.random.RandomState(S * 10 + shape[1]), (2, 3) + shape, -255, 255, step=0.125)
+    want = torch.nn.functional.interpolate(x, scale_factor=S, mode="bilinear", align_corners=False)
+    assert torch.equal(E.bilinear_up_ref(x, S), want)
+
+
+def test_bilinear_up_ref_budget_checks_fire():
+    x = E.ints(np.random.RandomState(0), (1, 3, 4, 4), -5, 5)
+    with pytest.raises(E.BudgetError, match="not dyadic"):
+        E.bilinear_up_ref(x, 3)
+    big = x.clone()
+    big[0, 1, 2, 3] = 2.0 ** 19 + 1.0          # (2^19 + 1) / 64 needs 26 bits
+    with pytest.raises(E.BudgetError, match="lerp may round"):
+        E.bilinear_up_ref(big, 4)
+
+
+def _tail_case(S, seed=0, N=2, h=5, w=6):
+    rs = np.random.RandomState(seed)
+    k = S + 4
+    return dict(hid=E.ints(rs, (N, 32, h, w), -2, 2), out_w=E.sparse_weights(rs, (32, 32, k, k), 1.0, 1), out_b=E.ints(rs, (32,), -3, 3), out_a=0.25,
+                cv_w=E.sparse_weights(rs, (3, 32, 3, 3), 1.0, 8, step=0.25), cv_b=E.ints(rs, (3,), -200, 200, step=0.5), S=S)
+
+
+@pytest.mark.parametrize("S", [2, 3, 4])
+def test_tail_ref_is_the_stock_composition(S):
+    c = _tail_case(S)
+    ref = E.tail_ref(**c)
+    out = torch.nn.ConvTranspose2d(32, 32, S + 4, S, 2).double()
+    cv = torch.nn.Conv2d(32, 3, 3, padding=1).double()
+    act = torch.nn.PReLU(init=c["out_a"]).double()
+    with torch.no_grad():
+        out.weight.copy_(c["out_w"]), out.bias.copy_(c["out_b"]), cv.weight.copy_(c["cv_w"]), cv.bias.copy_(c["cv_b"])
+        hr = act(out(c["hid"]))
+        want = cv(hr)
+    assert torch.equal(ref["hr"], hr) and torch.equal(ref["raw"], want) and torch.equal(ref["dec"], want[..., ::S, ::S])
+    assert ref["raw"].shape[-2:] == (S * 5, S * 6)
+    # int64 restatement of the deconvolution sum (in quarters after the PReLU)
+    hr0 = deconv_i64(_i(c["hid"]), _i(c["out_w"]), _i(c["out_b"]), S, 2)
+    assert np.array_equal(np.where(hr0 > 0, 4 * hr0, hr0), _i(ref["hr"] * 4))
+
+
+def test_tail_ref_budget_checks_fire():
+    c = _tail_case(4)
+    bad = dict(c, hid=c["hid"] * 64.0)                      # deconvolution sums of a few thousand: quarters of them are not fp16 values
+    with pytest.raises(E.BudgetError, match="tail deconvolution"):
+        E.tail_ref(**bad)
+    bad = dict(c, cv_w=c["cv_w"] + 2.0 ** -12)
+    with pytest.raises(E.BudgetError, match="conv_out weight"):
+        E.tail_ref(**bad)
+    bad = dict(c, cv_b=c["cv_b"] + 2.0 ** -30)              # float32 sum budget
+    with pytest.raises(E.BudgetError, match="conv_out"):
+        E.tail_ref(**bad)
+    with pytest.raises(E.BudgetError, match="PReLU slope"):
+        E.tail_ref(**dict(c, out_a=0.1))
+    with pytest.raises(E.BudgetError, match="non-zero|one sign|distinct"):
+        E.tail_ref(**dict(c, hid=c["hid"] * 0.0, out_b=c["out_b"] * 0.0))
+
+
+def test_fold_ref_is_the_stock_composition_and_checks_its_budget():
+    rs = np.random.RandomState(1)
+    N, h, w = 2, 4, 7
+    a, b = E.ints(rs, (N, 32, h, w), -2, 2), E.ints(rs, (N, 32, h, w), -2, 2)
+    co_w, co_b, cmap = E.sparse_weights(rs, (32, 64), 0.1, 1), E.ints(rs, (32,), -1, 1), E.ints(rs, (32, h, w), -2, 2)
+    got = E.fold_ref(a, b, cmap, co_w, co_b, 0.5)
+    want = torch.nn.functional.prelu(torch.nn.functional.conv2d(torch.cat((a, b), 1), co_w.view(32, 64, 1, 1), co_b) + cmap, torch.tensor([0.5], dtype=torch.float64))
+    assert torch.equal(got, want)
+    with pytest.raises(E.BudgetError, match="compress_out"):
+        E.fold_ref(a * 1024.0, b, cmap, co_w, co_b, 0.5)
+    with pytest.raises(E.BudgetError, match="constant map"):
+        E.fold_ref(a, b, cmap + 2.0 ** -40, co_w, co_b, 0.5)
+
+
+def test_chain_ref_is_the_stock_composition_and_checks_its_budget():
+    rs = np.random.RandomState(2)
+    N, P = 2, 50
+    x = [E.ints(rs, (N, 32, P), -2, 2) for _ in range(3)]
+    w = [E.sparse_weights(rs, (32, 32), 0.15, 1) for _ in range(5)]
+    b = [E.ints(rs, (32,), -2, 2) for _ in range(3)]
+    cmap = E.ints(rs, (32, P), -4, 4, step=0.5)
+    stages = [dict(ins=[(x[0], w[0]), (x[1], w[1])], prev=None, bias=b[0], cmap=cmap, slope=0.5),
+              dict(ins=[(x[2], w[2])], prev=w[3], bias=b[1], cmap=None, slope=0.25),
+              dict(ins=[], prev=w[4], bias=b[2], cmap=None, slope=2.0)]
+    outs = E.chain_ref(stages)
+    F = torch.nn.functional
+    pr = lambda v, a: torch.where(v > 0, v, a * v)
+    c1 = lambda xs, ws, bias: F.conv1d(torch.cat(xs, 1), torch.cat(ws, 1).unsqueeze(-1), bias)
+    s0 = pr(c1([x[0], x[1]], [w[0], w[1]], b[0]) + cmap, 0.5)
+    s1 = pr(c1([x[2], s0], [w[2], w[3]], b[1]), 0.25)
+    s2 = pr(c1([s1], [w[4]], b[2]), 2.0)
+    assert torch.equal(outs[0], s0) and torch.equal(outs[1], s1) and torch.equal(outs[2], s2)
+    with pytest.raises(E.BudgetError, match="chain stage 1"):
+        E.chain_ref([stages[0], dict(stages[1], bias=b[1] + 2.0 ** -20), stages[2]])
+    with pytest.raises(E.BudgetError, match="stage 0 weight"):
+        E.chain_ref([dict(stages[0], ins=[(x[0], w[0] * (1 + 2.0 ** -12))])])
+    with pytest.raises(ValueError, match="no input"):
+        E.chain_ref([dict(stages[2])])
+
+
+def _head_case(f32, seed=3, shape=(2, 6, 9)):
+    rs = np.random.RandomState(seed)
+    N, h, w = shape
+    x = E.ints(rs, (N, 3, h, w), 0, 255 if f32 else 63)
+    if f32:
+        sub = (torch.ones(3, dtype=torch.float64), -255.0 * torch.tensor((0.5, 0.25, 0.375), dtype=torch.float64))
+        return dict(x=x, sub=sub, w_in=E.sparse_weights(rs, (128, 3, 3, 3), 1.0, 3), b_in=E.ints(rs, (128,), -50, 50), a_in=0.5,
+                    w_feat=E.sparse_weights(rs, (32, 128), 1.0, 2), b_feat=E.ints(rs, (32,), -50, 50), a_feat=0.25, store=torch.float32)
+    sub = (torch.tensor((1.0, 0.5, 2.0), dtype=torch.float64), torch.tensor((-31.5, -16.0, -63.0), dtype=torch.float64))   # (fp16: 6-bit pixels, halves)
+    return dict(x=x, sub=sub, w_in=E.sparse_weights(rs, (128, 3, 3, 3), 2.5 / 27, 1), b_in=E.ints(rs, (128,), -4, 4), a_in=0.5,
+                w_feat=E.sparse_weights(rs, (32, 128), 2.0 / 128, 1), b_feat=E.ints(rs, (32,), -4, 4), a_feat=0.25, store=torch.float16)
+
+
+@pytest.mark.parametrize("f32", [False, True])
+def test_head_ref_is_the_stock_composition(f32):
+    c = _head_case(f32)
+    got = E.head_ref(**c)
+    F = torch.nn.functional
+    t = F.conv2d(c["x"], torch.diag(c["sub"][0]).view(3, 3, 1, 1), c["sub"][1])          # MeanShift
+    mid = F.prelu(F.conv2d(t, c["w_in"], c["b_in"], padding=1), torch.tensor([c["a_in"]], dtype=torch.float64))
+    want = F.prelu(F.conv2d(mid, c["w_feat"].view(32, 128, 1, 1), c["b_feat"]), torch.tensor([c["a_feat"]], dtype=torch.float64))
+    assert torch.equal(got, want)
+
+
+def test_head_ref_budget_checks_fire():
+    c = _head_case(False)
+    with pytest.raises(E.BudgetError, match="mean-shifted pixels"):       # 255 + 95.625: eighths above 256
+        E.head_ref(**dict(c, sub=(torch.ones(3, dtype=torch.float64), torch.tensor((127.5, 63.75, 95.625), dtype=torch.float64)),
+                          x=torch.full_like(c["x"], 255.0)))
+    with pytest.raises(E.BudgetError, match="conv_in"):
+        E.head_ref(**dict(c, w_in=torch.ones_like(c["w_in"]), x=torch.full_like(c["x"], 255.0)))
+    with pytest.raises(E.BudgetError, match="feat_in"):
+        E.head_ref(**dict(c, w_feat=torch.ones_like(c["w_feat"]) * 3.0))
+
+
+def _fc(rs, n):
+    w1 = E.sparse_weights(rs, (32, n), 0.7, 2)
+    w2 = torch.from_numpy(rs.randint(1, 5, size=32) * 0.5 * np.where(np.arange(32) % 2 == 0, 1.0, -1.0))      # halves of alternating sign
+    return w1, E.ints(rs, (32,), -60, 60) - 128.0 * w1.sum(1), w2, E.ints(rs, (1,), -40, 40)
+
+
+def _fusion_case(S, dec, n=8, seed=4, shape=(3, 5)):
+    rs = np.random.RandomState(seed)
+    h, w = shape
+    ho, wo = (h, w) if dec else (S * h, S * w)
+    one = torch.ones(3, dtype=torch.float64)
+    mean = 255.0 * torch.tensor((0.5, 0.25, 0.375), dtype=torch.float64)
+    return dict(raw=E.ints(rs, (n, 3, ho, wo), -64, 64, step=0.125), x=E.ints(rs, (n, 3, h, w), 0, 255), sub=(one, -mean), add=(one, mean),
+                fc=_fc(rs, n),
+                S=S, decimate=dec)
+
+
+@pytest.mark.parametrize("dec", [False, True])
+@pytest.mark.parametrize("S", [2, 4])
+def test_fusion_ref_is_the_stock_composition(S, dec):
+    c = _fusion_case(S, dec)
+    got = E.fusion_ref(**c)
+    F = torch.nn.functional
+    eye = torch.eye(3, dtype=torch.float64).view(3, 3, 1, 1)
+    skip = F.interpolate(F.conv2d(c["x"], eye, c["sub"][1]), scale_factor=S, mode="bilinear", align_corners=False)
+    if dec:
+        skip = skip[..., ::S, ::S]
+    planes = F.conv2d(skip + c["raw"], eye, c["add"][1])
+    w1, b1, w2, b2 = c["fc"]
+    v = planes.permute(1, 2, 3, 0)                                               # the MLP runs over the plane axis
+    want = F.relu(F.linear(F.relu(F.linear(v, w1, b1)), w2.view(1, -1), b2)).permute(3, 0, 1, 2)
+    assert got.shape == (1, 3) + planes.shape[2:] and torch.equal(got, want)
+    assert torch.equal(E.planes_ref(c["raw"], c["x"], c["sub"], c["add"], S, dec), planes)
+
+
+def test_fusion_ref_budget_checks_fire():
+    c = _fusion_case(4, False)
+    w1, b1, w2, b2 = c["fc"]
+    with pytest.raises(E.BudgetError, match="layer 1"):
+        E.fusion_ref(**dict(c, fc=(w1 * 2.0 ** 12 + 1.0, b1, w2, b2)))
+    with pytest.raises(E.BudgetError, match="layer 2"):
+        E.fusion_ref(**dict(c, fc=(w1, b1, w2 * 2.0 ** 14 + 0.5, b2)))
+    with pytest.raises(E.BudgetError, match="skip \\+ raw|lerp|bilinear"):
+        E.fusion_ref(**dict(c, raw=c["raw"] + 2.0 ** -20 + 2.0 ** 10))
+    with pytest.raises(E.BudgetError, match="non-zero|one sign|distinct"):
+        E.fusion_ref(**dict(c, fc=(w1 * 0.0, b1 * 0.0 - 1.0, w2, b2)))          # a dead hidden layer

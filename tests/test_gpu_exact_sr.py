@@ -12,8 +12,9 @@ with exactly the predicted footprint.
 
 Out of scope: whole `SRProjectionModule.forward` / `VSR.forward` in exact arithmetic (the mean shifts by 255 * mean, the fusion MLP and
 three recurrent steps leave the exact regime; the oracle tests cover them), the flow operators already compared bit-exactly with
-oracle/native_ops.c, the training kernels of csrc/sr_train.hip (float64 autograd in test_gpu_train_step.py).  The tails (k_tail3,
-k_tail_s2, the x3 tail), the 1x1 chain kernel on its own and the head k_head_h have no exact case yet; they keep their Gaussian tests."""
+oracle/native_ops.c, the training kernels of csrc/sr_train.hip (float64 autograd in test_gpu_train_step.py).  The two ends of the net --
+the head k_head_h, the 1x1 chain kernel on its own, the tails (k_tail3, k_tail_s2, the x3 tail), the fusion kernels and the uint8
+conversions -- have their exact cases in tests/test_gpu_exact_sr_ends.py."""
 import copy
 
 import numpy as np
