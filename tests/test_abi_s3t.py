@@ -1,0 +1,254 @@
+"""CPU-side checks of libvsr_hip_s3t.so (include/vsr_hip_s3t.h): the one-launch x3 tail is a library of its own, built for gfx950 by
+the same `make`; it exports exactly what its header declares, the four other libraries export what they exported and nothing of it,
+both entries validate their arguments before any launch (no compute without a GPU), the host-side packer produces blobs of the sizes
+the library reports with the elements where the header says, and a float64 restatement of the kernel's per-wave tap loops on the
+DECODED blob equals conv_transpose2d -> PReLU -> conv2d (slot order, tap algebra, channel permutation and parameter block are right
+before the first GPU run)."""
+import ctypes
+import os
+import subprocess
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from video_super_resolution_amd import _lib
+
+ENTRIES = ["vsr_s3t_abi_version", "vsr_s3t_last_error", "vsr_s3t_query", "vsr_s3t_sr_tail_f16", "vsr_s3t_sr_tail_fold_f16"]
+UP_BYTES, CV_BYTES, PAR_BYTES, CO_BYTES = 4 * 13 * 2 * 1024, 9 * 1024, 512, 4096 + 256
+
+
+def _exported(path):
+    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+    return sorted(set(ln.split()[-1] for ln in out.splitlines() if " T vsr_" in ln))
+
+
+def test_s3t_library_builds_and_exports_exactly_what_its_header_declares():
+    _lib.build()
+    assert os.path.exists(_lib.S3TLIB_PATH)
+    declared = _lib.declared_symbols(s3t=True)
+    assert declared == ENTRIES
+    assert _exported(_lib.S3TLIB_PATH) == declared
+    lib = _lib.load_s3t()
+    assert lib.vsr_s3t_abi_version() == 1
+    assert lib.vsr_s3t_query(_lib.Q_S3T_STRIP_WIDTH) == 30
+    assert lib.vsr_s3t_query(_lib.Q_S3T_BLOB_BYTES) == UP_BYTES + CV_BYTES + PAR_BYTES
+    assert lib.vsr_s3t_query(_lib.Q_S3T_BLOB_FOLD_BYTES) == UP_BYTES + CV_BYTES + PAR_BYTES + CO_BYTES
+    assert lib.vsr_s3t_query(99) == 0
+    assert "gfx950" in subprocess.run(["strings", _lib.S3TLIB_PATH], capture_output=True, text=True).stdout
+
+
+def test_the_other_four_libraries_export_what_they_exported_before():
+    _lib.build()
+    declared, xdeclared, gdeclared = _lib.declared_symbols(), _lib.declared_symbols(xcheck=True), _lib.declared_symbols(grad=True)
+    s3declared, s3tdeclared = _lib.declared_symbols(s3=True), _lib.declared_symbols(s3t=True)
+    assert len(declared) == 66 and len(gdeclared) == 5 and len(s3declared) == 4
+    assert not set(s3tdeclared) & (set(declared) | set(xdeclared) | set(gdeclared) | set(s3declared))
+    assert _exported(_lib.LIB_PATH) == declared
+    assert _exported(_lib.XLIB_PATH) == sorted(set(declared) | set(xdeclared))
+    assert _exported(_lib.GLIB_PATH) == gdeclared
+    assert _exported(_lib.S3LIB_PATH) == s3declared
+    for path in (_lib.LIB_PATH, _lib.XLIB_PATH, _lib.GLIB_PATH, _lib.S3LIB_PATH):
+        assert not [s for s in _exported(path) if s.startswith("vsr_s3t_")], path
+    assert not [s for s in _exported(_lib.S3TLIB_PATH) if not s.startswith("vsr_s3t_")]
+
+
+# never dereferenced on the host: far apart, so that no range of a refused shape reaches from one into another
+_NULL = ctypes.c_void_p(0)
+_IN, _IN2, _CM, _BLOB, _RAW = (ctypes.c_void_p(0x100000000000 * (i + 1)) for i in range(5))
+
+
+def test_s3t_entries_validate_before_any_launch():
+    T = _lib.load_s3t()
+    plain, fold = T.vsr_s3t_sr_tail_f16, T.vsr_s3t_sr_tail_fold_f16
+
+    def msg():
+        return T.vsr_s3t_last_error()
+
+    for args in ((_NULL, _BLOB, _RAW), (_IN, _NULL, _RAW), (_IN, _BLOB, _NULL)):
+        assert plain(*args, 1, 4, 4, 4, 1, 0, _NULL) == -1 and b"null" in msg()
+    for args in ((_NULL, _IN2, _CM, _BLOB, _RAW), (_IN, _NULL, _CM, _BLOB, _RAW), (_IN, _IN2, _NULL, _BLOB, _RAW), (_IN, _IN2, _CM, _NULL, _RAW),
+                 (_IN, _IN2, _CM, _BLOB, _NULL)):
+        assert fold(*args, 1, 4, 4, 4, 1, 0, _NULL) == -1 and b"null" in msg()
+    for N, h, w, rps in ((0, 4, 4, 4), (-1, 4, 4, 4), (1, 0, 4, 4), (1, 4, -3, 4), (1, 4, 4, -1), (70000, 4, 4, 4)):
+        assert plain(_IN, _BLOB, _RAW, N, h, w, rps, 1, 0, _NULL) == -1 and b"bad shape" in msg(), (N, h, w, rps)
+        assert fold(_IN, _IN2, _CM, _BLOB, _RAW, N, h, w, rps, 1, 0, _NULL) == -1 and b"bad shape" in msg(), (N, h, w, rps)
+    off8 = lambda p: ctypes.c_void_p(p.value + 8)
+    assert plain(off8(_IN), _BLOB, _RAW, 1, 4, 4, 4, 1, 0, _NULL) == -1 and b"aligned" in msg()
+    assert plain(_IN, off8(_BLOB), _RAW, 1, 4, 4, 4, 1, 0, _NULL) == -1 and b"aligned" in msg()
+    assert plain(_IN, _BLOB, ctypes.c_void_p(_RAW.value + 2), 1, 4, 4, 4, 1, 0, _NULL) == -1 and b"aligned" in msg()
+    assert fold(_IN, off8(_IN2), _CM, _BLOB, _RAW, 1, 4, 4, 4, 1, 0, _NULL) == -1 and b"aligned" in msg()
+    assert fold(_IN, _IN2, off8(_CM), _BLOB, _RAW, 1, 4, 4, 4, 1, 0, _NULL) == -1 and b"aligned" in msg()
+    # in / out overlap: the same address, the planes starting inside the input (1 x 4 x 4 x 64 B = 1024 B), the input inside the planes
+    inside = ctypes.c_void_p(_IN.value + 1020)
+    before = ctypes.c_void_p(_IN.value - 16)
+    for raw in (_IN, inside, before):
+        assert plain(_IN, _BLOB, raw, 1, 4, 4, 4, 1, 0, _NULL) == -1 and b"overlap" in msg(), hex(raw.value)
+    assert fold(_IN, _IN2, _CM, _BLOB, _IN2, 1, 4, 4, 4, 1, 0, _NULL) == -1 and b"overlap" in msg()
+    assert fold(_IN, _IN2, _CM, _BLOB, _CM, 1, 4, 4, 4, 1, 0, _NULL) == -1 and b"overlap" in msg()
+    assert plain(_IN, _BLOB, _BLOB, 1, 4, 4, 4, 1, 0, _NULL) == -1 and b"overlap" in msg()
+    # the 4 GiB launch limit names the way out; the constant map has its own
+    assert plain(_IN, _BLOB, _RAW, 8, 3000, 3000, 16, 1, 0, _NULL) == -3 and b"4 GiB" in msg() and b"split the planes" in msg()
+    assert fold(_IN, _IN2, _CM, _BLOB, _RAW, 8, 3000, 3000, 16, 1, 1, _NULL) == -3 and b"split the planes" in msg()
+    assert fold(_IN, _IN2, _CM, _BLOB, _RAW, 1, 8192, 4096, 16, 1, 1, _NULL) == -3 and b"constant map" in msg()
+    assert plain(_IN, _BLOB, _RAW, 1, 70000, 8, 1, 1, 0, _NULL) == -1 and b"row segments" in msg()
+    assert fold(_IN, _IN2, _CM, _BLOB, _RAW, 1, 70000, 8, 1, 1, 0, _NULL) == -1 and b"row segments" in msg()
+
+
+def test_check_reports_from_the_s3t_librarys_own_buffer():
+    T = _lib.load_s3t()
+    rc = T.vsr_s3t_sr_tail_f16(_IN, _BLOB, _RAW, 1, 4, 0, 4, 1, 0, None)
+    with pytest.raises(_lib.VsrHipError, match=r"sr_tail_s3_f16 failed \(-1\): s3t_sr_tail: bad shape \(N 1, h 4, w 0, rows_per_seg 4\)"):
+        _lib.check(rc, "sr_tail_s3_f16", lib=T)
+    # ... and the x3 stage's library keeps its own message
+    S = _lib.load_s3()
+    S.vsr_s3_sr_utd_f16(_IN, _BLOB, _RAW, 1, 0, 4, 4, 1, None)
+    assert b"s3_sr_utd" in S.vsr_s3_last_error() and b"s3t_sr_tail" in T.vsr_s3t_last_error()
+
+
+def _operands(seed=0):
+    g = torch.Generator().manual_seed(seed)
+    out_w = torch.randn(32, 32, 7, 7, generator=g) * 0.05
+    out_b, cv_b = torch.randn(32, generator=g), torch.randn(3, generator=g)
+    cv_w = torch.randn(3, 32, 3, 3, generator=g) * 0.1
+    co_w, co_b = torch.randn(32, 192, generator=g), torch.randn(32, generator=g)
+    return out_w, out_b, cv_w, cv_b, co_w, co_b
+
+
+def _perm(g, j):
+    return 4 * g + j if j < 4 else 16 + 4 * g + (j - 4)
+
+
+def test_pack_tail_s3_blob_on_cpu_tensors_has_the_queried_sizes_and_the_headers_layout():
+    from video_super_resolution_amd.sr import _S3_PHASES, _s3_taps, pack_tail_s3_blob, pack_utd_s3_blob
+    out_w, out_b, cv_w, cv_b, co_w, co_b = _operands()
+    T = _lib.load_s3t()
+    plain = pack_tail_s3_blob(out_w, out_b, 0.25, cv_w, cv_b)
+    fold = pack_tail_s3_blob(out_w, out_b, 0.25, cv_w, cv_b, fold_co=(co_w, (64, 160), co_b, -0.5))
+    assert plain.dtype == torch.uint8 and plain.numel() == T.vsr_s3t_query(_lib.Q_S3T_BLOB_BYTES)
+    assert fold.dtype == torch.uint8 and fold.numel() == T.vsr_s3t_query(_lib.Q_S3T_BLOB_FOLD_BYTES)
+    assert torch.equal(fold[:plain.numel()], plain)
+    # the up fragments ARE the up half of the stage's blob (same phase sets, same slot order)
+    stage = pack_utd_s3_blob(out_w, out_b, 0.25, torch.zeros(32, 96), 32, torch.zeros(32), 1.0, torch.zeros(32, 32, 7, 7), torch.zeros(32), 1.0)
+    assert torch.equal(plain[:UP_BYTES], stage[:UP_BYTES])
+    up = plain[:UP_BYTES].view(torch.float16).view(4, 13, 2, 64, 8)
+    # wave 3, phase (2, 0) is its second: slots 4..7; its taps (ky, kx) = (1, 2) (1, 5) (4, 2) (4, 5)
+    assert _S3_PHASES[3][1] == (2, 0) and _s3_taps(2) == [1, 4] and _s3_taps(0) == [2, 5]
+    lane, j, mt = 37, 5, 1
+    assert up[3, 6, mt, lane, j] == out_w[8 * (lane >> 4) + j, 16 * mt + (lane & 15), 4, 2].half()
+    assert up[0, 0, 0, lane, j] == out_w[8 * (lane >> 4) + j, lane & 15, 0, 0].half()          # wave 0, phase (1, 1), tap (0, 0)
+    assert not up[1:, 12].any()                                                                # waves 1-3 have 12 taps
+    cv = plain[UP_BYTES:UP_BYTES + CV_BYTES].view(torch.float16).view(3, 3, 64, 8)
+    lane, j = 16 * 2 + 1, 6                                                                    # output channel 1, lane group 2
+    assert cv[2, 0, lane, j] == cv_w[1, _perm(2, j), 2, 0].half()
+    assert not cv[:, :, [l for l in range(64) if (l & 15) >= 3]].any()
+    fpar = plain[UP_BYTES + CV_BYTES:].view(torch.float32)
+    assert fpar.numel() == 128 and torch.equal(fpar[:32], out_b) and torch.equal(fpar[32:35], cv_b) and fpar[96] == 0.25
+    assert not fpar[35:96].any() and not fpar[97:].any()
+    co = fold[plain.numel():plain.numel() + 4096].view(torch.float16).view(2, 2, 64, 8)
+    lane, j = 53, 3
+    assert co[1, 1, lane, j] == co_w[16 + (lane & 15), 160 + 8 * (lane >> 4) + j].half()
+    assert co[0, 0, lane, j] == co_w[lane & 15, 64 + 8 * (lane >> 4) + j].half()
+    cpar = fold[plain.numel() + 4096:].view(torch.float32)
+    assert cpar.numel() == 64 and torch.equal(cpar[:32], co_b) and cpar[32] == -0.5 and not cpar[33:].any()
+
+
+# ---- the kernel's constexpr helpers, restated (csrc/sr_tail_s3.hip)
+def _ph(wv):
+    return (((1, 1), (0, 0)), ((0, 1), (2, 1)), ((1, 0), (1, 2)), ((0, 2), (2, 0), (2, 2)))[wv]
+
+
+def _tap_ok(x, d):
+    return 0 <= x + 2 - 3 * d <= 6
+
+
+def _tap_slot(wv, p, dy, dx):
+    cnt = lambda x: 3 if x == 1 else 2
+    rank = lambda x, d: 1 - d - (1 if x == 0 else 0)
+    base = sum(cnt(r) * cnt(c) for r, c in _ph(wv)[:p])
+    r, c = _ph(wv)[p]
+    return base + rank(r, dy) * cnt(c) + rank(c, dx)
+
+
+def _emulate(blob, hid, fold_in=None):
+    """The kernel's arithmetic in float64 on the DECODED blob, on whole planes: hid [N,32,h,w] float64 (fp16 values) -> raw [N,3,3h,3w].
+    fold_in = (lr3, lr6, cmap [32,h,w]): the LR load path of the FOLD build first."""
+    up = blob[:UP_BYTES].view(torch.float16).view(4, 13, 2, 64, 8).double()
+    cv = blob[UP_BYTES:UP_BYTES + CV_BYTES].view(torch.float16).view(3, 3, 64, 8).double()
+    fpar = blob[UP_BYTES + CV_BYTES:UP_BYTES + CV_BYTES + PAR_BYTES].view(torch.float32).double()
+    b_out, b_cv, a_out = fpar[:32], fpar[32:35], float(fpar[96])
+    lanes = torch.arange(64)
+    row, g = lanes & 15, lanes >> 4
+
+    def matrix(frag, natural=True):   # [mt 2][lane 64][8] -> W[co 32][ci 32]
+        W = torch.zeros(32, 32, dtype=torch.float64)
+        for mt in range(2):
+            for j in range(8):
+                ci = 8 * g + j if natural else torch.tensor([_perm(int(gg), j) for gg in g])
+                W[16 * mt + row, ci] = frag[mt, :, j]
+        return W
+
+    prelu16 = lambda v, a: (lambda q: torch.where(q >= 0, q, (q * a).half().double()))(v.half().double())
+    if fold_in is not None:
+        lr3, lr6, cmap = fold_in
+        co = blob[UP_BYTES + CV_BYTES + PAR_BYTES:][:4096].view(torch.float16).view(2, 2, 64, 8).double()
+        cpar = blob[UP_BYTES + CV_BYTES + PAR_BYTES + 4096:].view(torch.float32).double()
+        s = cpar[:32].view(1, 32, 1, 1) + cmap.unsqueeze(0)
+        s = s + torch.einsum("oc,nchw->nohw", matrix(co[0]), lr3) + torch.einsum("oc,nchw->nohw", matrix(co[1]), lr6)
+        hid = prelu16(s, float(cpar[32]))
+    N, _, h, w = hid.shape
+    lr = F.pad(hid, (1, 1, 1, 1))   # rows / columns -1 .. h / w: the zero rows the buffer loads return
+    hr = torch.zeros(N, 32, 3 * h, 3 * w, dtype=torch.float64)
+    seen = torch.zeros(3 * h, 3 * w, dtype=torch.int32)
+    for wv in range(4):
+        for p, (r, c) in enumerate(_ph(wv)):
+            acc = b_out.view(1, 32, 1, 1).expand(N, 32, h, w).clone()
+            for di in (1, 0, -1):
+                if not _tap_ok(r, di):
+                    continue
+                for dj in (1, 0, -1):
+                    if not _tap_ok(c, dj):
+                        continue
+                    W = matrix(up[wv, _tap_slot(wv, p, di, dj)])
+                    acc += torch.einsum("oc,nchw->nohw", W, lr[:, :, 1 + di:1 + di + h, 1 + dj:1 + dj + w])
+            hr[:, :, r::3, c::3] = prelu16(acc, a_out)
+            seen[r::3, c::3] += 1
+    assert (seen == 1).all()
+    hrp = F.pad(hr, (1, 1, 1, 1))
+    raw = b_cv.view(1, 3, 1, 1).expand(N, 3, 3 * h, 3 * w).clone()
+    for dy in range(3):
+        for dx in range(3):
+            Wc = torch.zeros(3, 32, dtype=torch.float64)
+            for gg in range(4):
+                for j in range(8):
+                    Wc[:, _perm(gg, j)] = cv[dy, dx, 16 * gg:16 * gg + 3, j]
+            raw += torch.einsum("oc,nchw->nohw", Wc, hrp[:, :, dy:dy + 3 * h, dx:dx + 3 * w])
+    return hr, raw
+
+
+@pytest.mark.parametrize("slope", [0.25, -0.5, 2.0])
+def test_float64_restatement_of_the_tap_loops_on_the_decoded_blob(slope):
+    from video_super_resolution_amd.sr import pack_tail_s3_blob
+    out_w, out_b, cv_w, cv_b, co_w, co_b = _operands(1)
+    g = torch.Generator().manual_seed(2)
+    N, h, w = 2, 5, 7
+    hid = torch.randn(N, 32, h, w, generator=g).half().double()
+    blob = pack_tail_s3_blob(out_w, out_b, slope, cv_w, cv_b, fold_co=(co_w, (64, 160), co_b, 0.5))
+    hr, raw = _emulate(blob, hid)
+    prelu16 = lambda v, a: (lambda q: torch.where(q >= 0, q, (q * a).half().double()))(v.half().double())
+    w16, cv16 = out_w.half().double(), cv_w.half().double()
+    want_hr = prelu16(F.conv_transpose2d(hid, w16, out_b.double(), stride=3, padding=2), slope)
+    want = F.conv2d(want_hr, cv16, cv_b.double(), padding=1)
+    assert tuple(raw.shape) == (N, 3, 3 * h, 3 * w)
+    # the same products in another order: float64 rounding of the sums, and the rare HR value that another order rounds to the
+    # neighbouring fp16 (one unit at 2^-11 relative, through one conv_out weight)
+    assert (hr - want_hr).abs().max() <= 2.0 ** -10 * want_hr.abs().max()
+    assert (raw - want).abs().max() <= 2e-3 * want.abs().max()
+    # FOLD: the LR load path against compress_out (two slices of its matrix) -> PReLU -> the plain tail
+    lr3, lr6 = (torch.randn(N, 32, h, w, generator=g).half().double() for _ in range(2))
+    cmap = torch.randn(32, h, w, generator=g).double()
+    s = F.conv2d(torch.cat((lr3, lr6), 1), torch.cat((co_w[:, 64:96], co_w[:, 160:192]), 1).half().double().view(32, 64, 1, 1), co_b.double()) + cmap
+    hid2 = prelu16(s, 0.5)
+    _, raw_f = _emulate(blob, None, fold_in=(lr3, lr6, cmap))
+    _, raw_p = _emulate(blob, hid2)
+    assert (raw_f - raw_p).abs().max() <= 2e-3 * raw_p.abs().max()

@@ -1,5 +1,6 @@
 """ctypes binding of libvsr_hip.so (the C ABI declared in include/vsr_hip.h), of libvsr_hip_grad.so (include/vsr_hip_grad.h:
-the backward of the three native flow operators) and of libvsr_hip_s3.so (include/vsr_hip_s3.h: the fused x3 stage of the SR net).
+the backward of the three native flow operators), of libvsr_hip_s3.so (include/vsr_hip_s3.h: the fused x3 stage of the SR net) and of
+libvsr_hip_s3t.so (include/vsr_hip_s3t.h: the one-launch x3 tail).
 
 There is deliberately no CPU or eager-PyTorch fallback behind these entry points: if the
 shared library is missing, or an operator is handed a non-CUDA tensor, the call raises.
@@ -23,10 +24,13 @@ GLIB_PATH = os.path.join(_PKG, "libvsr_hip_grad.so")
 GHEADER_PATH = os.path.join(_ROOT, "include", "vsr_hip_grad.h")
 S3LIB_PATH = os.path.join(_PKG, "libvsr_hip_s3.so")
 S3HEADER_PATH = os.path.join(_ROOT, "include", "vsr_hip_s3.h")
+S3TLIB_PATH = os.path.join(_PKG, "libvsr_hip_s3t.so")
+S3THEADER_PATH = os.path.join(_ROOT, "include", "vsr_hip_s3t.h")
 _lib = None
 _xlib = None
 _glib = None
 _s3lib = None
+_s3tlib = None
 # the cross-check library instead of the shipping one for every call (set by `xcheck()`; the environment switch serves the
 # measurement tools, whose VSR_TUNING codes only that library understands)
 _use_x = os.environ.get("VSR_USE_XCHECK", "0") == "1" or bool(os.environ.get("VSR_TUNING", "").strip())
@@ -37,8 +41,8 @@ class VsrHipError(RuntimeError):
 
 
 def build(verbose: bool = False) -> str:
-    """Compile every HIP source for gfx950 into the in-tree libvsr_hip.so, libvsr_hip_xcheck.so, libvsr_hip_grad.so and
-    libvsr_hip_s3.so (hipcc cross-compiles without a GPU)."""
+    """Compile every HIP source for gfx950 into the in-tree libvsr_hip.so, libvsr_hip_xcheck.so, libvsr_hip_grad.so,
+    libvsr_hip_s3.so and libvsr_hip_s3t.so (hipcc cross-compiles without a GPU)."""
     cmd = ["make", "-j4", "-C", os.path.join(_PKG, "csrc")]
     if not verbose:
         cmd.insert(1, "-s")
@@ -46,10 +50,10 @@ def build(verbose: bool = False) -> str:
     return LIB_PATH
 
 
-def declared_symbols(xcheck: bool = False, grad: bool = False, s3: bool = False) -> list:
-    """Entry points include/vsr_hip.h declares (xcheck: the ones include/vsr_hip_xcheck.h adds; grad / s3: the ones of
-    include/vsr_hip_grad.h / include/vsr_hip_s3.h, libraries of their own)."""
-    with open(S3HEADER_PATH if s3 else GHEADER_PATH if grad else XHEADER_PATH if xcheck else HEADER_PATH) as f:
+def declared_symbols(xcheck: bool = False, grad: bool = False, s3: bool = False, s3t: bool = False) -> list:
+    """Entry points include/vsr_hip.h declares (xcheck: the ones include/vsr_hip_xcheck.h adds; grad / s3 / s3t: the ones of
+    include/vsr_hip_grad.h / include/vsr_hip_s3.h / include/vsr_hip_s3t.h, libraries of their own)."""
+    with open(S3THEADER_PATH if s3t else S3HEADER_PATH if s3 else GHEADER_PATH if grad else XHEADER_PATH if xcheck else HEADER_PATH) as f:
         text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
     return sorted(set(re.findall(r"\b(vsr_[a-z0-9_]+)\s*\(", text)))
 
@@ -115,6 +119,21 @@ def load_s3() -> ctypes.CDLL:
     return _s3lib
 
 
+def load_s3t() -> ctypes.CDLL:
+    """libvsr_hip_s3t.so (include/vsr_hip_s3t.h): the one-launch tail of the x3 geometry (csrc/sr_tail_s3.hip).  Its own error
+    buffer: `check(rc, what, lib=load_s3t())`."""
+    global _s3tlib
+    if _s3tlib is None:
+        lib = _dlopen(S3TLIB_PATH)
+        lib.vsr_s3t_last_error.restype = ctypes.c_char_p
+        lib.vsr_last_error = lib.vsr_s3t_last_error   # the name `check` reads a library's message under
+        lib.vsr_s3t_query.restype = ctypes.c_size_t
+        if lib.vsr_s3t_abi_version() != 1:
+            raise VsrHipError(f"{os.path.basename(S3TLIB_PATH)}: ABI version mismatch")
+        _s3tlib = lib
+    return _s3tlib
+
+
 def load() -> ctypes.CDLL:
     """The library every product call goes through: libvsr_hip.so, unless a test / tool asked for the cross-check library."""
     global _lib
@@ -144,6 +163,8 @@ class xcheck:
 Q_UTD_BLOB_BYTES, Q_UTD_STRIP_WIDTH, Q_UTD_S2_BLOB_BYTES, Q_UTD_S2_STRIP_WIDTH, Q_TAIL_S2_BLOB_BYTES = range(5)
 # vsr_s3_query codes (include/vsr_hip_s3.h)
 Q_S3_BLOB_BYTES, Q_S3_STRIP_WIDTH = range(2)
+# vsr_s3t_query codes (include/vsr_hip_s3t.h)
+Q_S3T_BLOB_BYTES, Q_S3T_BLOB_FOLD_BYTES, Q_S3T_STRIP_WIDTH = range(3)
 
 
 def check(rc: int, what: str = "", lib=None) -> None:

@@ -215,6 +215,11 @@ class SRProjectionModule(nn.Module):
                                                  self.conv_out[0].bias,
                                                  fold_co=(P["co_w"], (_NF * 2, _NF * 5), P["co_b"], P["co_a"]) if G == 6 else None)
                 P["tail_s2_fold"] = G == 6   # compress_out reads exactly two live maps (lr3, lr6): folded into the tail's LR load path
+            if self.upscale_factor == 3 and self.fused_tail_s3:
+                P["tail_s3"] = pack_tail_s3_blob(self.out[0].weight, self.out[0].bias, P["out_a"], self.conv_out[0].weight,
+                                                 self.conv_out[0].bias,
+                                                 fold_co=(P["co_w"], (_NF * 2, _NF * 5), P["co_b"], P["co_a"]) if G == 6 else None)
+                P["tail_s3_fold"] = G == 6   # as at x2
             self._pack, self._pack_key = P, key
             self._const.clear()
             self._const_nhwc.clear()
@@ -360,7 +365,7 @@ class SRProjectionModule(nn.Module):
         """The FeedbackBlock maps of the FIRST `shared["n"]` planes of a later `forward(x, shared=shared)` call, computed ahead of
         it: `x_first` [n,3,h,w] are those planes, `live` = {3: buf, 6: buf} the caller's [planes,h*w,32] half buffers the maps go
         into (rows 0..n-1; the later calls write their own planes beside them); optional `live["prefc"]`: a [planes,3,Sh,Sw] float32
-        buffer -- the first planes' pre-fusion tail output is then evaluated too (x4 folded tail, x2 one-launch tail), and the later
+        buffer -- the first planes' pre-fusion tail output is then evaluated too (x4 folded tail, x2 / x3 one-launch tail), and the later
         calls run their tail on the other planes only.  The planes are independent up to the fusion
         MLP, so VSR.forward runs this on a side stream next to the guidance trunks, which the LR frames do not depend on
         (video_super_resolution.py:26-40): same kernels on the same values as the call that evaluated all planes at once
@@ -652,7 +657,9 @@ class SRProjectionModule(nn.Module):
     fused_s2 = True    # scale 2: the stage on k_utd_s2 (csrc/sr_utd_s2.hip); False: the unfused launches (cross-check).
                        # (read when the weights are packed: change it before the first forward or bump a parameter)
     fused_s3 = True    # scale 3: the stage on k_utd_s3 (csrc/sr_utd_s3.hip, libvsr_hip_s3.so); False: the unfused launches (cross-check).
-                       # (read when the weights are packed, as fused_s2; the x3 tail stays on _tail_unfused either way)
+                       # (read when the weights are packed, as fused_s2; the x3 tail has a switch of its own, below)
+    fused_tail_s3 = True   # scale 3: `out` deconvolution + conv_out on k_tail_s3 (csrc/sr_tail_s3.hip, libvsr_hip_s3t.so: one launch, the x3 map
+                           # stays in LDS); False: nine phase convolutions + k_convout_planes (cross-check).  Read when the weights are packed.
 
     utd_s2_build = int(os.environ.get("VSR_UTD_S2_BUILD", "1"))   # x2 stage: 1 = k_utd_s2 (default), 2 = k_utd_s2w (32x32x16 MFMA, one wave per SIMD: measured 5 % slower, LAB_NOTES R5.8)
     fuse_uptran = os.environ.get("VSR_UTD_POST", "1") != "0"   # the uptran 1x1 between the two stages of a step inside the first stage's launch
@@ -821,11 +828,11 @@ class SRProjectionModule(nn.Module):
                                                   int(P["slopes_le_one"]), 0, L.stream()), "sr_tail3_fold_f16")
                 L.TIMER.stop(tok)
                 shared["prefc_all"] = pre
-            elif (pre is not None and self.upscale_factor != 4 and "tail_s2" in P and tuple(pre.shape) == (N_tot, 3, self.upscale_factor * h, self.upscale_factor * w) and
+            elif (pre is not None and self.upscale_factor != 4 and self._tail_key(P) and tuple(pre.shape) == (N_tot, 3, self.upscale_factor * h, self.upscale_factor * w) and
                   len(co(live)["ins"]) <= 2):
-                # scale 2: the same for the one-launch tail of csrc/sr_tail_s2.hip (compress_out of the kept maps inside its LR load path,
-                # or -- cross-check -- as its own launch first)
-                fold = self._fold_s2(P, live, N, h, w, cmap_nhwc)
+                # scale 2 / 3: the same for the one-launch tails of csrc/sr_tail_s2.hip / sr_tail_s3.hip (compress_out of the kept maps inside
+                # their LR load path, or -- cross-check -- as its own launch first)
+                fold = self._fold_tail(P, live, N, h, w, cmap_nhwc)
                 hid = fold[0] if fold else self._chain([co(live)], N, hp, keep=[True])[0].view(N, h, w, _NF)
                 self._tail_raw(hid, P, False, pre[:N], cus=2 * getattr(self, "_utd_cus", 256), fold=fold)
                 shared["prefc_all"] = pre
@@ -844,10 +851,10 @@ class SRProjectionModule(nn.Module):
             nt = n0 if (pre is not None and tuple(pre.shape) == (N, 3, S * h, S * w) and pre.device == dev and len(co(live)["ins"]) <= 2) else 0
             if nt:
                 live_t = {k: v[nt:] for k, v in live.items()}
-                fold = self._fold_s2(P, live_t, N - nt, h, w, cmap_nhwc)
+                fold = self._fold_tail(P, live_t, N - nt, h, w, cmap_nhwc)
                 hid = fold[0] if fold else self._chain([co(live_t)], N - nt, hp, keep=[True])[0].view(N - nt, h, w, _NF)
                 return self._tail_unfused(x, hid, P, decimate, taps, pre=pre, fold=fold)
-            fold = self._fold_s2(P, live, N, h, w, cmap_nhwc) if taps is None else None
+            fold = self._fold_tail(P, live, N, h, w, cmap_nhwc) if taps is None else None
             if fold:
                 return self._tail_unfused(x, fold[0], P, decimate, taps, fold=fold)
             hid = self._chain([co(live)], N, hp, keep=[True])[0] if len(co(live)["ins"]) <= 2 else \
@@ -912,18 +919,42 @@ class SRProjectionModule(nn.Module):
             taps[f"prefc{self.num_steps - 1}"] = prefc
         return out
 
-    def _fold_s2(self, P, live, N, h, w, cmap_nhwc):
-        """(lr3, lr6 as [N,h,w,32] views, constant map) when the x2 tail applies compress_out itself (vsr_sr_tail_s2_fold_f16), else None."""
-        if not (self.fold_tail and P.get("tail_s2_fold") and "tail_s2" in P and sorted(k for k in live if k > 0) == [3, 6]) or L._use_x:
+    def _tail_key(self, P):
+        """Key of this scale's one-launch tail blob in the pack ("tail_s2" / "tail_s3"), or None: x4 (its tails are routed before this is
+        asked) and the unfused cross-check routes."""
+        key = {2: "tail_s2", 3: "tail_s3"}.get(self.upscale_factor)
+        return key if key in P else None
+
+    def _fold_tail(self, P, live, N, h, w, cmap_nhwc):
+        """(lr3, lr6 as [N,h,w,32] views, constant map) when this scale's one-launch tail applies compress_out itself
+        (vsr_sr_tail_s2_fold_f16, vsr_s3t_sr_tail_fold_f16), else None."""
+        key = self._tail_key(P)
+        if not (self.fold_tail and key and P.get(key + "_fold") and sorted(k for k in live if k > 0) == [3, 6]) or L._use_x:
             return None
         return live[3].view(N, h, w, _NF), live[6].view(N, h, w, _NF), cmap_nhwc
 
     def _tail_raw(self, hid, P, decimate, raw, cus=512, fold=None):
         """`out` DeconvBlock -> conv_out 3x3 of the planes of `hid` [n,h,w,32] into `raw` [n,3,.,.] (rows of the caller's tensor).
-        fold (scale 2, `_fold_s2`): `hid` is not materialised -- the kernel forms it from the two live maps."""
+        fold (scale 2 / 3, `_fold_tail`): `hid` is not materialised -- the kernel forms it from the two live maps."""
         lib = L.load()
         N, h, w, _ = hid.shape
         S = self.upscale_factor
+        if S == 3 and "tail_s3" in P:   # scale 3: the same in csrc/sr_tail_s3.hip, a library of its own (planes split by its 4 GiB limit alone)
+            lib3 = L.load_s3t()
+            nbt = max(1, min(N, ((1 << 32) - 32) // (h * w * _NF * 2)))
+            for n0 in range(0, N, nbt):
+                n = min(nbt, N - n0)
+                tok = L.TIMER.start("sr_tail_s3_dec_f16" if decimate else "sr_tail_s3_f16") if L.TIMER.enabled else None
+                rows = self._rows_per_segment(n, h, w, cus=cus, strip=30)
+                if fold:
+                    L.check(lib3.vsr_s3t_sr_tail_fold_f16(L.dptr(fold[0][n0:n0 + n], torch.float16), L.dptr(fold[1][n0:n0 + n], torch.float16), L.dptr(fold[2]),
+                                                          L.dptr(P["tail_s3"], torch.uint8), L.dptr(raw[n0:n0 + n]), n, h, w, rows,
+                                                          int(P["slopes_le_one"]), int(decimate), L.stream()), "sr_tail_s3_fold_f16", lib=lib3)
+                else:
+                    L.check(lib3.vsr_s3t_sr_tail_f16(L.dptr(hid[n0:n0 + n], torch.float16), L.dptr(P["tail_s3"], torch.uint8), L.dptr(raw[n0:n0 + n]),
+                                                     n, h, w, rows, int(P["slopes_le_one"]), int(decimate), L.stream()), "sr_tail_s3_f16", lib=lib3)
+                L.TIMER.stop(tok)
+            return
         nb = _planes_per_chunk(N, S * h, S * w)
         if "tail_s2" in P:   # scale 2: deconvolution + conv_out in one launch, the x2 map stays in LDS (csrc/sr_tail_s2.hip)
             nbt = max(1, min(N, ((1 << 32) - 32) // (h * w * _NF * 2)))
@@ -1237,6 +1268,66 @@ def pack_utd_s3_blob(up_w, up_b, up_a, tr_w, tr_col0, tr_b, tr_a, dn_w, dn_b, dn
     fpar[0:32], fpar[32:64], fpar[64:96] = up_b.detach().float(), tr_b.detach().float(), dn_b.detach().float()
     fpar[96], fpar[97], fpar[98] = float(up_a), float(tr_a), float(dn_a)
     blob[o_f:o_f + 512] = fpar.view(torch.uint8)
+    return blob
+
+
+def pack_tail_s3_blob(out_w, out_b, out_a, cv_w, cv_b, fold_co=None) -> torch.Tensor:
+    """Weights of the fused x3 tail (csrc/sr_tail_s3.hip, include/vsr_hip_s3t.h): the `out` ConvTranspose2d [32,32,7,7] in k_utd_s3's
+    per-wave slot order (_S3_PHASES / _s3_taps, the `up` half of pack_utd_s3_blob), conv_out [3,32,3,3] as nine A fragments whose rows
+    0-2 are its output channels (k index in the accumulator-derived channel order of the HR ring), then b_out[32], b_cv[3] and the
+    PReLU slope.  fold_co = (w [32,ld], (col_a, col_b), b [32], a): compress_out over two live maps, for vsr_s3t_sr_tail_fold_f16
+    (the blob is then VSR_S3T_Q_BLOB_FOLD_BYTES long; the plain entry reads its first VSR_S3T_Q_BLOB_BYTES)."""
+    dev = out_w.device
+    lib = L.load_s3t()
+    nplain = int(lib.vsr_s3t_query(L.Q_S3T_BLOB_BYTES))
+    nbytes = nplain if fold_co is None else int(lib.vsr_s3t_query(L.Q_S3T_BLOB_FOLD_BYTES))
+    lane = torch.arange(64, device=dev)
+    row, g = lane & 15, lane >> 4
+    perm = _chunk_channel_order(dev)
+    MT = torch.arange(2, device=dev).view(2, 1, 1)
+    # deconv: A[co][k = 8 g + j] in natural channel order (the B operand comes straight from the LR rows)
+    co_n, ci_n = torch.broadcast_tensors(16 * MT + row.view(1, 64, 1), 8 * g.view(1, 64, 1) + torch.arange(8, device=dev).view(1, 1, 8))
+    upw = out_w.detach().float()
+    slots = 13
+    up_frag = torch.zeros((4, slots, 2, 64, 8), dtype=torch.float16, device=dev)
+    for wv, phases in enumerate(_S3_PHASES):
+        t = 0
+        for r, c in phases:
+            for ky in _s3_taps(r):
+                for kx in _s3_taps(c):
+                    up_frag[wv, t] = upw[ci_n, co_n, ky, kx].to(torch.float16)
+                    t += 1
+        assert t <= slots
+    cv = torch.zeros((3, 3, 64, 8), dtype=torch.float32, device=dev)
+    live = row < 3
+    w = cv_w.detach().float()
+    for dy in range(3):
+        for dx in range(3):
+            cv[dy, dx, live] = w[row[live].unsqueeze(1), perm[g[live]], dy, dx]
+    blob = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+    o_cv = 4 * slots * 2 * 1024
+    o_f = o_cv + 9 * 1024
+    assert nplain == o_f + 512
+    blob[0:o_cv] = up_frag.contiguous().view(torch.uint8).reshape(-1)
+    blob[o_cv:o_f] = cv.to(torch.float16).contiguous().view(torch.uint8).reshape(-1)
+    fpar = torch.zeros(128, dtype=torch.float32, device=dev)
+    fpar[0:32] = out_b.detach().float()
+    fpar[32:35] = cv_b.detach().float()
+    fpar[96] = float(out_a)
+    blob[o_f:o_f + 512] = fpar.view(torch.uint8)
+    if fold_co is not None:
+        co_w, cols, co_b, co_a = fold_co
+        o_co = nplain
+        assert nbytes == o_co + 4096 + 256
+        T2 = torch.tensor(list(cols), device=dev).view(2, 1, 1, 1)
+        MT2 = torch.arange(2, device=dev).view(1, 2, 1, 1)
+        co_, ci_ = torch.broadcast_tensors(16 * MT2 + row.view(1, 1, 64, 1),
+                                           T2 + 8 * g.view(1, 1, 64, 1) + torch.arange(8, device=dev).view(1, 1, 1, 8))   # natural order: the raw maps
+        blob[o_co:o_co + 4096] = co_w.detach().float()[co_, ci_].to(torch.float16).contiguous().view(torch.uint8).reshape(-1)
+        cpar = torch.zeros(64, dtype=torch.float32, device=dev)
+        cpar[0:32] = co_b.detach().float()
+        cpar[32] = float(co_a)
+        blob[o_co + 4096:o_co + 4096 + 256] = cpar.view(torch.uint8)
     return blob
 
 
