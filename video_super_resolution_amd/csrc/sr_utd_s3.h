@@ -1,0 +1,376 @@
+// sr_utd_s3.h -- k_utd_s3 / k_utd_s3_post: the fused  up (deconv k7 s3 p2 + PReLU) -> tran (1x1 + PReLU) -> down (conv k7 s3 p2 + PReLU)
+// stage of the FeedbackBlock for the scale-3 extension (SRFBN's (7, 3, 2) row, sr.py:sr_geometry, under the zero-fill
+// semantic).  The x3 feature map (9 x h x w x 32 fp16 per plane: 4.2 GB per tensor at LR 720x1280 x 8 planes) never leaves the
+// registers; the unfused build (sr.py:_UnfusedStage: nine phase deconvolutions, in-place 1x1, strided convolution on the generic
+// kernel) moves it through HBM about four times and is kept as the cross-check.  The kernel text lives here once: sr_utd_s3.hip
+// (libvsr_hip_s3.so, include/vsr_hip_s3.h) instantiates the plain build, sr_utd_s3p.hip (libvsr_hip_s3p.so, include/vsr_hip_s3p.h) the
+// POST build, which also applies the next group's uptran 1x1 to its finished rows.
+//
+// Design = k_utd_s2's (sr_utd_s2.hip) with the x3 geometry:
+//   * a workgroup of 4 waves marches down a strip of 30 LR columns; step m handles the HR row TRIPLE m (rows 3m, 3m+1, 3m+2)
+//     at the 32 deconv positions q = x0-1 .. x0+30 (2 MFMA pixel tiles).  LR rows m-1, m, m+1 sit in a 4-row LDS ring.
+//   * tap algebra of (7, 3, 2): HR row 3m+r takes kernel row ky = r + 2 - 3 di from LR row m+di, so r = 0 has ky {2, 5} (di 0, -1),
+//     r = 1 has {0, 3, 6} (di +1, 0, -1), r = 2 has {1, 4} (di +1, 0); columns alike.  The nine phases (r, c) have
+//     4 6 4 / 6 9 6 / 4 6 4 taps, 49 in all.  The down-convolution mirrors it: HR row 3m+r is kernel row r + 2 - 3 d of output row
+//     m+d, HR column 3q+c kernel column c + 2 - 3 e of output pixel q+e.
+//   * the imbalance is dealt with by giving the waves phase SETS of equal tap count instead of a row or a column phase each:
+//         wave 0: (1,1) (0,0)          9 + 4     = 13 taps
+//         wave 1: (0,1) (2,1)          6 + 6     = 12
+//         wave 2: (1,0) (1,2)          6 + 6     = 12
+//         wave 3: (0,2) (2,0) (2,2)    4 + 4 + 4 = 12
+//     Three waves by row phase would carry 14 / 21 / 14 taps (the middle wave 1.5x the others, one SIMD idle); padding every phase
+//     to 3 x 3 taps with zero weights would pay 81 / 49 = 1.65x the MFMAs.  The sets cost nothing but four specialisations of
+//     the step body, chosen by a wave-uniform switch.
+//   * per phase a wave deconvolves its HR row at its 32 columns (B operand = LR pixels from the ring, A = weights in
+//     registers, bias-seeded accumulators), applies PReLU, the 1x1 with the accumulator tile re-used in place as its B operand
+//     (channel order permuted consistently in the packed weights), PReLU, zeroes the lanes outside the image (the conv's zero
+//     padding), and convolves the tile as it lies in registers: output rows m+1, m, m-1 (three accumulator sets in flight) and
+//     output pixel q+e = the tile shifted by 1 - e lanes (DPP row shifts, as shift_tiles of the x2 kernel).
+//   * the output row whose last kernel row was just added (m-1) leaves as 4 partial tiles (one per wave) through LDS, summed
+//     in a fixed order + bias + PReLU by all 256 threads.  One barrier per step.  The order of every sum is fixed by (row,
+//     strip) alone, so neither the row segmentation nor the planes of a launch change a bit.
+// Per step (30 output pixels x 32 channels; 49 taps x 4 = 196 MFMA 16x16x32 each for up and down, 9 x 4 for the 1x1):
+//         wave      MFMA up + 1x1 + down      activation VALU (2 act_pack + mask per tile)      DPP (12 per shifted tile pair)
+//         0         52 + 8 + 52 = 112         112                                                48
+//         1         48 + 8 + 48 = 104         112                                                48
+//         2         48 + 8 + 48 = 104         112                                                36
+//         3         48 + 12 + 48 = 108        168                                                48
+// 428 MFMA per step against 448 if every wave ran at wave 0's count (96 %).
+// Weights: 26 (wave 0) / 24 tap fragments of 4 registers for each of the two convolutions = 208 / 192 registers per lane, so the
+// kernel runs one wave per SIMD on the 512-register budget (__launch_bounds__(256, 1)); the 1x1's two fragments and the biases
+// are read from LDS at use.  The tap fragments are pinned in AGPRs (MFMA reads A from either file) and the file is compiled with
+// -amdgpu-mfma-vgpr-form (Makefile) so that MFMA results stay in VGPRs: no v_accvgpr copy in the kernel; and with
+// -amdgpu-sched-strategy=max-ilp, which places the activation VALU in the MFMAs' shadow better than the default scheduler (same
+// instructions, same bits, 10 % less time).
+// As compiled by hipcc for gfx950 (-Rpass-analysis=kernel-resource-usage; max / select build): 176 / 170 VGPRs + 208 AGPRs,
+// 43 / 48 SGPRs, scratch 0 bytes per lane (no spill), occupancy 1 wave per SIMD; 47,872 bytes of dynamic LDS (ring 8,704 +
+// partial tiles 2 x 18,432 + parameters 2,304).
+// Measured on an MI355X (tools/utd_s3_time.py): 8 x 720 x 1280 in 1.75 ms = 924 TFLOP/s at 219,136 FLOP per pixel and plane,
+// against 7.20 ms of the unfused launches.
+#pragma once
+#include "sr_f16_common.h"
+
+namespace {
+
+constexpr int S3_TX = 30;                    // LR output columns per strip (32 deconv positions = 2 MFMA pixel tiles)
+constexpr int S3_LRC = 34;                   // staged LR columns x0-2 .. x0+31
+constexpr int S3_LR_SLOT = S3_LRC * 64;
+constexpr int S3_LR_BYTES = 4 * S3_LR_SLOT;  // rows m-1, m, m+1 + the row being loaded
+constexpr int S3_PART_W = 32 * PART_PX_PITCH;
+constexpr int S3_PART_BUF = 4 * S3_PART_W;
+constexpr int S3_PAR_BYTES = 256 + 2048;     // b_up[32], b_dt[32] fp32 + the two 1x1 fragments
+constexpr int S3_LDS = S3_LR_BYTES + 2 * S3_PART_BUF + S3_PAR_BYTES;
+constexpr int S3_OROW = 2048;                           // POST: a finished output row as fp16 [32 px][64 B], 16-byte pieces swizzled (lr_off)
+constexpr int S3_LDS_POST = 2 * S3_OROW + 2048 + 256;   // two rows + the uptran 1x1's two fragments + its bias and slope
+static_assert(S3_LDS + S3_LDS_POST <= 64 * 1024, "dynamic LDS without the large-LDS attribute");
+
+constexpr int S3_SLOTS = 13;                                      // tap fragments per wave and convolution (waves 1-3 use 12)
+constexpr int S3_BLOB_UP = 0;                                     // [wave 4][slot 13][mt 2][lane 64][8] fp16
+constexpr int S3_BLOB_DN = 4 * S3_SLOTS * 2 * 1024;               // [wave 4][slot 13][mt 2][lane 64][8] fp16
+constexpr int S3_BLOB_DT = 2 * S3_BLOB_DN;                        // [mt 2][lane 64][8] fp16
+constexpr int S3_BLOB_F32 = S3_BLOB_DT + 2 * 1024;                // b_up[32] b_dt[32] b_dn[32] slope_up slope_dt slope_dn
+constexpr int S3_BLOB_BYTES = S3_BLOB_F32 + 512;
+constexpr int S3_BLOB_POST = S3_BLOB_BYTES;                       // POST: [mt 2][lane 64][8] fp16 (natural channel order), then b_post[32], slope_post (64 floats)
+constexpr int S3_BLOB_POST_BYTES = S3_BLOB_POST + 2048 + 256;
+
+// ---- the waves' phase sets and the slot order of their tap fragments (sr.py:pack_utd_s3_blob restates these)
+constexpr int ph_cnt(int wv) { return wv == 3 ? 3 : 2; }
+constexpr int ph_r(int wv, int p) { return wv == 0 ? (p == 0 ? 1 : 0) : wv == 2 ? 1 : (p == 0 ? 0 : 2); }
+constexpr int ph_c(int wv, int p) { return wv == 0 ? (p == 0 ? 1 : 0) : wv == 1 ? 1 : wv == 2 ? (p == 0 ? 0 : 2) : (p == 1 ? 0 : 2); }
+// phase x (a row or a column phase) and offset d in {+1, 0, -1}: kernel index x + 2 - 3 d, live when it lies in 0 .. 6
+constexpr bool tap_ok(int x, int d) { return x + 2 - 3 * d >= 0 && x + 2 - 3 * d <= 6; }
+constexpr int tap_cnt(int x) { return x == 1 ? 3 : 2; }
+constexpr int tap_rank(int x, int d) { return 1 - d - (x == 0 ? 1 : 0); }   // position of d among the live offsets, +1 first
+constexpr int ph_base(int wv, int p) {
+    int s = 0;
+    for (int i = 0; i < p; ++i) s += tap_cnt(ph_r(wv, i)) * tap_cnt(ph_c(wv, i));
+    return s;
+}
+constexpr int tap_slot(int wv, int p, int dy, int dx) {
+    return ph_base(wv, p) + tap_rank(ph_r(wv, p), dy) * tap_cnt(ph_c(wv, p)) + tap_rank(ph_c(wv, p), dx);
+}
+static_assert(ph_base(0, 2) == 13 && ph_base(1, 2) == 12 && ph_base(2, 2) == 12 && ph_base(3, 3) == 12, "tap counts of the phase sets");
+
+template <int V>
+struct IntC { static constexpr int value = V; };
+
+typedef unsigned int u4v __attribute__((ext_vector_type(4)));
+
+// tile pair T (pixel tiles 0, 1: deconv positions n = 16 nt + lane&15) moved down SH lanes: B[nt] lane <- position n + SH
+template <int SH>
+__device__ __forceinline__ void shift_tiles(const h8 (&T)[2], h8 (&B)[2]) {
+    if (SH == 0) {
+        B[0] = T[0];
+        B[1] = T[1];
+        return;
+    }
+    const u4v v0 = __builtin_bit_cast(u4v, T[0]), v1 = __builtin_bit_cast(u4v, T[1]);
+    u4v b0, b1;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        // lanes 16-SH .. 15 of tile 0 take lanes 0 .. SH-1 of tile 1 (row_ror:16-SH), the others their right neighbour (row_shl:SH)
+        const unsigned ror = (unsigned)__builtin_amdgcn_mov_dpp((int)v1[q], 0x120 + (16 - SH), 0xF, 0xF, false);
+        b0[q] = (unsigned)__builtin_amdgcn_update_dpp((int)ror, (int)v0[q], 0x100 + SH, 0xF, 0xF, false);
+        b1[q] = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v1[q], 0x100 + SH, 0xF, 0xF, true);   // positions >= 32: zeros (discarded outputs)
+    }
+    B[0] = __builtin_bit_cast(h8, b0);
+    B[1] = __builtin_bit_cast(h8, b1);
+}
+
+// POST: the NEXT group's uptran slice (1x1 + PReLU on this stage's output) applied to every finished output row inside the launch and
+// written to `out2`, as k_utd_s2<.., POST> does (sr_utd_s2.hip).  The reduce leaves the row's fp16 values in LDS as well (orow, two
+// buffers); after the next barrier each wave multiplies one 16 x 16 quadrant (out-channel tile wv / 2, pixel tile wv % 2): 1 MFMA +
+// 6 VALU per wave and step, outside the per-role switch.  Same operation order as k_chain1x1_s (bias-seeded accumulator, K = 32 in
+// one MFMA, fp16 PReLU): bit-identical to the chain launch it replaces.  POST = false compiles to the kernel without any of it.
+template <bool ALLMAX, bool POST>
+__device__ __forceinline__ void utd_s3_body(const _Float16* __restrict__ in, const unsigned char* __restrict__ blob, _Float16* __restrict__ out,
+                                            int h, int w, int rows_per_seg, _Float16* __restrict__ out2) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned char* const lrr = smem;
+    unsigned char* const part = smem + S3_LR_BYTES;
+    [[maybe_unused]] unsigned char* const orow = smem + S3_LDS;   // (POST only: the launch allocates S3_LDS + S3_LDS_POST)
+    [[maybe_unused]] unsigned char* const postw = orow + 2 * S3_OROW;
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l15 = lane & 15, g = lane >> 4;
+    const int x0 = blockIdx.x * S3_TX;
+    const int n = blockIdx.z;
+    const int r0 = blockIdx.y * rows_per_seg;
+    const int r1 = min(h, r0 + rows_per_seg);
+    if (r0 >= r1) return;   // uniform per workgroup
+
+    // ---- weights -> registers, once per workgroup (slot 12 of waves 1-3 is zero padding that no step reads)
+    h8 Aup[S3_SLOTS][2], Adn[S3_SLOTS][2];
+#pragma unroll
+    for (int t = 0; t < S3_SLOTS; ++t)
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+            Aup[t][mt] = *reinterpret_cast<const h8*>(blob + S3_BLOB_UP + (((wv * S3_SLOTS + t) * 2 + mt) * 64 + lane) * 16);
+            Adn[t][mt] = *reinterpret_cast<const h8*>(blob + S3_BLOB_DN + (((wv * S3_SLOTS + t) * 2 + mt) * 64 + lane) * 16);
+            // the tap fragments live in AGPRs (MFMA reads A from either file), everything the VALU touches in VGPRs: pinning the class
+            // here keeps hipcc from parking fragments in VGPRs first and copying the rest out of AGPRs per use
+            asm volatile("" : "+a"(Aup[t][mt]));
+            asm volatile("" : "+a"(Adn[t][mt]));
+        }
+    const float* fpar = reinterpret_cast<const float*>(blob + S3_BLOB_F32);
+    float* const bias_s = reinterpret_cast<float*>(smem + S3_LR_BYTES + 2 * S3_PART_BUF);
+    if (tid < 64) bias_s[tid] = fpar[tid];   // (visible after the prologue's barrier)
+    unsigned char* const adt_s = smem + S3_LR_BYTES + 2 * S3_PART_BUF + 256;
+    if (tid < 128) *reinterpret_cast<u4v*>(adt_s + tid * 16) = *reinterpret_cast<const u4v*>(blob + S3_BLOB_DT + tid * 16);
+    auto adt = [&](int mt) __attribute__((always_inline)) { return *reinterpret_cast<const h8*>(adt_s + (mt * 64 + lane) * 16); };
+    // this lane's accumulator rows are channels {4g..4g+3} of tile mt
+    auto bup = [&](int mt) __attribute__((always_inline)) { return *reinterpret_cast<const f4*>(bias_s + 16 * mt + 4 * g); };
+    auto bdt = [&](int mt) __attribute__((always_inline)) { return *reinterpret_cast<const f4*>(bias_s + 32 + 16 * mt + 4 * g); };
+    const float a_up = fpar[96], a_dt = fpar[97], a_dn = fpar[98];
+    const h2 a_up2 = {(_Float16)a_up, (_Float16)a_up}, a_dt2 = {(_Float16)a_dt, (_Float16)a_dt};
+    const bool up_max = ALLMAX || a_up <= 1.0f, dt_max = ALLMAX || a_dt <= 1.0f;
+    [[maybe_unused]] h2 a_post2 = {(_Float16)1.0f, (_Float16)1.0f};
+    [[maybe_unused]] bool post_max = true;
+    if constexpr (POST) {
+        const float* ppar = reinterpret_cast<const float*>(blob + S3_BLOB_POST + 2048);
+        if (tid < 128) *reinterpret_cast<u4v*>(postw + tid * 16) = *reinterpret_cast<const u4v*>(blob + S3_BLOB_POST + tid * 16);
+        else if (tid < 160) *reinterpret_cast<float*>(postw + 2048 + (tid - 128) * 4) = ppar[tid - 128];   // (visible after the prologue's barrier)
+        a_post2 = h2{(_Float16)ppar[32], (_Float16)ppar[32]};
+        post_max = ALLMAX || ppar[32] <= 1.0f;
+    }
+
+    // ---- LR loader: 34 columns x 4 chunks of 16 bytes per row; out-of-image pieces read zeros (out-of-range buffer offset)
+    const __amdgpu_buffer_rsrc_t in_rsrc =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(in), 0, (int)((size_t)gridDim.z * h * w * NF * 2), 0x00020000);
+    const bool lr_loader = tid < S3_LRC * 4;
+    const int lr_px = tid >> 2, lr_ch = tid & 3, lr_col = x0 - 2 + lr_px;
+    const bool lr_col_ok = lr_loader && lr_col >= 0 && lr_col < w;
+    const int lr_st = lr_off(lr_px, lr_ch);
+    auto fetch_lr = [&](int row) __attribute__((always_inline)) -> u4v {
+        const unsigned off = (lr_col_ok && row >= 0 && row < h) ? (unsigned)(((((size_t)n * h + row) * w + lr_col) * NF + lr_ch * 8) * 2) : 0xFFFFFFFFu;
+        return __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, off, 0, 0);
+    };
+    auto lr_slot = [&](int row) __attribute__((always_inline)) { return ((row + 4) & 3) * S3_LR_SLOT; };   // (row >= -3)
+
+    // ---- reduce role: output pixel tid>>3 (32 of them, 30 live), channels 4*(tid&7) .. +3
+    const int rj = tid >> 3, rc4 = tid & 7;
+    const f4 bdn = *reinterpret_cast<const f4*>(fpar + 64 + 4 * rc4);
+    const bool red_ok = (rj < S3_TX) && (x0 + rj < w);
+    const __amdgpu_buffer_rsrc_t out_rsrc =
+        __builtin_amdgcn_make_buffer_rsrc(out, 0, (int)((size_t)gridDim.z * h * w * NF * 2), 0x00020000);
+    typedef unsigned int u2v __attribute__((ext_vector_type(2)));
+    typedef float f2v __attribute__((ext_vector_type(2)));
+    const int part_wr = wv * S3_PART_W + l15 * PART_PX_PITCH + 4 * g * 4;   // + 64 mt + 16 nt PART_PX_PITCH
+    const int part_rd = rj * PART_PX_PITCH + rc4 * 16;                       // + k S3_PART_W
+    auto reduce_store = [&](int i, const unsigned char* pbase) __attribute__((always_inline)) {
+        f4 s = *reinterpret_cast<const f4*>(pbase + part_rd);
+#pragma unroll
+        for (int k = 1; k < 4; ++k) s += *reinterpret_cast<const f4*>(pbase + part_rd + k * S3_PART_W);
+        s += bdn;
+        float v[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = s[e] >= 0.0f ? s[e] : s[e] * a_dn;
+        const unsigned lo = __builtin_bit_cast(unsigned, __builtin_convertvector(f2v{v[0], v[1]}, h2));
+        const unsigned hi = __builtin_bit_cast(unsigned, __builtin_convertvector(f2v{v[2], v[3]}, h2));
+        const unsigned off = red_ok ? (unsigned)(((((size_t)n * h + i) * w + x0 + rj) * NF + 4 * rc4) * 2) : 0xFFFFFFFFu;
+        __builtin_amdgcn_raw_buffer_store_b64(u2v{lo, hi}, out_rsrc, off, 0, 0);
+        if constexpr (POST) *reinterpret_cast<u2v*>(orow + (i & 1) * S3_OROW + lr_off(rj, rc4 >> 1) + (rc4 & 1) * 8) = u2v{lo, hi};
+    };
+    // POST: the 1x1 on finished row i (its fp16 values lie in orow[i & 1] since the barrier that followed its reduce): this wave's quadrant;
+    // dead pixels and rows outside [r0, r1) store to an out-of-range buffer offset (dropped)
+    [[maybe_unused]] const __amdgpu_buffer_rsrc_t out2_rsrc =
+        __builtin_amdgcn_make_buffer_rsrc(POST ? out2 : out, 0, (int)((size_t)gridDim.z * h * w * NF * 2), 0x00020000);
+    [[maybe_unused]] const int pmt = wv >> 1, ppx = 16 * (wv & 1) + l15;
+    [[maybe_unused]] const bool post_px_ok = ppx < S3_TX && x0 + ppx < w;
+    [[maybe_unused]] auto post_row = [&](int i) __attribute__((always_inline)) {
+        const h8 b = *reinterpret_cast<const h8*>(orow + (i & 1) * S3_OROW + lr_off(ppx, g));
+        const h8 a = *reinterpret_cast<const h8*>(postw + (pmt * 64 + lane) * 16);
+        const f4 e = mfma16(a, b, *reinterpret_cast<const f4*>(postw + 2048 + (16 * pmt + 4 * g) * 4));
+        const h2 p0 = prelu_h2(__builtin_convertvector(f2v{e[0], e[1]}, h2), a_post2, post_max);
+        const h2 p1 = prelu_h2(__builtin_convertvector(f2v{e[2], e[3]}, h2), a_post2, post_max);
+        const unsigned off = (post_px_ok && i >= r0 && i < r1) ? (unsigned)(((((size_t)n * h + i) * w + x0 + ppx) * NF + 16 * pmt + 4 * g) * 2) : 0xFFFFFFFFu;
+        __builtin_amdgcn_raw_buffer_store_b64(u2v{__builtin_bit_cast(unsigned, p0), __builtin_bit_cast(unsigned, p1)}, out2_rsrc, off, 0, 0);
+    };
+
+    // ---- prologue: LR rows r0-2, r0-1, r0 (the first triple, m = r0-1, reads them)
+    if (lr_loader) {
+        *reinterpret_cast<u4v*>(lrr + lr_slot(r0 - 2) + lr_st) = fetch_lr(r0 - 2);
+        *reinterpret_cast<u4v*>(lrr + lr_slot(r0 - 1) + lr_st) = fetch_lr(r0 - 1);
+        *reinterpret_cast<u4v*>(lrr + lr_slot(r0) + lr_st) = fetch_lr(r0);
+    }
+    __syncthreads();
+
+    // accumulators of the three output rows in flight: [0] row m-1 (gets its last kernel rows in step m), [1] row m, [2] row m+1
+    f4 acc[3][2][2];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt) acc[a][mt][nt] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+
+    // lanes whose deconv position q lies outside the image (HR columns 3q .. 3q+2) hold the conv's zero padding
+    bool col_ok[2];
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) {
+        const int q = x0 - 1 + 16 * nt + l15;
+        col_ok[nt] = q >= 0 && q < w;
+    }
+
+    // ---- one step of wave role WV: its phases' deconv -> PReLU -> 1x1 -> PReLU -> down conv into the three accumulator sets
+    auto compute = [&](auto role, int m) __attribute__((always_inline)) {
+        constexpr int WV = decltype(role)::value;
+#pragma unroll
+        for (int p = 0; p < ph_cnt(WV); ++p) {
+            const int r = ph_r(WV, p), c = ph_c(WV, p);
+            f4 d[2][2];
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < 2; ++nt) d[mt][nt] = bup(mt);
+#pragma unroll
+            for (int di = 1; di >= -1; --di) {
+                if (!tap_ok(r, di)) continue;
+                const unsigned char* rowp = lrr + lr_slot(m + di);
+#pragma unroll
+                for (int dj = 1; dj >= -1; --dj) {
+                    if (!tap_ok(c, dj)) continue;
+                    const int slot = tap_slot(WV, p, di, dj);
+                    h8 B[2];
+#pragma unroll
+                    for (int nt = 0; nt < 2; ++nt) B[nt] = *reinterpret_cast<const h8*>(rowp + lr_off(16 * nt + l15 + 1 + dj, g));
+#pragma unroll
+                    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                        for (int nt = 0; nt < 2; ++nt) d[mt][nt] = mfma16(Aup[slot][mt], B[nt], d[mt][nt]);
+                }
+            }
+            // ---- PReLU -> 1x1 (accumulator tile as B operand) -> PReLU
+            h8 T[2];
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt) {
+                const h8 a1 = act_pack(d[0][nt], d[1][nt], a_up2, up_max);
+                const f4 e0 = mfma16(adt(0), a1, bdt(0));
+                const f4 e1 = mfma16(adt(1), a1, bdt(1));
+                h8 t = act_pack(e0, e1, a_dt2, dt_max);
+                if (!col_ok[nt]) {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) t[e] = (_Float16)0.0f;
+                }
+                T[nt] = t;
+            }
+            // ---- down conv from registers: kernel column c + 2 - 3 e of output pixel q + e (tile shifted 1 - e lanes), kernel row
+            // r + 2 - 3 dd of output row m + dd
+#pragma unroll
+            for (int e = 1; e >= -1; --e) {
+                if (!tap_ok(c, e)) continue;
+                h8 B[2];
+                if (e == 1) shift_tiles<0>(T, B);
+                else if (e == 0) shift_tiles<1>(T, B);
+                else shift_tiles<2>(T, B);
+#pragma unroll
+                for (int dd = 1; dd >= -1; --dd) {
+                    if (!tap_ok(r, dd)) continue;
+                    const int slot = tap_slot(WV, p, dd, e);
+#pragma unroll
+                    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                        for (int nt = 0; nt < 2; ++nt) acc[dd + 1][mt][nt] = mfma16(Adn[slot][mt], B[nt], acc[dd + 1][mt][nt]);
+                }
+            }
+        }
+    };
+
+    for (int m = r0 - 1; m <= r1; ++m) {
+        const u4v nxt = fetch_lr(m + 2);
+        if (m >= 0 && m < h) {   // (uniform) triples outside the image are the conv's zero padding
+            switch (wv) {
+                case 0: compute(IntC<0>{}, m); break;
+                case 1: compute(IntC<1>{}, m); break;
+                case 2: compute(IntC<2>{}, m); break;
+                default: compute(IntC<3>{}, m); break;
+            }
+        }
+        // ---- output row m-1 has all its kernel rows: partial tile of this wave -> LDS; rotate the accumulator sets
+        const bool row_out = (m - 1 >= r0) && (m - 1 < r1);
+        unsigned char* const pbase = part + (m & 1) * S3_PART_BUF;
+        if (row_out) {
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < 2; ++nt)
+                    *reinterpret_cast<f4*>(pbase + part_wr + 64 * mt + 16 * nt * PART_PX_PITCH) = acc[0][mt][nt];
+        }
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt) {
+                acc[0][mt][nt] = acc[1][mt][nt];
+                acc[1][mt][nt] = acc[2][mt][nt];
+                acc[2][mt][nt] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+            }
+        if (lr_loader) *reinterpret_cast<u4v*>(lrr + lr_slot(m + 2) + lr_st) = nxt;   // over row m-2 (last read in step m-1)
+        __syncthreads();
+        if (row_out) reduce_store(m - 1, pbase);
+        // POST: row m-2 was reduced at the end of the previous step and lies in orow since this step's barrier; its 1x1 is issued here, after
+        // the barrier and the reduce, before the next step's first MFMAs, common to all wave roles (rows outside [r0, r1): dropped)
+        if constexpr (POST) post_row(m - 2);
+    }
+    if constexpr (POST) {   // the segment's last row (a one-row segment's only row)
+        __syncthreads();
+        post_row(r1 - 1);
+    }
+}
+
+template <bool ALLMAX>
+__global__ void __launch_bounds__(256, 1)
+k_utd_s3(const _Float16* __restrict__ in, const unsigned char* __restrict__ blob, _Float16* __restrict__ out, int h, int w,
+         int rows_per_seg) {
+    utd_s3_body<ALLMAX, false>(in, blob, out, h, w, rows_per_seg, nullptr);
+}
+
+template <bool ALLMAX>
+__global__ void __launch_bounds__(256, 1)
+k_utd_s3_post(const _Float16* __restrict__ in, const unsigned char* __restrict__ blob, _Float16* __restrict__ out, int h, int w,
+              int rows_per_seg, _Float16* __restrict__ out2) {
+    utd_s3_body<ALLMAX, true>(in, blob, out, h, w, rows_per_seg, out2);
+}
+
+}  // namespace

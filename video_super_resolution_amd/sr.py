@@ -209,6 +209,10 @@ class SRProjectionModule(nn.Module):
                     return _FusedStageS3(*args, slopes_le_one=P["slopes_le_one"], rows_fn=self._rows_per_segment)
                 return _UnfusedStage(*args, self.upscale_factor)
             P["stage"] = {j: stage(j) for j in range(0, G - 2, 3)}
+            if self.upscale_factor == 3 and self.fused_s3:
+                # the same stage with the next group's uptran slice inside the launch, where another stage follows (as x4's P["utd_post"])
+                P["stage_post"] = {j: _FusedStageS3Post(P["stage"][j], (P["ut_w"][j + 3], _NF * (j + 4), P["ut_b"][j + 3], P["ut_a"][j + 3]),
+                                                        rows_fn=self._rows_per_segment) for j in range(0, G - 5, 3)}
             P["out_deconv"] = _PhaseDeconv(self.out[0].weight, self.out[0].bias, P["out_a"], self.upscale_factor)
             if self.upscale_factor == 2 and self.fused_s2:
                 P["tail_s2"] = pack_tail_s2_blob(self.out[0].weight, self.out[0].bias, P["out_a"], self.conv_out[0].weight,
@@ -663,7 +667,9 @@ class SRProjectionModule(nn.Module):
 
     utd_s2_build = int(os.environ.get("VSR_UTD_S2_BUILD", "1"))   # x2 stage: 1 = k_utd_s2 (default), 2 = k_utd_s2w (32x32x16 MFMA, one wave per SIMD: measured 5 % slower, LAB_NOTES R5.8)
     fuse_uptran = os.environ.get("VSR_UTD_POST", "1") != "0"   # the uptran 1x1 between the two stages of a step inside the first stage's launch
-                                                                # (vsr_sr_utd_post_f16; False: its own chain launch -- the cross-check, bit-identical)
+                                                                # (vsr_sr_utd_post_f16, x2: vsr_sr_utd_s2_post_f16, x3: vsr_s3p_sr_utd_post_f16; False: its own chain
+                                                                # launch -- the cross-check, bit-identical).  x3, 8 x 720 x 1280: stage pair 3453 us against
+                                                                # 3510 us with the chain launch (-56 us, spread 9 us; LAB_NOTES "x3 stage with the uptran slice")
 
     def _utd_timer_name(self, N):
         # (timer names carry the plane count when it is not the full 8 -- the roofline leg prices a launch by its planes -- and `_side` for
@@ -804,6 +810,9 @@ class SRProjectionModule(nn.Module):
                     live[j + 3], a_next = o.view(N, hp, _NF), a_next.view(N, hp, _NF)
                 elif self.upscale_factor != 4 and self.fuse_uptran and getattr(P["stage"][j], "has_post", False) and not L._use_x:
                     o, a_next = P["stage"][j](a.view(N, h, w, _NF), self._chain, out=dst, side=getattr(self, "_utd_side", False), post=True)
+                    live[j + 3], a_next = o.view(N, hp, _NF), a_next.view(N, hp, _NF)
+                elif self.upscale_factor == 3 and self.fuse_uptran and j in P.get("stage_post", {}) and not L._use_x:
+                    o, a_next = P["stage_post"][j](a.view(N, h, w, _NF), self._chain, out=dst, side=getattr(self, "_utd_side", False), post=True)
                     live[j + 3], a_next = o.view(N, hp, _NF), a_next.view(N, hp, _NF)
                 else:
                     live[j + 3] = (self._utd(a, P["utd"][j], N, h, w, out=dst) if self.upscale_factor == 4 else
@@ -1360,6 +1369,66 @@ class _FusedStageS3:
                     "sr_utd_s3_f16", lib=lib)
             L.TIMER.stop(tok)
         return out
+
+
+def _append_post_s3(stage_blob, post) -> torch.Tensor:
+    """stage_blob (pack_utd_s3_blob's bytes) + the POST section of include/vsr_hip_s3p.h: post = (w [32,ld], col0, b [32], a) as two A
+    fragments in NATURAL channel order (the B operand is the stage's output row as it lies in memory), then b_post[32], slope_post."""
+    dev = stage_blob.device
+    nbytes = int(L.load_s3p().vsr_s3p_query(L.Q_S3P_BLOB_BYTES))
+    o_p = stage_blob.numel()
+    assert nbytes == o_p + 2048 + 256
+    pw, pcol, pb, pa = post
+    lane = torch.arange(64, device=dev)
+    MT2 = torch.arange(2, device=dev).view(2, 1, 1)
+    co2, ci2 = torch.broadcast_tensors(16 * MT2 + (lane & 15).view(1, 64, 1), pcol + 8 * (lane >> 4).view(1, 64, 1) + torch.arange(8, device=dev).view(1, 1, 8))
+    blob = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+    blob[:o_p] = stage_blob
+    blob[o_p:o_p + 2048] = pw.detach().float()[co2, ci2].to(torch.float16).contiguous().view(torch.uint8).reshape(-1)
+    ppar = torch.zeros(64, dtype=torch.float32, device=dev)
+    ppar[0:32] = pb.detach().float()
+    ppar[32] = float(pa)
+    blob[o_p + 2048:o_p + 2048 + 256] = ppar.view(torch.uint8)
+    return blob
+
+
+def pack_utd_s3_post_blob(up_w, up_b, up_a, tr_w, tr_col0, tr_b, tr_a, dn_w, dn_b, dn_a, post) -> torch.Tensor:
+    """The blob of vsr_s3p_sr_utd_post_f16 (include/vsr_hip_s3p.h): pack_utd_s3_blob's bytes, then post = (w [32,ld], col0, b [32], a), the
+    1x1 + PReLU applied to every finished output row (the next group's uptran slice)."""
+    return _append_post_s3(pack_utd_s3_blob(up_w, up_b, up_a, tr_w, tr_col0, tr_b, tr_a, dn_w, dn_b, dn_a), post)
+
+
+class _FusedStageS3Post:
+    """A _FusedStageS3 and the NEXT group's uptran slice of its output in ONE launch (k_utd_s3_post, libvsr_hip_s3p.so): replaces the
+    stage's launch and the one-stage 1x1 chain launch that followed it, bit for bit."""
+
+    has_post = True
+
+    def __init__(self, stage, post, rows_fn):
+        # stage: the _FusedStageS3 of the same weights (its blob is the first part of this one); post = (w, col0, b, a)
+        self.blob = _append_post_s3(stage.blob, post)
+        self.slopes_le_one = stage.slopes_le_one
+        self.post_slopes_le_one = self.slopes_le_one and float(post[3]) <= 1.0
+        self.rows_fn = rows_fn
+
+    def __call__(self, a, chain, out=None, side=False, post=True):
+        """-> (out, the next group's uptran slice of it), both [N,h,w,32] fp16."""
+        assert post
+        N, h, w, _ = a.shape
+        if out is None:
+            out = torch.empty((N, h, w, _NF), dtype=torch.float16, device=a.device)
+        out2 = torch.empty((N, h, w, _NF), dtype=torch.float16, device=a.device)
+        lib = L.load_s3p()
+        nb = max(1, min(N, ((1 << 32) - 32) // (h * w * _NF * 2)))   # planes per launch: the kernel's 32-bit byte offsets
+        for n0 in range(0, N, nb):
+            n = min(nb, N - n0)
+            tok = L.TIMER.start(("sr_utd_s3_post_f16" if n == 8 else f"sr_utd_s3_post_f16_p{n}") + ("_side" if side else ""))
+            rows = self.rows_fn(n, h, w, cus=256, strip=int(lib.vsr_s3p_query(L.Q_S3P_STRIP_WIDTH)))
+            L.check(lib.vsr_s3p_sr_utd_post_f16(L.dptr(a[n0:n0 + n], torch.float16), L.dptr(self.blob, torch.uint8),
+                                                L.dptr(out[n0:n0 + n], torch.float16), L.dptr(out2[n0:n0 + n], torch.float16), n, h, w, rows,
+                                                int(self.post_slopes_le_one), L.stream()), "sr_utd_s3_post_f16", lib=lib)
+            L.TIMER.stop(tok)
+        return out, out2
 
 
 class _UnfusedStage:

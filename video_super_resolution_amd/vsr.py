@@ -84,6 +84,8 @@ class VSR(nn.Module):
         # in the shadow of FlowNet2 (pass 2's long pole); False = batched with the three LR frames in pass 1 (where the hourglass IS the long pole)
         self.depth_est_late = os.environ.get("VSR_DEPTH_EST_LATE", "0") != "0"   # (measured level: guidance 1 -1.0 ms, guidance 2 +0.9 ms, profiles/r05_early_planes_stages.txt: off)
         self.early_scales = (4,)   # x2 (C3-B): measured level with the plain order (14.15 / 14.26 vs 14.17 / 14.16 frames/s, same box): off there
+                                   # x3 (LR 720 x 1280): 41.26 / 41.19 / 41.05 ms per frame at early_planes 1 / 2 / 3 against 40.77 ms with the plain
+                                   # order (round-to-round spread 0.3 ms, same box, tools/utd_s3_post_time.py): not faster, off there too
         # Opt-in streaming mode (OFF by default; the headline benchmark leaves it off): consecutive windows of a clip share
         # two of their three LR frames (utils/video_utils.py:25), so the depth prediction of a frame and the flow picture of a
         # frame pair computed for window t are what window t+1 computes again.  With temporal_cache = True they are kept
@@ -288,7 +290,7 @@ class VSR(nn.Module):
             # depend on nothing the guidance trunks produce, so they are evaluated NOW, on a side stream, next to those trunks
             # (whose low-resolution layers leave most CUs idle); both SR calls then run head + FeedbackBlock on planes 3-7 only
             shared = {"n": 3} if self.share_planes else None
-            s_sr = None
+            s_sr = ev_packed = None
             if shared is not None and self.overlap_shared and not self._fast() and self.f32_streams:
                 # float32 configuration: the same overlap; the SR module keeps the planes' pre-fusion maps in `shared`
                 main = torch.cuda.current_stream(d.device)
@@ -313,6 +315,11 @@ class VSR(nn.Module):
                 early = self.early_planes if self.model.upscale_factor in self.early_scales else 0
                 with torch.cuda.stream(s_sr):
                     self.model.precompute_shared(x_first, shared, live)
+                    if early and self.early_planes >= 3:
+                        # level 3 evaluates planes on the MAIN stream while this one is still busy (`after_flow`): on the first call of a model
+                        # or geometry the packed weights and the constant maps were produced just now, on this stream, so main waits for them
+                        ev_packed = torch.cuda.Event()
+                        ev_packed.record(torch.cuda.current_stream(d.device))
                     if early:   # plane 7 of pass 1: the previous output at h x w (:37), frame 0 on the first call (:38)
                         self.model.precompute_rows((est if est is not None else x_first[0]).unsqueeze(0), live, n_planes - 1)
                         shared["todo"] = (3, n_planes - 1)
@@ -326,6 +333,8 @@ class VSR(nn.Module):
             if shared is not None and shared.get("todo") is not None and self.early_planes >= 3:
                 def after_flow(p):   # planes 3, 4 of pass 1: the flow pictures at h x w (:35), as k_assemble_planes writes them
                     zd = torch.zeros((1, 1, h, w), dtype=torch.float32, device=d.device)
+                    if ev_packed is not None:
+                        torch.cuda.current_stream(d.device).wait_event(ev_packed)
                     self.model.precompute_rows(self._assemble(d, p, [zd, zd, zd], est)[3:5], shared["live"], 3)
                     shared["todo"] = (5, shared["todo"][1])
             pics, z, _ = self._guidance((f0, f1, f2), depth_cache, extra_depth=() if (self.depth_est_late and self._fast()) else (est_hw3,), cacheable=True,
