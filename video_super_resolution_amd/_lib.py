@@ -1,7 +1,8 @@
 """ctypes binding of libvsr_hip.so (the C ABI declared in include/vsr_hip.h), of libvsr_hip_grad.so (include/vsr_hip_grad.h:
 the backward of the three native flow operators), of libvsr_hip_s3.so (include/vsr_hip_s3.h: the fused x3 stage of the SR net), of
-libvsr_hip_s3t.so (include/vsr_hip_s3t.h: the one-launch x3 tail) and of libvsr_hip_s3p.so (include/vsr_hip_s3p.h: the x3 stage with
-the next group's uptran slice inside the launch).
+libvsr_hip_s3t.so (include/vsr_hip_s3t.h: the one-launch x3 tail), of libvsr_hip_s3p.so (include/vsr_hip_s3p.h: the x3 stage with
+the next group's uptran slice inside the launch) and of libvsr_hip_s3f.so (include/vsr_hip_s3f.h: the x3 stage with the step-opening
+1x1 chain in its LR load path).
 
 There is deliberately no CPU or eager-PyTorch fallback behind these entry points: if the
 shared library is missing, or an operator is handed a non-CUDA tensor, the call raises.
@@ -34,7 +35,10 @@ _xlib = None
 _glib = None
 _s3lib = None
 _s3tlib = None
+S3FLIB_PATH = os.path.join(_PKG, "libvsr_hip_s3f.so")
+S3FHEADER_PATH = os.path.join(_ROOT, "include", "vsr_hip_s3f.h")
 _s3plib = None
+_s3flib = None
 # the cross-check library instead of the shipping one for every call (set by `xcheck()`; the environment switch serves the
 # measurement tools, whose VSR_TUNING codes only that library understands)
 _use_x = os.environ.get("VSR_USE_XCHECK", "0") == "1" or bool(os.environ.get("VSR_TUNING", "").strip())
@@ -46,7 +50,7 @@ class VsrHipError(RuntimeError):
 
 def build(verbose: bool = False) -> str:
     """Compile every HIP source for gfx950 into the in-tree libvsr_hip.so, libvsr_hip_xcheck.so, libvsr_hip_grad.so,
-    libvsr_hip_s3.so, libvsr_hip_s3t.so and libvsr_hip_s3p.so (hipcc cross-compiles without a GPU)."""
+    libvsr_hip_s3.so, libvsr_hip_s3t.so, libvsr_hip_s3p.so and libvsr_hip_s3f.so (hipcc cross-compiles without a GPU)."""
     cmd = ["make", "-j4", "-C", os.path.join(_PKG, "csrc")]
     if not verbose:
         cmd.insert(1, "-s")
@@ -54,10 +58,11 @@ def build(verbose: bool = False) -> str:
     return LIB_PATH
 
 
-def declared_symbols(xcheck: bool = False, grad: bool = False, s3: bool = False, s3t: bool = False, s3p: bool = False) -> list:
-    """Entry points include/vsr_hip.h declares (xcheck: the ones include/vsr_hip_xcheck.h adds; grad / s3 / s3t / s3p: the ones of
-    include/vsr_hip_grad.h / include/vsr_hip_s3.h / include/vsr_hip_s3t.h / include/vsr_hip_s3p.h, libraries of their own)."""
-    with open(S3PHEADER_PATH if s3p else S3THEADER_PATH if s3t else S3HEADER_PATH if s3 else GHEADER_PATH if grad else XHEADER_PATH if xcheck else HEADER_PATH) as f:
+def declared_symbols(xcheck: bool = False, grad: bool = False, s3: bool = False, s3t: bool = False, s3p: bool = False, s3f: bool = False) -> list:
+    """Entry points include/vsr_hip.h declares (xcheck: the ones include/vsr_hip_xcheck.h adds; grad / s3 / s3t / s3p / s3f: the ones of
+    include/vsr_hip_grad.h / include/vsr_hip_s3.h / include/vsr_hip_s3t.h / include/vsr_hip_s3p.h / include/vsr_hip_s3f.h, libraries of
+    their own)."""
+    with open(S3FHEADER_PATH if s3f else S3PHEADER_PATH if s3p else S3THEADER_PATH if s3t else S3HEADER_PATH if s3 else GHEADER_PATH if grad else XHEADER_PATH if xcheck else HEADER_PATH) as f:
         text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
     return sorted(set(re.findall(r"\b(vsr_[a-z0-9_]+)\s*\(", text)))
 
@@ -153,6 +158,21 @@ def load_s3p() -> ctypes.CDLL:
     return _s3plib
 
 
+def load_s3f() -> ctypes.CDLL:
+    """libvsr_hip_s3f.so (include/vsr_hip_s3f.h): the x3 stage with the step-opening 1x1 chain in its LR load path
+    (csrc/sr_utd_s3f.hip).  Its own error buffer: `check(rc, what, lib=load_s3f())`."""
+    global _s3flib
+    if _s3flib is None:
+        lib = _dlopen(S3FLIB_PATH)
+        lib.vsr_s3f_last_error.restype = ctypes.c_char_p
+        lib.vsr_last_error = lib.vsr_s3f_last_error   # the name `check` reads a library's message under
+        lib.vsr_s3f_query.restype = ctypes.c_size_t
+        if lib.vsr_s3f_abi_version() != 1:
+            raise VsrHipError(f"{os.path.basename(S3FLIB_PATH)}: ABI version mismatch")
+        _s3flib = lib
+    return _s3flib
+
+
 def load() -> ctypes.CDLL:
     """The library every product call goes through: libvsr_hip.so, unless a test / tool asked for the cross-check library."""
     global _lib
@@ -186,6 +206,8 @@ Q_S3_BLOB_BYTES, Q_S3_STRIP_WIDTH = range(2)
 Q_S3T_BLOB_BYTES, Q_S3T_BLOB_FOLD_BYTES, Q_S3T_STRIP_WIDTH = range(3)
 # vsr_s3p_query codes (include/vsr_hip_s3p.h)
 Q_S3P_BLOB_BYTES, Q_S3P_STRIP_WIDTH = range(2)
+# vsr_s3f_query codes (include/vsr_hip_s3f.h)
+Q_S3F_BLOB_BYTES, Q_S3F_STRIP_WIDTH = range(2)
 
 
 def check(rc: int, what: str = "", lib=None) -> None:

@@ -4,7 +4,8 @@
 // registers; the unfused build (sr.py:_UnfusedStage: nine phase deconvolutions, in-place 1x1, strided convolution on the generic
 // kernel) moves it through HBM about four times and is kept as the cross-check.  The kernel text lives here once: sr_utd_s3.hip
 // (libvsr_hip_s3.so, include/vsr_hip_s3.h) instantiates the plain build, sr_utd_s3p.hip (libvsr_hip_s3p.so, include/vsr_hip_s3p.h) the
-// POST build, which also applies the next group's uptran 1x1 to its finished rows.
+// POST build, which also applies the next group's uptran 1x1 to its finished rows, sr_utd_s3f.hip (libvsr_hip_s3f.so,
+// include/vsr_hip_s3f.h) the PRE builds, which evaluate the 1x1 chain that opens a FeedbackBlock step in the LR load path.
 //
 // Design = k_utd_s2's (sr_utd_s2.hip) with the x3 geometry:
 //   * a workgroup of 4 waves marches down a strip of 30 LR columns; step m handles the HR row TRIPLE m (rows 3m, 3m+1, 3m+2)
@@ -62,7 +63,9 @@ constexpr int S3_PAR_BYTES = 256 + 2048;     // b_up[32], b_dt[32] fp32 + the tw
 constexpr int S3_LDS = S3_LR_BYTES + 2 * S3_PART_BUF + S3_PAR_BYTES;
 constexpr int S3_OROW = 2048;                           // POST: a finished output row as fp16 [32 px][64 B], 16-byte pieces swizzled (lr_off)
 constexpr int S3_LDS_POST = 2 * S3_OROW + 2048 + 256;   // two rows + the uptran 1x1's two fragments + its bias and slope
-static_assert(S3_LDS + S3_LDS_POST <= 64 * 1024, "dynamic LDS without the large-LDS attribute");
+constexpr int S3_PRE_FRAGS = 10;                         // PRE: co (2 inputs x 2 tiles), ci (feat half, chained half), ut0: A fragments of 1 KiB
+constexpr int S3_LDS_PRE = S3_PRE_FRAGS * 1024 + 512;   // + b_co[32] b_ci[32] b_ut0[32] fp32 (the slopes are read from the blob)
+static_assert(S3_LDS + S3_LDS_POST + S3_LDS_PRE <= 64 * 1024, "dynamic LDS without the large-LDS attribute");
 
 constexpr int S3_SLOTS = 13;                                      // tap fragments per wave and convolution (waves 1-3 use 12)
 constexpr int S3_BLOB_UP = 0;                                     // [wave 4][slot 13][mt 2][lane 64][8] fp16
@@ -72,6 +75,12 @@ constexpr int S3_BLOB_F32 = S3_BLOB_DT + 2 * 1024;                // b_up[32] b_
 constexpr int S3_BLOB_BYTES = S3_BLOB_F32 + 512;
 constexpr int S3_BLOB_POST = S3_BLOB_BYTES;                       // POST: [mt 2][lane 64][8] fp16 (natural channel order), then b_post[32], slope_post (64 floats)
 constexpr int S3_BLOB_POST_BYTES = S3_BLOB_POST + 2048 + 256;
+// PRE: 12 fragments [lane 64][8] fp16 -- co input a (mt 0, 1), co input b, ci feat half, ci chained half (accumulator channel order),
+// ut0 (accumulator order), ci second half in NATURAL order (PRE2: both halves multiply feat as it lies in memory) -- then b_co[32]
+// b_ci[32] b_ut0[32] slope_co slope_ci slope_ut0 (128 floats)
+constexpr int S3_BLOB_PRE = S3_BLOB_POST_BYTES;
+constexpr int S3_BLOB_PRE_F32 = S3_BLOB_PRE + 12 * 1024;
+constexpr int S3_BLOB_PRE_BYTES = S3_BLOB_PRE_F32 + 512;
 
 // ---- the waves' phase sets and the slot order of their tap fragments (sr.py:pack_utd_s3_blob restates these)
 constexpr int ph_cnt(int wv) { return wv == 3 ? 3 : 2; }
@@ -122,14 +131,40 @@ __device__ __forceinline__ void shift_tiles(const h8 (&T)[2], h8 (&B)[2]) {
 // buffers); after the next barrier each wave multiplies one 16 x 16 quadrant (out-channel tile wv / 2, pixel tile wv % 2): 1 MFMA +
 // 6 VALU per wave and step, outside the per-role switch.  Same operation order as k_chain1x1_s (bias-seeded accumulator, K = 32 in
 // one MFMA, fp16 PReLU): bit-identical to the chain launch it replaces.  POST = false compiles to the kernel without any of it.
-template <bool ALLMAX, bool POST>
+//
+// PRE: the 1x1 chain that opens a FeedbackBlock step, applied in the LR load path instead of a launch of its own (k_chain1x1_s).  `in`
+// is then `feat`, and the value written into the ring for LR pixel p is
+//     PRE3 (pa != nullptr; steps >= 1):  ut0(ci(feat[p], co(pa[p], pb[p], cmap[p])))        cmap: [h w, 32] fp32, shared by the planes
+//     PRE2 (pa == nullptr; step 0):      ut0(ci(feat[p], feat[p]))
+// in k_chain1x1_s's own order of operations: per 1x1 a bias-seeded fp32 accumulator (+ cmap for co), the memory-input MFMAs t = 0, 1
+// (K = 32 in one MFMA per out-channel tile), the MFMA on the previous 1x1's activated tile used in place as B operand, act_pack (round
+// to fp16, PReLU in fp16).  Bit-identical to the chain launch.  The 34 staged columns are three 16-pixel MFMA tiles (the third with two
+// live columns); wave 1 + T carries tile T: lane (l15, g) fetches the 16-byte chunk g of pixel 16 T + l15 of each input at the start
+// of a step (as `nxt` of the plain build), runs the chain after its compute and writes its two 8-byte pieces (channels 4g .. 4g+3 and
+// 16+4g .. 16+4g+3) into the ring before the step's barrier.  Pixels outside the image put ZEROS into the ring (the deconvolution's
+// zero padding), not the chain's value of zero operands.  Per step and wave: PRE3 4 + 4 + 2 = 10 MFMAs, PRE2 2 + 2 + 2 = 6:
+//         wave      plain     + PRE3     + PRE2          (+ 1 each with POST)
+//         0         112       112        112
+//         1         104       114        110
+//         2         104       114        110
+//         3         108       118        114
+// PRE = false compiles to the kernels without any of it.
+struct S3PreOps {
+    u4v f, a, b;
+    f4 cm[2];
+};
+
+template <bool ALLMAX, bool POST, bool PRE = false>
 __device__ __forceinline__ void utd_s3_body(const _Float16* __restrict__ in, const unsigned char* __restrict__ blob, _Float16* __restrict__ out,
-                                            int h, int w, int rows_per_seg, _Float16* __restrict__ out2) {
+                                            int h, int w, int rows_per_seg, _Float16* __restrict__ out2,
+                                            const _Float16* __restrict__ pa = nullptr, const _Float16* __restrict__ pb = nullptr,
+                                            const float* __restrict__ cmap = nullptr) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* const lrr = smem;
     unsigned char* const part = smem + S3_LR_BYTES;
     [[maybe_unused]] unsigned char* const orow = smem + S3_LDS;   // (POST only: the launch allocates S3_LDS + S3_LDS_POST)
     [[maybe_unused]] unsigned char* const postw = orow + 2 * S3_OROW;
+    [[maybe_unused]] unsigned char* const prew = smem + S3_LDS + (POST ? S3_LDS_POST : 0);   // (PRE only: + S3_LDS_PRE)
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -189,6 +224,92 @@ __device__ __forceinline__ void utd_s3_body(const _Float16* __restrict__ in, con
     };
     auto lr_slot = [&](int row) __attribute__((always_inline)) { return ((row + 4) & 3) * S3_LR_SLOT; };   // (row >= -3)
 
+    // ---- PRE: the folded chain.  Waves 1-3, pixel tile wv - 1 of the staged columns; lane = MFMA operand lane (pixel l15, chunk g)
+    [[maybe_unused]] const bool pre3 = PRE && pa != nullptr;
+    [[maybe_unused]] const int pre_px = PRE ? 16 * (wv - 1) + l15 : 0, pre_col = PRE ? x0 - 2 + pre_px : 0;
+    [[maybe_unused]] const bool pre_lane = PRE && wv >= 1 && pre_px < S3_LRC;
+    [[maybe_unused]] const bool pre_col_ok = pre_lane && pre_col >= 0 && pre_col < w;
+    [[maybe_unused]] h2 a_co2 = {(_Float16)1.0f, (_Float16)1.0f}, a_ci2 = a_co2, a_ut2 = a_co2;
+    [[maybe_unused]] bool co_max = true, ci_max = true, ut_max = true;
+    [[maybe_unused]] __amdgpu_buffer_rsrc_t a_rsrc = in_rsrc, b_rsrc = in_rsrc, cm_rsrc = in_rsrc;
+    if constexpr (PRE) {
+        const unsigned char* const src = blob + S3_BLOB_PRE;
+        for (int i = tid; i < S3_PRE_FRAGS * 64; i += 256) {
+            int f = i >> 6;
+            if (!pre3 && (f == 6 || f == 7)) f += 4;   // PRE2: the second half of ci in natural channel order (its B operand is feat)
+            *reinterpret_cast<u4v*>(prew + i * 16) = *reinterpret_cast<const u4v*>(src + (f * 64 + (i & 63)) * 16);
+        }
+        const float* qpar = reinterpret_cast<const float*>(blob + S3_BLOB_PRE_F32);
+        if (tid < 96) *reinterpret_cast<float*>(prew + S3_PRE_FRAGS * 1024 + tid * 4) = qpar[tid];
+        a_co2 = h2{(_Float16)qpar[96], (_Float16)qpar[96]};
+        a_ci2 = h2{(_Float16)qpar[97], (_Float16)qpar[97]};
+        a_ut2 = h2{(_Float16)qpar[98], (_Float16)qpar[98]};
+        co_max = ALLMAX || qpar[96] <= 1.0f, ci_max = ALLMAX || qpar[97] <= 1.0f, ut_max = ALLMAX || qpar[98] <= 1.0f;
+        if (pre3) {
+            a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(pa), 0, (int)((size_t)gridDim.z * h * w * NF * 2), 0x00020000);
+            b_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(pb), 0, (int)((size_t)gridDim.z * h * w * NF * 2), 0x00020000);
+            cm_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(cmap), 0, (int)((size_t)h * w * NF * 4), 0x00020000);
+        }
+    }
+    // out-of-image pixels (and the lanes of the third tile beyond column 33) read zeros: out-of-range buffer offsets
+    [[maybe_unused]] auto fetch_pre = [&](int row) __attribute__((always_inline)) -> S3PreOps {
+        const bool ok = pre_col_ok && row >= 0 && row < h;
+        const unsigned off = ok ? (unsigned)(((((size_t)n * h + row) * w + pre_col) * NF + g * 8) * 2) : 0xFFFFFFFFu;
+        S3PreOps o;
+        o.f = __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, off, 0, 0);
+        if (pre3) {
+            o.a = __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, off, 0, 0);
+            o.b = __builtin_amdgcn_raw_buffer_load_b128(b_rsrc, off, 0, 0);
+            // this lane's accumulator rows: channels 4g .. 4g+3 of tile mt
+            const unsigned c0 = ok ? (unsigned)((((size_t)row * w + pre_col) * NF + 4 * g) * 4) : 0xFFFFFFFFu;
+            const unsigned c1 = ok ? c0 + 64u : 0xFFFFFFFFu;
+            o.cm[0] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(cm_rsrc, c0, 0, 0));
+            o.cm[1] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(cm_rsrc, c1, 0, 0));
+        } else {
+            o.a = o.b = u4v{0u, 0u, 0u, 0u};
+            o.cm[0] = o.cm[1] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+        }
+        return o;
+    };
+    [[maybe_unused]] auto pre_frag = [&](int f) __attribute__((always_inline)) { return *reinterpret_cast<const h8*>(prew + (f * 64 + lane) * 16); };
+    [[maybe_unused]] auto pre_bias = [&](int s, int mt) __attribute__((always_inline)) {
+        return *reinterpret_cast<const f4*>(prew + S3_PRE_FRAGS * 1024 + (32 * s + 16 * mt + 4 * g) * 4);
+    };
+    // the chain on the fetched operands of LR row `row` -> ring (two 8-byte pieces in natural channel order)
+    [[maybe_unused]] auto pre_row = [&](const S3PreOps& o, int row) __attribute__((always_inline)) {
+        const h8 f = __builtin_bit_cast(h8, o.f);
+        h8 prev = f;   // (PRE2: ci's second input is feat itself)
+        f4 c0, c1;
+        if (pre3) {
+            c0 = pre_bias(0, 0);
+            c1 = pre_bias(0, 1);
+            c0 += o.cm[0];
+            c1 += o.cm[1];
+            const h8 ia = __builtin_bit_cast(h8, o.a), ib = __builtin_bit_cast(h8, o.b);
+            c0 = mfma16(pre_frag(0), ia, c0);
+            c1 = mfma16(pre_frag(1), ia, c1);
+            c0 = mfma16(pre_frag(2), ib, c0);
+            c1 = mfma16(pre_frag(3), ib, c1);
+            prev = act_pack(c0, c1, a_co2, co_max);
+        }
+        c0 = mfma16(pre_frag(4), f, pre_bias(1, 0));
+        c1 = mfma16(pre_frag(5), f, pre_bias(1, 1));
+        c0 = mfma16(pre_frag(6), prev, c0);
+        c1 = mfma16(pre_frag(7), prev, c1);
+        prev = act_pack(c0, c1, a_ci2, ci_max);
+        c0 = mfma16(pre_frag(8), prev, pre_bias(2, 0));
+        c1 = mfma16(pre_frag(9), prev, pre_bias(2, 1));
+        prev = act_pack(c0, c1, a_ut2, ut_max);
+        u4v v = __builtin_bit_cast(u4v, prev);
+        if (!(pre_col_ok && row >= 0 && row < h)) v = u4v{0u, 0u, 0u, 0u};   // the deconvolution's zero padding
+        if (pre_lane) {
+            typedef unsigned int u2p __attribute__((ext_vector_type(2)));
+            unsigned char* const rp = lrr + lr_slot(row) + (g & 1) * 8;
+            *reinterpret_cast<u2p*>(rp + lr_off(pre_px, g >> 1)) = u2p{v[0], v[1]};
+            *reinterpret_cast<u2p*>(rp + lr_off(pre_px, 2 + (g >> 1))) = u2p{v[2], v[3]};
+        }
+    };
+
     // ---- reduce role: output pixel tid>>3 (32 of them, 30 live), channels 4*(tid&7) .. +3
     const int rj = tid >> 3, rc4 = tid & 7;
     const f4 bdn = *reinterpret_cast<const f4*>(fpar + 64 + 4 * rc4);
@@ -230,7 +351,15 @@ __device__ __forceinline__ void utd_s3_body(const _Float16* __restrict__ in, con
     };
 
     // ---- prologue: LR rows r0-2, r0-1, r0 (the first triple, m = r0-1, reads them)
-    if (lr_loader) {
+    if constexpr (PRE) {
+        __syncthreads();   // the chain's fragments and biases are in LDS
+        if (wv >= 1) {
+            const S3PreOps o0 = fetch_pre(r0 - 2), o1 = fetch_pre(r0 - 1), o2 = fetch_pre(r0);
+            pre_row(o0, r0 - 2);
+            pre_row(o1, r0 - 1);
+            pre_row(o2, r0);
+        }
+    } else if (lr_loader) {
         *reinterpret_cast<u4v*>(lrr + lr_slot(r0 - 2) + lr_st) = fetch_lr(r0 - 2);
         *reinterpret_cast<u4v*>(lrr + lr_slot(r0 - 1) + lr_st) = fetch_lr(r0 - 1);
         *reinterpret_cast<u4v*>(lrr + lr_slot(r0) + lr_st) = fetch_lr(r0);
@@ -319,7 +448,13 @@ __device__ __forceinline__ void utd_s3_body(const _Float16* __restrict__ in, con
     };
 
     for (int m = r0 - 1; m <= r1; ++m) {
-        const u4v nxt = fetch_lr(m + 2);
+        [[maybe_unused]] u4v nxt;
+        [[maybe_unused]] S3PreOps pnxt;
+        if constexpr (PRE) {
+            if (wv >= 1) pnxt = fetch_pre(m + 2);
+        } else {
+            nxt = fetch_lr(m + 2);
+        }
         if (m >= 0 && m < h) {   // (uniform) triples outside the image are the conv's zero padding
             switch (wv) {
                 case 0: compute(IntC<0>{}, m); break;
@@ -346,7 +481,11 @@ __device__ __forceinline__ void utd_s3_body(const _Float16* __restrict__ in, con
                 acc[1][mt][nt] = acc[2][mt][nt];
                 acc[2][mt][nt] = f4{0.0f, 0.0f, 0.0f, 0.0f};
             }
-        if (lr_loader) *reinterpret_cast<u4v*>(lrr + lr_slot(m + 2) + lr_st) = nxt;   // over row m-2 (last read in step m-1)
+        if constexpr (PRE) {
+            if (wv >= 1) pre_row(pnxt, m + 2);   // over row m-2 (last read in step m-1)
+        } else if (lr_loader) {
+            *reinterpret_cast<u4v*>(lrr + lr_slot(m + 2) + lr_st) = nxt;   // over row m-2 (last read in step m-1)
+        }
         __syncthreads();
         if (row_out) reduce_store(m - 1, pbase);
         // POST: row m-2 was reduced at the end of the previous step and lies in orow since this step's barrier; its 1x1 is issued here, after
@@ -371,6 +510,14 @@ __global__ void __launch_bounds__(256, 1)
 k_utd_s3_post(const _Float16* __restrict__ in, const unsigned char* __restrict__ blob, _Float16* __restrict__ out, int h, int w,
               int rows_per_seg, _Float16* __restrict__ out2) {
     utd_s3_body<ALLMAX, true>(in, blob, out, h, w, rows_per_seg, out2);
+}
+
+// PRE builds (libvsr_hip_s3f.so): `feat` in place of the stage's input, the step-opening 1x1 chain in the load path (pa == nullptr: PRE2)
+template <bool ALLMAX, bool POST>
+__global__ void __launch_bounds__(256, 1)
+k_utd_s3_pre(const _Float16* __restrict__ feat, const _Float16* __restrict__ pa, const _Float16* __restrict__ pb, const float* __restrict__ cmap,
+             const unsigned char* __restrict__ blob, _Float16* __restrict__ out, int h, int w, int rows_per_seg, _Float16* __restrict__ out2) {
+    utd_s3_body<ALLMAX, POST, true>(feat, blob, out, h, w, rows_per_seg, out2, pa, pb, cmap);
 }
 
 }  // namespace

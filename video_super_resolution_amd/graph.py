@@ -57,7 +57,7 @@ class GraphedVSR:
         weights = (m.model._weights_key(), m._flow_exec.key(), m._depth_exec.key(), m._vos_exec.key())
         return (tuple(data.shape), data.dtype, data.device.index, None if est is None else (tuple(est.shape), est.dtype),
                 m.precision, m.upscale_factor, m.share_planes, m.share_tail, m.overlap_shared, m.early_planes, m.depth_est_late, tuple(m.early_scales),
-                m.model.fuse_uptran, m.model.fold_tail, m.model.utd_build, m.model.tail_build, weights)
+                m.model.fuse_uptran, m.model.fold_chain, tuple(m.model.fold_chain_modes), m.model.fold_tail, m.model.utd_build, m.model.tail_build, weights)
 
     def _capture(self, data, est):
         m = self.model

@@ -213,6 +213,11 @@ class SRProjectionModule(nn.Module):
                 # the same stage with the next group's uptran slice inside the launch, where another stage follows (as x4's P["utd_post"])
                 P["stage_post"] = {j: _FusedStageS3Post(P["stage"][j], (P["ut_w"][j + 3], _NF * (j + 4), P["ut_b"][j + 3], P["ut_a"][j + 3]),
                                                         rows_fn=self._rows_per_segment) for j in range(0, G - 5, 3)}
+                if G == 6:
+                    # ... and with the step-opening 1x1 chain in its LR load path (`fold_chain`; compress_out reads exactly two live maps)
+                    P["stage_pre"] = {0: _FusedStageS3Pre(P["stage_post"][0], (P["co_w"], (_NF * 2, _NF * 5), P["co_b"], P["co_a"]),
+                                                          (P["ci_w"], P["ci_b"], P["ci_a"]), (P["ut_w"][0], _NF, P["ut_b"][0], P["ut_a"][0]),
+                                                          rows_fn=self._rows_per_segment)}
             P["out_deconv"] = _PhaseDeconv(self.out[0].weight, self.out[0].bias, P["out_a"], self.upscale_factor)
             if self.upscale_factor == 2 and self.fused_s2:
                 P["tail_s2"] = pack_tail_s2_blob(self.out[0].weight, self.out[0].bias, P["out_a"], self.conv_out[0].weight,
@@ -671,6 +676,14 @@ class SRProjectionModule(nn.Module):
                                                                 # launch -- the cross-check, bit-identical).  x3, 8 x 720 x 1280: stage pair 3453 us against
                                                                 # 3510 us with the chain launch (-56 us, spread 9 us; LAB_NOTES "x3 stage with the uptran slice")
 
+    # x3: the 1x1 chain that opens a step (compress_out -> compress_in -> uptran slice of group 0) inside the LR load path of the step's first
+    # stage (vsr_s3f_sr_utd_pre_f16, libvsr_hip_s3f.so; False: its own chain launch -- bit-identical).  Opt-in: the rule for turning a mode
+    # on (tools/utd_s3_pre_time.py: faster than chain + POST + plain by more than the larger round-to-round spread at 8 x 720 x 1280) has
+    # not been met by a measurement yet (LAB_NOTES "x3 stage with the step-opening chain"); `fold_chain_modes`: the modes the switch routes
+    # (2 = step 0: compress_in -> uptran slice; 3 = later steps: compress_out -> compress_in -> uptran slice)
+    fold_chain = os.environ.get("VSR_FOLD_CHAIN", "0") != "0"
+    fold_chain_modes = (2, 3)
+
     def _utd_timer_name(self, N):
         # (timer names carry the plane count when it is not the full 8 -- the roofline leg prices a launch by its planes -- and `_side` for
         # the launches of precompute_shared / precompute_rows, which share the chip with the guidance trunks)
@@ -776,8 +789,14 @@ class SRProjectionModule(nn.Module):
         live = {}
         hid = None
         for step in range(self.num_steps if N else 0):
+            # x3: that chain inside the first stage's LR load path (`fold_chain`); the taps path needs its intermediate tensors
+            fold = (self.fold_chain and self.upscale_factor == 3 and G == 6 and taps is None and not L._use_x and 0 in P.get("stage_pre", {})
+                    and (step == 0 or sorted(live) == [3, 6]) and (3 if step > 0 else 2) in self.fold_chain_modes)
             # one launch: (compress_out of the previous step ->) compress_in -> uptran slice of group 1
-            if step > 0 and len(co(live)["ins"]) > 2:   # more than 6 groups: compress_out on its own (three inputs)
+            if fold:
+                prev_a, prev_b = (live[3], live[6]) if step > 0 else (None, None)
+                outs = [None, None]
+            elif step > 0 and len(co(live)["ins"]) > 2:   # more than 6 groups: compress_out on its own (three inputs)
                 hid = self._c1h(co(live)["ins"], P["co_b"], P["co_a"], N, hp, cmap=cmap_nhwc)
                 outs = [hid] + self._chain([ci(hid), ut(0)], N, hp, keep=[want_lr0, True])
             elif step > 0:
@@ -799,7 +818,15 @@ class SRProjectionModule(nn.Module):
                 dst = shared["live"][j + 3][n0:n0 + N].view(N, h, w, _NF) if (n0 and step == self.num_steps - 1) else None
                 if precompute is not None and step == self.num_steps - 1:
                     dst = precompute[j + 3][:N].view(N, h, w, _NF)
-                if self.upscale_factor == 4 and self.utd_build == 4 and not L._use_x:
+                if fold and j == 0:
+                    v4 = lambda t: None if t is None else t.view(N, h, w, _NF)
+                    r = P["stage_pre"][0](feat.view(N, h, w, _NF), v4(prev_a), v4(prev_b), cmap_nhwc if step > 0 else None, out=dst,
+                                          side=getattr(self, "_utd_side", False), post=self.fuse_uptran)
+                    if self.fuse_uptran:
+                        live[3], a_next = r[0].view(N, hp, _NF), r[1].view(N, hp, _NF)
+                    else:
+                        live[3] = r.view(N, hp, _NF)
+                elif self.upscale_factor == 4 and self.utd_build == 4 and not L._use_x:
                     if self.fuse_uptran and j + 6 <= G:
                         o, a_next = self._utd4(a, P["utd4"][j], N, h, w, out=dst, post=True)
                         live[j + 3], a_next = o.view(N, hp, _NF), a_next.view(N, hp, _NF)
@@ -1429,6 +1456,75 @@ class _FusedStageS3Post:
                                                 int(self.post_slopes_le_one), L.stream()), "sr_utd_s3_post_f16", lib=lib)
             L.TIMER.stop(tok)
         return out, out2
+
+
+PRE_SECTION_BYTES = 12 * 1024 + 512
+
+
+def pack_utd_s3_pre_blob(post_blob, co, ci, ut0) -> torch.Tensor:
+    """The blob of vsr_s3f_sr_utd_pre_f16 (include/vsr_hip_s3f.h): post_blob (pack_utd_s3_post_blob's bytes, byte for byte), then the PRE
+    section -- the step-opening 1x1 chain as twelve A fragments [lane 64][8] fp16 (fragment 2 i + mt: rows 16 mt + lane % 16 of matrix i)
+    and a parameter block.  co = (w [32,ld], (col_a, col_b), b [32], a): compress_out over the two live maps; ci = (w [32,64], b, a):
+    compress_in (columns 0:32 multiply `feat`, 32:64 the previous 1x1's tile); ut0 = (w [32,ld], col0, b, a): the first uptran slice.
+    Memory inputs in natural channel order, chained inputs in the accumulator's (_chunk_channel_order); the second half of ci a second time
+    in natural order (step 0, where it multiplies `feat`).  fp32 -> fp16 by round to nearest even, as k_chain1x1_s rounds at load."""
+    dev = post_blob.device
+    nbytes = int(L.load_s3f().vsr_s3f_query(L.Q_S3F_BLOB_BYTES))
+    o_p = post_blob.numel()
+    assert nbytes == o_p + PRE_SECTION_BYTES
+    co_w, (col_a, col_b), co_b, co_a = co
+    ci_w, ci_b, ci_a = ci
+    ut_w, ut_col, ut_b, ut_a = ut0
+    lane = torch.arange(64, device=dev)
+    row = (16 * torch.arange(2, device=dev).view(2, 1, 1) + (lane & 15).view(1, 64, 1)).expand(2, 64, 8)
+    nat = (8 * (lane >> 4).view(1, 64, 1) + torch.arange(8, device=dev).view(1, 1, 8)).expand(2, 64, 8)
+    acc = _chunk_channel_order(dev)[lane >> 4].view(1, 64, 8).expand(2, 64, 8)
+    frag = lambda wm, k: wm.detach().float().to(dev)[row, k].to(torch.float16)
+    frags = torch.stack((frag(co_w, col_a + nat), frag(co_w, col_b + nat), frag(ci_w, nat), frag(ci_w, _NF + acc), frag(ut_w, ut_col + acc),
+                         frag(ci_w, _NF + nat)))   # [6][mt 2][lane 64][8]
+    blob = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+    blob[:o_p] = post_blob
+    blob[o_p:o_p + 12 * 1024] = frags.contiguous().view(torch.uint8).reshape(-1)
+    par = torch.zeros(128, dtype=torch.float32, device=dev)
+    par[0:32], par[32:64], par[64:96] = co_b.detach().float(), ci_b.detach().float(), ut_b.detach().float()
+    par[96], par[97], par[98] = float(co_a), float(ci_a), float(ut_a)
+    blob[o_p + 12 * 1024:] = par.view(torch.uint8)
+    return blob
+
+
+class _FusedStageS3Pre:
+    """The step-opening 1x1 chain (compress_out -> compress_in -> first uptran slice; step 0: compress_in -> uptran slice), the x3 stage
+    of group 0 and -- post=True -- the next group's uptran slice in ONE launch (k_utd_s3_pre, libvsr_hip_s3f.so): replaces the chain
+    launch and the stage launch that followed it, bit for bit."""
+
+    def __init__(self, stage_post, co, ci, ut0, rows_fn):
+        # stage_post: the _FusedStageS3Post of the same weights (its blob is the first part of this one)
+        self.blob = pack_utd_s3_pre_blob(stage_post.blob, co, ci, ut0)
+        pre_le_one = all(float(a) <= 1.0 for a in (co[3], ci[2], ut0[3]))
+        self.slopes_le_one = stage_post.slopes_le_one and pre_le_one             # without POST: its slope is not read
+        self.post_slopes_le_one = stage_post.post_slopes_le_one and pre_le_one
+        self.rows_fn = rows_fn
+
+    def __call__(self, feat, a, b, cmap, out=None, side=False, post=True):
+        """feat [N,h,w,32] fp16; a, b: the two live maps of the previous step and cmap [h w, 32] fp32, or all None (step 0)
+        -> (out, the next group's uptran slice of it) with post, else out."""
+        N, h, w, _ = feat.shape
+        if out is None:
+            out = torch.empty((N, h, w, _NF), dtype=torch.float16, device=feat.device)
+        out2 = torch.empty((N, h, w, _NF), dtype=torch.float16, device=feat.device) if post else None
+        lib = L.load_s3f()
+        nb = max(1, min(N, ((1 << 32) - 32) // (h * w * _NF * 2)))   # planes per launch: the kernel's 32-bit byte offsets
+        sl = lambda t, n0, n: None if t is None else t[n0:n0 + n]
+        for n0 in range(0, N, nb):
+            n = min(nb, N - n0)
+            tok = L.TIMER.start(("sr_utd_s3_pre_f16" if n == 8 else f"sr_utd_s3_pre_f16_p{n}") + ("_side" if side else ""))
+            rows = self.rows_fn(n, h, w, cus=256, strip=int(lib.vsr_s3f_query(L.Q_S3F_STRIP_WIDTH)))
+            L.check(lib.vsr_s3f_sr_utd_pre_f16(L.dptr(feat[n0:n0 + n], torch.float16), L.optr(sl(a, n0, n), torch.float16), L.optr(sl(b, n0, n), torch.float16),
+                                               L.optr(cmap), L.dptr(self.blob, torch.uint8), L.dptr(out[n0:n0 + n], torch.float16),
+                                               L.optr(sl(out2, n0, n), torch.float16), n, h, w, rows,
+                                               int(self.post_slopes_le_one if post else self.slopes_le_one), L.stream()), "sr_utd_s3_pre_f16", lib=lib)
+            L.TIMER.stop(tok)
+        return (out, out2) if post else out
 
 
 class _UnfusedStage:
