@@ -67,6 +67,23 @@ def test_s3_entry_validates_before_any_launch():
     assert fn(fake, fake, fake2, 1, 70000, 8, 1, 1, null) == -1 and b"row segments" in msg()
 
 
+def test_s3_entry_refuses_overlapping_byte_ranges_for_every_pair():
+    """in, blob, out as RANGES (1 x 4 x 4 x 64 B = 1024 B per tensor): the same address, one starting inside another, one ending inside
+    another -- for every pair; far apart they pass every check up to the launch, which a host without a GPU refuses with another code."""
+    S = _lib.load_s3()
+    fn = S.vsr_s3_sr_utd_f16
+    null = ctypes.c_void_p(0)
+    bufs = [ctypes.c_void_p(0x100000000000 * (i + 1)) for i in range(3)]   # never dereferenced on the host
+    inside = lambda p: ctypes.c_void_p(p.value + 1008)
+    before = lambda p: ctypes.c_void_p(p.value - 16)
+    for i in range(3):
+        for j in range(i + 1, 3):
+            for shift in (lambda p: p, inside, before):
+                args = list(bufs)
+                args[j] = shift(bufs[i])
+                assert fn(*args, 1, 4, 4, 4, 1, null) == -1 and b"overlap" in S.vsr_s3_last_error(), (i, j)
+
+
 def test_check_reports_from_the_s3_librarys_own_buffer():
     S = _lib.load_s3()
     fake = ctypes.c_void_p(0x1000)

@@ -94,6 +94,14 @@ def test_s3p_entry_validates_before_any_launch():
         assert fn(_IN, _BLOB, _OUT, shift(_IN), 1, 4, 4, 4, 1, _NULL) == -1 and b"overlap" in msg()
         assert fn(_IN, _BLOB, _OUT, shift(_OUT), 1, 4, 4, 4, 1, _NULL) == -1 and b"overlap" in msg()
     assert fn(_IN, _BLOB, _BLOB, _POST, 1, 4, 4, 4, 1, _NULL) == -1 and b"overlap" in msg()       # an output over the weights
+    # ... and every pair of the four, the blob among them, with the same three shifts
+    bufs = (_IN, _BLOB, _OUT, _POST)
+    for i in range(4):
+        for j in range(i + 1, 4):
+            for shift in (lambda p: p, inside, before):
+                args = list(bufs)
+                args[j] = shift(bufs[i])
+                assert fn(*args, 1, 4, 4, 4, 1, _NULL) == -1 and b"overlap" in msg(), (i, j)
     assert fn(_IN, _BLOB, _OUT, _POST, 8, 3000, 3000, 16, 1, _NULL) == -3 and b"4 GiB" in msg() and b"split the planes" in msg()
     assert fn(_IN, _BLOB, _OUT, _POST, 1, 70000, 8, 1, 1, _NULL) == -1 and b"row segments" in msg()
 

@@ -22,23 +22,23 @@ LIB_PATH = os.path.join(_PKG, "libvsr_hip.so")
 XLIB_PATH = os.path.join(_PKG, "libvsr_hip_xcheck.so")
 HEADER_PATH = os.path.join(_ROOT, "include", "vsr_hip.h")
 XHEADER_PATH = os.path.join(_ROOT, "include", "vsr_hip_xcheck.h")
-GLIB_PATH = os.path.join(_PKG, "libvsr_hip_grad.so")
-GHEADER_PATH = os.path.join(_ROOT, "include", "vsr_hip_grad.h")
-S3LIB_PATH = os.path.join(_PKG, "libvsr_hip_s3.so")
-S3HEADER_PATH = os.path.join(_ROOT, "include", "vsr_hip_s3.h")
-S3TLIB_PATH = os.path.join(_PKG, "libvsr_hip_s3t.so")
-S3THEADER_PATH = os.path.join(_ROOT, "include", "vsr_hip_s3t.h")
-S3PLIB_PATH = os.path.join(_PKG, "libvsr_hip_s3p.so")
-S3PHEADER_PATH = os.path.join(_ROOT, "include", "vsr_hip_s3p.h")
 _lib = None
 _xlib = None
-_glib = None
-_s3lib = None
-_s3tlib = None
-S3FLIB_PATH = os.path.join(_PKG, "libvsr_hip_s3f.so")
-S3FHEADER_PATH = os.path.join(_ROOT, "include", "vsr_hip_s3f.h")
-_s3plib = None
-_s3flib = None
+
+
+def _side(name: str, prefix: str, abi: int, has_query: bool) -> tuple:
+    return (os.path.join(_PKG, f"libvsr_hip_{name}.so"), os.path.join(_ROOT, "include", f"vsr_hip_{name}.h"), prefix, abi, has_query)
+
+
+# the side libraries, each with a version entry and an error buffer of its own: (library, header, symbol prefix, ABI version, has a
+# `<prefix>_query`).  grad: the backward kernels of Resample2d, ChannelNorm and Correlation; s3: the fused FeedbackBlock stage of the x3
+# geometry (csrc/sr_utd_s3.hip); s3t: the one-launch x3 tail (csrc/sr_tail_s3.hip); s3p: the x3 stage with the next group's uptran slice
+# inside the launch (csrc/sr_utd_s3p.hip); s3f: the x3 stage with the step-opening 1x1 chain in its LR load path (csrc/sr_utd_s3f.hip)
+_SIDE = {"grad": _side("grad", "vsr_grad", 1, False), "s3": _side("s3", "vsr_s3", 1, True), "s3t": _side("s3t", "vsr_s3t", 1, True),
+         "s3p": _side("s3p", "vsr_s3p", 1, True), "s3f": _side("s3f", "vsr_s3f", 1, True)}
+(GLIB_PATH, GHEADER_PATH), (S3LIB_PATH, S3HEADER_PATH), (S3TLIB_PATH, S3THEADER_PATH), (S3PLIB_PATH, S3PHEADER_PATH), \
+    (S3FLIB_PATH, S3FHEADER_PATH) = (row[:2] for row in _SIDE.values())
+_gradlib = _s3lib = _s3tlib = _s3plib = _s3flib = None   # `_<name>lib`: the loaded side library (None: this process has not asked for it)
 # the cross-check library instead of the shipping one for every call (set by `xcheck()`; the environment switch serves the
 # measurement tools, whose VSR_TUNING codes only that library understands)
 _use_x = os.environ.get("VSR_USE_XCHECK", "0") == "1" or bool(os.environ.get("VSR_TUNING", "").strip())
@@ -62,7 +62,8 @@ def declared_symbols(xcheck: bool = False, grad: bool = False, s3: bool = False,
     """Entry points include/vsr_hip.h declares (xcheck: the ones include/vsr_hip_xcheck.h adds; grad / s3 / s3t / s3p / s3f: the ones of
     include/vsr_hip_grad.h / include/vsr_hip_s3.h / include/vsr_hip_s3t.h / include/vsr_hip_s3p.h / include/vsr_hip_s3f.h, libraries of
     their own)."""
-    with open(S3FHEADER_PATH if s3f else S3PHEADER_PATH if s3p else S3THEADER_PATH if s3t else S3HEADER_PATH if s3 else GHEADER_PATH if grad else XHEADER_PATH if xcheck else HEADER_PATH) as f:
+    side = [name for name, on in (("grad", grad), ("s3", s3), ("s3t", s3t), ("s3p", s3p), ("s3f", s3f)) if on]
+    with open(_SIDE[side[-1]][1] if side else XHEADER_PATH if xcheck else HEADER_PATH) as f:
         text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
     return sorted(set(re.findall(r"\b(vsr_[a-z0-9_]+)\s*\(", text)))
 
@@ -99,78 +100,45 @@ def load_xcheck() -> ctypes.CDLL:
     return _xlib
 
 
+def _load_side(name: str) -> ctypes.CDLL:
+    """The side library `name` of `_SIDE`, opened once.  Its own error buffer: `check(rc, what, lib=load_<name>())`."""
+    cache = f"_{name}lib"
+    if globals()[cache] is None:
+        path, _, prefix, abi, has_query = _SIDE[name]
+        lib = _dlopen(path)
+        getattr(lib, prefix + "_last_error").restype = ctypes.c_char_p
+        lib.vsr_last_error = getattr(lib, prefix + "_last_error")   # the name `check` reads a library's message under
+        if has_query:
+            getattr(lib, prefix + "_query").restype = ctypes.c_size_t
+        if getattr(lib, prefix + "_abi_version")() != abi:
+            raise VsrHipError(f"{os.path.basename(path)}: ABI version mismatch")
+        globals()[cache] = lib
+    return globals()[cache]
+
+
 def load_grad() -> ctypes.CDLL:
-    """libvsr_hip_grad.so (include/vsr_hip_grad.h): the backward kernels of Resample2d, ChannelNorm and Correlation.  Its own error
-    buffer: `check(rc, what, lib=load_grad())`."""
-    global _glib
-    if _glib is None:
-        lib = _dlopen(GLIB_PATH)
-        lib.vsr_grad_last_error.restype = ctypes.c_char_p
-        lib.vsr_last_error = lib.vsr_grad_last_error   # the name `check` reads a library's message under
-        if lib.vsr_grad_abi_version() != 1:
-            raise VsrHipError(f"{os.path.basename(GLIB_PATH)}: ABI version mismatch")
-        _glib = lib
-    return _glib
+    """libvsr_hip_grad.so (include/vsr_hip_grad.h)."""
+    return _load_side("grad")
 
 
 def load_s3() -> ctypes.CDLL:
-    """libvsr_hip_s3.so (include/vsr_hip_s3.h): the fused FeedbackBlock stage of the x3 geometry (csrc/sr_utd_s3.hip).  Its own error
-    buffer: `check(rc, what, lib=load_s3())`."""
-    global _s3lib
-    if _s3lib is None:
-        lib = _dlopen(S3LIB_PATH)
-        lib.vsr_s3_last_error.restype = ctypes.c_char_p
-        lib.vsr_last_error = lib.vsr_s3_last_error   # the name `check` reads a library's message under
-        lib.vsr_s3_query.restype = ctypes.c_size_t
-        if lib.vsr_s3_abi_version() != 1:
-            raise VsrHipError(f"{os.path.basename(S3LIB_PATH)}: ABI version mismatch")
-        _s3lib = lib
-    return _s3lib
+    """libvsr_hip_s3.so (include/vsr_hip_s3.h)."""
+    return _load_side("s3")
 
 
 def load_s3t() -> ctypes.CDLL:
-    """libvsr_hip_s3t.so (include/vsr_hip_s3t.h): the one-launch tail of the x3 geometry (csrc/sr_tail_s3.hip).  Its own error
-    buffer: `check(rc, what, lib=load_s3t())`."""
-    global _s3tlib
-    if _s3tlib is None:
-        lib = _dlopen(S3TLIB_PATH)
-        lib.vsr_s3t_last_error.restype = ctypes.c_char_p
-        lib.vsr_last_error = lib.vsr_s3t_last_error   # the name `check` reads a library's message under
-        lib.vsr_s3t_query.restype = ctypes.c_size_t
-        if lib.vsr_s3t_abi_version() != 1:
-            raise VsrHipError(f"{os.path.basename(S3TLIB_PATH)}: ABI version mismatch")
-        _s3tlib = lib
-    return _s3tlib
+    """libvsr_hip_s3t.so (include/vsr_hip_s3t.h)."""
+    return _load_side("s3t")
 
 
 def load_s3p() -> ctypes.CDLL:
-    """libvsr_hip_s3p.so (include/vsr_hip_s3p.h): the x3 stage with the next group's uptran slice inside the launch
-    (csrc/sr_utd_s3p.hip).  Its own error buffer: `check(rc, what, lib=load_s3p())`."""
-    global _s3plib
-    if _s3plib is None:
-        lib = _dlopen(S3PLIB_PATH)
-        lib.vsr_s3p_last_error.restype = ctypes.c_char_p
-        lib.vsr_last_error = lib.vsr_s3p_last_error   # the name `check` reads a library's message under
-        lib.vsr_s3p_query.restype = ctypes.c_size_t
-        if lib.vsr_s3p_abi_version() != 1:
-            raise VsrHipError(f"{os.path.basename(S3PLIB_PATH)}: ABI version mismatch")
-        _s3plib = lib
-    return _s3plib
+    """libvsr_hip_s3p.so (include/vsr_hip_s3p.h)."""
+    return _load_side("s3p")
 
 
 def load_s3f() -> ctypes.CDLL:
-    """libvsr_hip_s3f.so (include/vsr_hip_s3f.h): the x3 stage with the step-opening 1x1 chain in its LR load path
-    (csrc/sr_utd_s3f.hip).  Its own error buffer: `check(rc, what, lib=load_s3f())`."""
-    global _s3flib
-    if _s3flib is None:
-        lib = _dlopen(S3FLIB_PATH)
-        lib.vsr_s3f_last_error.restype = ctypes.c_char_p
-        lib.vsr_last_error = lib.vsr_s3f_last_error   # the name `check` reads a library's message under
-        lib.vsr_s3f_query.restype = ctypes.c_size_t
-        if lib.vsr_s3f_abi_version() != 1:
-            raise VsrHipError(f"{os.path.basename(S3FLIB_PATH)}: ABI version mismatch")
-        _s3flib = lib
-    return _s3flib
+    """libvsr_hip_s3f.so (include/vsr_hip_s3f.h)."""
+    return _load_side("s3f")
 
 
 def load() -> ctypes.CDLL:

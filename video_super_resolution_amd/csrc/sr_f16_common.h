@@ -110,4 +110,10 @@ __device__ __forceinline__ void bil4(int dst, int n, int& i0, int& i1, float& l1
 template <bool B>
 struct BoolC { static constexpr bool value = B; };
 
+// host: do the byte ranges [a, a + na) and [b, b + nb) share a byte (the entries refuse overlapping buffers before they launch)
+inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + nb && b0 < a0 + na;
+}
+
 }  // namespace

@@ -345,11 +345,6 @@ k_tail_s3(const _Float16* __restrict__ in, const unsigned char* __restrict__ blo
 
 typedef void (*kern_t)(const _Float16*, const unsigned char*, float*, int, int, int, int, const _Float16*, const float*);
 
-bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + nb && b0 < a0 + na;
-}
-
 int launch_tail_s3(const void* in, const void* in2, const float* cmap, const void* blob, float* raw, int N, int h, int w, int rows_per_seg,
                    int slopes_le_one, int decimate, vsr_stream_t stream, const char* what) {
     VSR_REQUIRE(in && blob && raw, "%s: null pointer", what);

@@ -520,4 +520,32 @@ k_utd_s3_pre(const _Float16* __restrict__ feat, const _Float16* __restrict__ pa,
     utd_s3_body<ALLMAX, POST, true>(feat, blob, out, h, w, rows_per_seg, out2, pa, pb, cmap);
 }
 
+// ---- host: what the three stage entries (sr_utd_s3.hip, sr_utd_s3p.hip, sr_utd_s3f.hip) check before they launch, and their grid
+struct S3Buf {
+    const void* p;
+    size_t bytes;
+    bool may_be_null;
+};
+
+// `what`: the entry's name in the messages; bufs: every buffer of the call with its length in bytes.  0 and `grid` (strips, row segments,
+// planes) / `rows_per_seg` (0 -> h: one march per strip) when the call may launch, else the error code with the message set.  Overlap is
+// refused on the byte ranges of EVERY pair of buffers given, after the size checks (which bound the ranges).
+inline int s3_stage_args(const char* what, const S3Buf* bufs, int nbufs, int N, int h, int w, int& rows_per_seg, dim3& grid) {
+    for (int i = 0; i < nbufs; ++i) VSR_REQUIRE(bufs[i].p || bufs[i].may_be_null, "%s: null pointer", what);
+    VSR_REQUIRE(N > 0 && h > 0 && w > 0 && rows_per_seg >= 0 && N <= 65535, "%s: bad shape (N %d, h %d, w %d, rows_per_seg %d)", what, N, h, w,
+                rows_per_seg);
+    for (int i = 0; i < nbufs; ++i)
+        VSR_REQUIRE((reinterpret_cast<uintptr_t>(bufs[i].p) & 15) == 0, "%s: pointers must be 16-byte aligned", what);
+    if ((size_t)N * h * w * NF * 2 >= (1ull << 32) - 16) return vsr::fail(VSR_E_UNSUPPORTED, "%s: tensors beyond 4 GiB (split the planes)", what);
+    if (rows_per_seg == 0) rows_per_seg = h;
+    const unsigned strips = vsr::cdiv(w, S3_TX), segs = vsr::cdiv(h, rows_per_seg);
+    VSR_REQUIRE(segs <= 65535, "%s: too many row segments", what);
+    for (int i = 0; i < nbufs; ++i)
+        for (int j = i + 1; j < nbufs; ++j)
+            VSR_REQUIRE(!bufs[i].p || !bufs[j].p || !ranges_overlap(bufs[i].p, bufs[i].bytes, bufs[j].p, bufs[j].bytes),
+                        "%s: the buffers of a call must not overlap", what);
+    grid = dim3(strips, segs, N);
+    return VSR_OK;
+}
+
 }  // namespace

@@ -8,15 +8,6 @@
 
 #include "../../include/vsr_hip_s3p.h"
 
-namespace {
-
-bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + nb && b0 < a0 + na;
-}
-
-}  // namespace
-
 extern "C" {
 
 int vsr_s3p_abi_version(void) { return VSR_S3P_ABI_VERSION; }
@@ -32,21 +23,11 @@ size_t vsr_s3p_query(int what) {
 
 int vsr_s3p_sr_utd_post_f16(const void* in, const void* blob, void* out, void* out_post, int N, int h, int w, int rows_per_seg,
                             int slopes_le_one, vsr_stream_t stream) {
-    VSR_REQUIRE(in && blob && out && out_post, "s3p_sr_utd_post: null pointer");
-    VSR_REQUIRE(N > 0 && h > 0 && w > 0 && rows_per_seg >= 0 && N <= 65535, "s3p_sr_utd_post: bad shape (N %d, h %d, w %d, rows_per_seg %d)", N, h, w,
-                rows_per_seg);
-    VSR_REQUIRE((reinterpret_cast<uintptr_t>(in) & 15) == 0 && (reinterpret_cast<uintptr_t>(blob) & 15) == 0 &&
-                    (reinterpret_cast<uintptr_t>(out) & 15) == 0 && (reinterpret_cast<uintptr_t>(out_post) & 15) == 0,
-                "s3p_sr_utd_post: pointers must be 16-byte aligned");
     const size_t bytes = (size_t)N * h * w * NF * 2;
-    VSR_REQUIRE(!ranges_overlap(in, bytes, out, bytes) && !ranges_overlap(in, bytes, out_post, bytes) && !ranges_overlap(out, bytes, out_post, bytes) &&
-                    !ranges_overlap(blob, S3_BLOB_POST_BYTES, out, bytes) && !ranges_overlap(blob, S3_BLOB_POST_BYTES, out_post, bytes),
-                "s3p_sr_utd_post: in, out and out_post must not overlap (nor an output the blob)");
-    if (bytes >= (1ull << 32) - 16) return vsr::fail(VSR_E_UNSUPPORTED, "s3p_sr_utd_post: tensors beyond 4 GiB (split the planes)");
-    if (rows_per_seg == 0) rows_per_seg = h;   // one march per strip
-    const unsigned strips = vsr::cdiv(w, S3_TX), segs = vsr::cdiv(h, rows_per_seg);
-    VSR_REQUIRE(segs <= 65535, "s3p_sr_utd_post: too many row segments");
-    hipLaunchKernelGGL(slopes_le_one ? k_utd_s3_post<true> : k_utd_s3_post<false>, dim3(strips, segs, N), dim3(256), S3_LDS + S3_LDS_POST,
+    const S3Buf bufs[] = {{in, bytes, false}, {blob, (size_t)S3_BLOB_POST_BYTES, false}, {out, bytes, false}, {out_post, bytes, false}};
+    dim3 grid;
+    if (int rc = s3_stage_args("s3p_sr_utd_post", bufs, 4, N, h, w, rows_per_seg, grid)) return rc;
+    hipLaunchKernelGGL(slopes_le_one ? k_utd_s3_post<true> : k_utd_s3_post<false>, grid, dim3(256), S3_LDS + S3_LDS_POST,
                        vsr::S(stream), (const _Float16*)in, (const unsigned char*)blob, (_Float16*)out, h, w, rows_per_seg, (_Float16*)out_post);
     return vsr::launched("s3p_sr_utd_post");
 }

@@ -693,29 +693,21 @@ class SRProjectionModule(nn.Module):
     # bit-identity reference of the older builds).  Equal to rounding, not bit for bit (the K dimension is summed in another order).
     utd_build = int(os.environ.get("VSR_UTD_BUILD", "4"))
 
-    def _utd4(self, a, blob, N, h, w, out=None, post=False):
+    def _utd4(self, a, blob, N, h, w, out=None, post=False, entry="vsr_sr_utd4_f16"):
         """The fused stage on k_utd4 -> out [N,h,w,32] fp16 (and, post=True, the next group's uptran slice of it)."""
         if out is None:
             out = torch.empty((N, h, w, _NF), dtype=torch.float16, device=a.device)
         out_post = torch.empty((N, h, w, _NF), dtype=torch.float16, device=a.device) if post else None
         tok = L.TIMER.start(self._utd_timer_name(N))
-        L.check(L.load().vsr_sr_utd4_f16(L.dptr(a, torch.float16), L.dptr(blob, torch.uint8), L.dptr(out, torch.float16), L.optr(out_post, torch.float16),
+        L.check(getattr(L.load(), entry)(L.dptr(a, torch.float16), L.dptr(blob, torch.uint8), L.dptr(out, torch.float16), L.optr(out_post, torch.float16),
                                          N, h, w, self._rows_per_segment(N, h, w, cus=getattr(self, "_utd_cus", 256), flat_ok=getattr(self, "utd_flat_split", True)),
-                                         int(self._pack["post_slopes_le_one"] if post else self._pack["slopes_le_one"]), L.stream()), "sr_utd4_f16")
+                                         int(self._pack["post_slopes_le_one"] if post else self._pack["slopes_le_one"]), L.stream()), entry[4:])
         L.TIMER.stop(tok)
         return (out, out_post) if post else out
 
     def _utd_post(self, a, blob, N, h, w, out=None):
-        """The fused stage + the next group's uptran slice on its output rows -> (out, out_post), both [N,h,w,32] fp16."""
-        if out is None:
-            out = torch.empty((N, h, w, _NF), dtype=torch.float16, device=a.device)
-        out_post = torch.empty((N, h, w, _NF), dtype=torch.float16, device=a.device)
-        tok = L.TIMER.start(self._utd_timer_name(N))
-        L.check(L.load().vsr_sr_utd_post_f16(L.dptr(a, torch.float16), L.dptr(blob, torch.uint8), L.dptr(out, torch.float16), L.dptr(out_post, torch.float16),
-                                             N, h, w, self._rows_per_segment(N, h, w, cus=getattr(self, "_utd_cus", 256), flat_ok=getattr(self, "utd_flat_split", True)),
-                                             int(self._pack["post_slopes_le_one"]), L.stream()), "sr_utd_post_f16")
-        L.TIMER.stop(tok)
-        return out, out_post
+        """The fused stage + the next group's uptran slice on its output rows (k_utd3's build) -> (out, out_post), both [N,h,w,32] fp16."""
+        return self._utd4(a, blob, N, h, w, out=out, post=True, entry="vsr_sr_utd_post_f16")
 
     def _utd(self, a, blob, N, h, w, deconv_only=False, out=None):
         if out is None:
@@ -730,27 +722,15 @@ class SRProjectionModule(nn.Module):
         L.TIMER.stop(tok)
         return out
 
-    def _forward_f16(self, x, P, cmap, taps, decimate=False, shared=None, precompute=None):
-        """`shared` (a dict owned by the caller, {"n": k}): the network treats its planes independently up to the fusion
-        MLP, so when two calls have their first k planes in common -- the three LR frames in both SR passes of
-        VSR.forward, video_super_resolution.py:40,62 -- the FeedbackBlock maps of those planes are computed by the first
-        call and kept here; the second call runs head + FeedbackBlock on its other planes only, writes them beside the
-        kept ones, and evaluates tail + fusion on all.  Same kernels on the same values: bit-identical frames
-        (tests/test_gpu_sr_f16.py::test_shared_planes_bit_identical).  The caller guarantees the planes are equal."""
-        lib = L.load()
-        N_all, _, h, w = x.shape
-        dev = x.device
-        G = self.block.num_groups
-        hp = h * w
-        n0 = n_sh = 0   # n_sh: the shared planes [0, n_sh) (their maps -- and tails, with `prefc_all` -- are kept); n0: first plane this call evaluates
+    def _share_plan(self, N_all, h, w, taps, shared, precompute):
+        """The share / `todo` bookkeeping of `_forward_f16` -> (skey, share_ok, n_sh, n0, m_done).  skey: what kept maps are valid for;
+        share_ok: this call may keep its first shared["n"] planes' maps; [0, n_sh): the shared planes whose maps -- and tails, with
+        `prefc_all` -- ARE kept; [n0, N_all - m_done): the planes this call evaluates."""
         if precompute is not None:   # `x` = the first planes only; their maps go to rows 0.. of the caller's buffers (precompute_shared)
-            N_tot = precompute[3].shape[0]
-            share_ok = False
-            skey = (self._pack_key, h, w, N_tot, self.upscale_factor)
-        else:
-            share_ok = shared is not None and taps is None and G == 6 and 0 < int(shared.get("n", 0)) < N_all
-            skey = (self._pack_key, h, w, N_all, self.upscale_factor)
-        m_done = 0
+            return (self._pack_key, h, w, precompute[3].shape[0], self.upscale_factor), False, 0, 0, 0
+        skey = (self._pack_key, h, w, N_all, self.upscale_factor)
+        share_ok = shared is not None and taps is None and self.block.num_groups == 6 and 0 < int(shared.get("n", 0)) < N_all
+        n0 = n_sh = m_done = 0
         if share_ok and shared.get("live") is not None and shared.get("key") == skey:
             n0 = n_sh = int(shared["n"])
             # `todo` = (a, b): the FeedbackBlock maps of every other plane of this call are in shared["live"] already (`precompute_rows`,
@@ -761,11 +741,56 @@ class SRProjectionModule(nn.Module):
                 if not (n0 <= a_ <= b_ <= N_all):
                     raise ValueError(f"shared['todo'] = {shared['todo']} outside the unshared planes [{n0}, {N_all})")
                 n0, m_done = int(a_), N_all - int(b_)
-        x_all, x = x, (x[n0:N_all - m_done] if (n0 or m_done) else x)
+        return skey, share_ok, n_sh, n0, m_done
+
+    def _forward_f16(self, x, P, cmap, taps, decimate=False, shared=None, precompute=None):
+        """`shared` (a dict owned by the caller, {"n": k}): the network treats its planes independently up to the fusion
+        MLP, so when two calls have their first k planes in common -- the three LR frames in both SR passes of
+        VSR.forward, video_super_resolution.py:40,62 -- the FeedbackBlock maps of those planes are computed by the first
+        call and kept here; the second call runs head + FeedbackBlock on its other planes only, writes them beside the
+        kept ones, and evaluates tail + fusion on all.  Same kernels on the same values: bit-identical frames
+        (tests/test_gpu_sr_f16.py::test_shared_planes_bit_identical).  The caller guarantees the planes are equal."""
+        N_all, _, h, w = x.shape
+        skey, share_ok, n_sh, n0, m_done = self._share_plan(N_all, h, w, taps, shared, precompute)
         N = N_all - n0 - m_done
         if (h, w) not in self._const_nhwc:
             self._const_nhwc[(h, w)] = cmap.t().contiguous()  # [h*w, 32] fp32, added before the activation
         cmap_nhwc = self._const_nhwc[(h, w)]
+        # where the last step writes its maps: beside the kept maps of the first call when this one shares planes, into the caller's
+        # buffers for precompute_shared / precompute_rows
+        into = precompute if precompute is not None else shared["live"] if n0 else None
+        dst = {k: into[k][n0:n0 + N].view(N, h, w, _NF) for k in (3, 6)} if into is not None else {}
+        live = self._steps_f16(x[n0:N_all - m_done] if (n0 or m_done) else x, P, cmap_nhwc, taps, dst)
+        if precompute is not None:
+            shared.update(live={k: precompute[k] for k in (3, 6)}, key=skey)
+            self._tail_ahead(P, precompute, shared, live, N, h, w, cmap_nhwc)
+            return None
+        if n_sh:
+            live = {k: shared["live"][k] for k in (3, 6)}
+        elif share_ok:
+            shared.update(live={k: live[k] for k in (3, 6)}, key=skey)
+        kept = shared is not None and shared.get("key") == skey and taps is None   # (`prefc_all` belongs to the kept maps)
+        return self._tail_f16(x, live, P, cmap_nhwc, taps, decimate, shared.get("prefc_all") if (n_sh and kept) else None, n_sh)
+
+    def _co(self, P, live, cmap_nhwc):
+        """Stage descriptor (`_chain`) of compress_out (SRProjectionModule.py:99) over the live maps."""
+        return dict(ins=[(live[k], P["co_w"], _NF * (k - 1)) for k in sorted(live) if k > 0], bias=P["co_b"], slope=P["co_a"], cmap=cmap_nhwc)
+
+    def _hid(self, P, live, N, hp, cmap_nhwc):
+        """compress_out as a launch of its own -> [N,hp,32] (more than 6 groups: three inputs, the plain 1x1)."""
+        co = self._co(P, live, cmap_nhwc)
+        return self._chain([co], N, hp, keep=[True])[0] if len(co["ins"]) <= 2 else self._c1h(co["ins"], P["co_b"], P["co_a"], N, hp, cmap=cmap_nhwc)
+
+    def _steps_f16(self, x, P, cmap_nhwc, taps, dst):
+        """Head + the FeedbackBlock steps of the planes `x` [N,3,h,w] -> the live maps {3: lr3, 6: lr6, ..} as [N,h*w,32] fp16 (with
+        taps: 0 too).  dst[k]: where the LAST step writes map k ([N,h,w,32]; absent: a new tensor)."""
+        lib = L.load()
+        N, _, h, w = x.shape
+        dev = x.device
+        G = self.block.num_groups
+        S = self.upscale_factor
+        hp = h * w
+        side = getattr(self, "_utd_side", False)
         feat = torch.empty((N, hp, _NF), dtype=torch.float16, device=dev)
         if N:
             x = x.contiguous()
@@ -775,175 +800,166 @@ class SRProjectionModule(nn.Module):
                                         L.cf(P["a_feat"]), L.dptr(feat, torch.float16), N, h, w, L.stream()), "sr_head_f16")
             L.TIMER.stop(tok)
         nchw = lambda t: t.view(N, h, w, _NF).permute(0, 3, 1, 2).float()
+        v4 = lambda t: None if t is None else t.view(N, h, w, _NF)
         if taps is not None:
             taps["feat_in"] = nchw(feat)
         if G < 3:
             raise NotImplementedError("num_groups < 3 leaves compress_out without a live input")
         want_lr0 = taps is not None
-        # stage descriptors of the 1x1 glue (SRProjectionModule.py:47-48 compress_in, :55-61 uptran slice, :99 compress_out)
+        # stage descriptors of the 1x1 glue (SRProjectionModule.py:47-48 compress_in, :55-61 uptran slice)
         ci = lambda last: dict(ins=[(feat, P["ci_w"], 0), (last, P["ci_w"], _NF)], bias=P["ci_b"], slope=P["ci_a"])
         ut = lambda j, src=None: dict(ins=[] if src is None else [(src, P["ut_w"][j], _NF * (j + 1))],
                                       prev=None if src is not None else (P["ut_w"][j], _NF * (j + 1)), bias=P["ut_b"][j], slope=P["ut_a"][j])
-        co = lambda live: dict(ins=[(live[k], P["co_w"], _NF * (k - 1)) for k in sorted(live) if k > 0], bias=P["co_b"], slope=P["co_a"],
-                               cmap=cmap_nhwc)
         live = {}
-        hid = None
+        stage_post, utd_post = P.get("stage_post", ()), P.get("utd_post", ())
         for step in range(self.num_steps if N else 0):
+            last_step = step == self.num_steps - 1
             # x3: that chain inside the first stage's LR load path (`fold_chain`); the taps path needs its intermediate tensors
-            fold = (self.fold_chain and self.upscale_factor == 3 and G == 6 and taps is None and not L._use_x and 0 in P.get("stage_pre", {})
+            fold = (self.fold_chain and S == 3 and G == 6 and taps is None and not L._use_x and 0 in P.get("stage_pre", {})
                     and (step == 0 or sorted(live) == [3, 6]) and (3 if step > 0 else 2) in self.fold_chain_modes)
             # one launch: (compress_out of the previous step ->) compress_in -> uptran slice of group 1
             if fold:
-                prev_a, prev_b = (live[3], live[6]) if step > 0 else (None, None)
+                prev = (live[3], live[6], cmap_nhwc) if step > 0 else (None, None, None)
                 outs = [None, None]
-            elif step > 0 and len(co(live)["ins"]) > 2:   # more than 6 groups: compress_out on its own (three inputs)
-                hid = self._c1h(co(live)["ins"], P["co_b"], P["co_a"], N, hp, cmap=cmap_nhwc)
+            elif step > 0 and len(self._co(P, live, cmap_nhwc)["ins"]) > 2:   # more than 6 groups: compress_out on its own (three inputs)
+                hid = self._hid(P, live, N, hp, cmap_nhwc)
                 outs = [hid] + self._chain([ci(hid), ut(0)], N, hp, keep=[want_lr0, True])
             elif step > 0:
                 ci_chained = dict(ins=[(feat, P["ci_w"], 0)], prev=(P["ci_w"], _NF), bias=P["ci_b"], slope=P["ci_a"])
-                outs = self._chain([co(live), ci_chained, ut(0)], N, hp, keep=[taps is not None, want_lr0, True])
+                outs = self._chain([self._co(P, live, cmap_nhwc), ci_chained, ut(0)], N, hp, keep=[taps is not None, want_lr0, True])
             else:
                 outs = self._chain([ci(feat), ut(0)], N, hp, keep=[want_lr0, True])
             if taps is not None and step > 0:
                 taps[f"block{step - 1}"] = nchw(outs[0])
             live = {0: outs[-2]} if want_lr0 else {}
             a = outs[-1]
-            j = 0
             a_next = None
-            while j + 3 <= G:
+            for j in range(0, G - 2, 3):   # lr[j] -> hr[j+1] -> lr[j+3]
                 if j > 0:
                     a = a_next if a_next is not None else self._chain([ut(j, live[j])], N, hp, keep=[True])[0]
-                    a_next = None
-                # (the last step of a call that shares planes writes beside the kept maps of the first call)
-                dst = shared["live"][j + 3][n0:n0 + N].view(N, h, w, _NF) if (n0 and step == self.num_steps - 1) else None
-                if precompute is not None and step == self.num_steps - 1:
-                    dst = precompute[j + 3][:N].view(N, h, w, _NF)
-                if fold and j == 0:
-                    v4 = lambda t: None if t is None else t.view(N, h, w, _NF)
-                    r = P["stage_pre"][0](feat.view(N, h, w, _NF), v4(prev_a), v4(prev_b), cmap_nhwc if step > 0 else None, out=dst,
-                                          side=getattr(self, "_utd_side", False), post=self.fuse_uptran)
-                    if self.fuse_uptran:
-                        live[3], a_next = r[0].view(N, hp, _NF), r[1].view(N, hp, _NF)
-                    else:
-                        live[3] = r.view(N, hp, _NF)
-                elif self.upscale_factor == 4 and self.utd_build == 4 and not L._use_x:
-                    if self.fuse_uptran and j + 6 <= G:
-                        o, a_next = self._utd4(a, P["utd4"][j], N, h, w, out=dst, post=True)
-                        live[j + 3], a_next = o.view(N, hp, _NF), a_next.view(N, hp, _NF)
-                    else:
-                        live[j + 3] = self._utd4(a, P["utd4"][j], N, h, w, out=dst).view(N, hp, _NF)
-                elif self.upscale_factor == 4 and self.fuse_uptran and j in P.get("utd_post", {}) and not L._use_x:
-                    o, a_next = self._utd_post(a, P["utd_post"][j], N, h, w, out=dst)
-                    live[j + 3], a_next = o.view(N, hp, _NF), a_next.view(N, hp, _NF)
-                elif self.upscale_factor != 4 and self.fuse_uptran and getattr(P["stage"][j], "has_post", False) and not L._use_x:
-                    o, a_next = P["stage"][j](a.view(N, h, w, _NF), self._chain, out=dst, side=getattr(self, "_utd_side", False), post=True)
-                    live[j + 3], a_next = o.view(N, hp, _NF), a_next.view(N, hp, _NF)
-                elif self.upscale_factor == 3 and self.fuse_uptran and j in P.get("stage_post", {}) and not L._use_x:
-                    o, a_next = P["stage_post"][j](a.view(N, h, w, _NF), self._chain, out=dst, side=getattr(self, "_utd_side", False), post=True)
-                    live[j + 3], a_next = o.view(N, hp, _NF), a_next.view(N, hp, _NF)
+                out = dst.get(j + 3) if last_step else None
+                build, post = _stage_route(S, j, G, fold, self.fuse_uptran, self.utd_build, L._use_x,
+                                           S != 4 and getattr(P["stage"][j], "has_post", False), j in stage_post, j in utd_post)
+                if build == "pre":
+                    r = P["stage_pre"][0](v4(feat), v4(prev[0]), v4(prev[1]), prev[2], out=out, side=side, post=post)
+                elif S == 4:
+                    r = getattr(self, "_" + build)(a, P[build][j], N, h, w, out=out, **({"post": True} if build == "utd4" and post else {}))
                 else:
-                    live[j + 3] = (self._utd(a, P["utd"][j], N, h, w, out=dst) if self.upscale_factor == 4 else
-                                   P["stage"][j](a.view(N, h, w, _NF), self._chain, out=dst, side=getattr(self, "_utd_side", False))).view(N, hp, _NF)
-                j += 3
-            if taps is not None and step == self.num_steps - 1:
+                    r = P[build][j](v4(a), self._chain, out=out, side=side, **({"post": True} if post else {}))
+                o, a_next = r if post else (r, None)
+                live[j + 3], a_next = o.view(N, hp, _NF), (None if a_next is None else a_next.view(N, hp, _NF))
+            if taps is not None and last_step:
                 for k, v in live.items():
                     taps[f"lr{k}"] = nchw(v)
-        if precompute is not None:
-            shared.update(live={k: precompute[k] for k in (3, 6)}, key=skey)
-            pre = precompute.get("prefc")
-            if (pre is not None and self.upscale_factor == 4 and self.fold_tail and self.tail_build == 3 and "utd_out_fold" in P and
-                    tuple(pre.shape) == (N_tot, 3, 4 * h, 4 * w)):
-                # ... and their pre-fusion planes at FULL resolution (rows 0..N-1 of the caller's buffer): pass 2's tail then runs on
-                # its other planes only, and pass 1 reads its pixels (4i, 4j) out of these (the decimated tail returns exactly the full
-                # tail's values there: tests/test_gpu_sr_f16.py::test_decimated_output_is_a_subset_of_the_full_frame)
-                tok = L.TIMER.start("sr_tail_f16_p%d" % N)
-                L.check(lib.vsr_sr_tail3_fold_f16(L.dptr(precompute[3], torch.float16), L.dptr(precompute[6], torch.float16), L.dptr(cmap_nhwc),
-                                                  L.dptr(P["utd_out_fold"], torch.uint8), L.dptr(P["cv_frags3"], torch.float16),
-                                                  L.dptr(P["tail_par"]), L.dptr(pre), N, h, w,
-                                                  self._rows_per_segment(N, h, w, cus=getattr(self, "_utd_cus", 256)),
-                                                  int(P["slopes_le_one"]), 0, L.stream()), "sr_tail3_fold_f16")
-                L.TIMER.stop(tok)
-                shared["prefc_all"] = pre
-            elif (pre is not None and self.upscale_factor != 4 and self._tail_key(P) and tuple(pre.shape) == (N_tot, 3, self.upscale_factor * h, self.upscale_factor * w) and
-                  len(co(live)["ins"]) <= 2):
-                # scale 2 / 3: the same for the one-launch tails of csrc/sr_tail_s2.hip / sr_tail_s3.hip (compress_out of the kept maps inside
-                # their LR load path, or -- cross-check -- as its own launch first)
-                fold = self._fold_tail(P, live, N, h, w, cmap_nhwc)
-                hid = fold[0] if fold else self._chain([co(live)], N, hp, keep=[True])[0].view(N, h, w, _NF)
-                self._tail_raw(hid, P, False, pre[:N], cus=2 * getattr(self, "_utd_cus", 256), fold=fold)
-                shared["prefc_all"] = pre
-            return None
-        if n_sh:
-            live = {k: shared["live"][k] for k in (3, 6)}
-            N, x = N_all, x_all
-            n0 = n_sh
-        elif share_ok:
-            shared.update(live={k: live[k] for k in (3, 6)}, key=skey)
+        return live
+
+    @staticmethod
+    def _planes_ahead(pre, nt, N, S, h, w, n_live, dev):
+        """How many leading planes of the tail were evaluated ahead (`precompute_shared` with a "prefc" buffer): nt, when `pre` is their
+        [N,3,Sh,Sw] buffer on this device and compress_out reads at most two live maps, else 0."""
+        return nt if (pre is not None and tuple(pre.shape) == (N, 3, S * h, S * w) and pre.device == dev and n_live <= 2) else 0
+
+    @staticmethod
+    def _planes_buffer(pre, nt, N, S, ho, wo, decimate, dev):
+        """The [N,3,ho,wo] float32 buffer the tail writes planes nt.. of: `pre` itself, whose first nt planes were evaluated ahead at full
+        resolution, when the full frame is wanted; else a new one, with their pixels (S i, S j) copied in."""
+        if nt and not decimate:
+            return pre
+        buf = torch.empty((N, 3, ho, wo), dtype=torch.float32, device=dev)
+        if nt:
+            buf[:nt].copy_(pre[:nt, :, ::S, ::S])
+        return buf
+
+    def _fuse_planes(self, raw, x, P, decimate):
+        """Skip + add_mean + the fusion MLP over the raw tail planes `raw` [N,3,.,.] of the LR planes `x` -> [1,3,.,.] (x4: csrc/sr_f16.hip,
+        other scales: csrc/sr_scale.hip)."""
+        N, _, h, w = x.shape
+        S = self.upscale_factor
+        lib = L.load()
+        out = torch.empty((1,) + tuple(raw.shape[1:]), dtype=torch.float32, device=raw.device)
+        what = "sr_fc_planes_skip" if S == 4 else "sr_fc_planes_skip_scale"
+        tok = L.TIMER.start(what + ("_dec" if decimate and S == 4 else "")) if L.TIMER.enabled else None
+        fn, scale = (lib.vsr_sr_fc_planes_skip_f32, ()) if S == 4 else (lib.vsr_sr_fc_planes_skip_scale_f32, (S,))
+        L.check(fn(L.dptr(raw), L.dptr(x), L.dptr(P["tail_par"]), L.dptr(P["fc_w1"]), L.dptr(P["fc_b1"]), L.dptr(P["fc_w2"]), L.dptr(P["fc_b2"]),
+                   N, P["fc_w1"].shape[0], L.dptr(out), h, w, *scale, int(decimate), L.stream()), what)
+        L.TIMER.stop(tok)
+        return out
+
+    def _tail3_fold(self, lr3, lr6, cmap_nhwc, P, prefc, N, h, w, cus, decimate, name):
+        """compress_out + `out` deconvolution + conv_out of N planes in one launch (k_tail3<.., FOLD>) into `prefc` (rows of the caller's)."""
+        tok = L.TIMER.start(name)
+        L.check(L.load().vsr_sr_tail3_fold_f16(L.dptr(lr3, torch.float16), L.dptr(lr6, torch.float16), L.dptr(cmap_nhwc),
+                                               L.dptr(P["utd_out_fold"], torch.uint8), L.dptr(P["cv_frags3"], torch.float16),
+                                               L.dptr(P["tail_par"]), L.dptr(prefc), N, h, w, self._rows_per_segment(N, h, w, cus=cus),
+                                               int(P["slopes_le_one"]), int(decimate), L.stream()), "sr_tail3_fold_f16")
+        L.TIMER.stop(tok)
+
+    def _tail_ahead(self, P, precompute, shared, live, N, h, w, cmap_nhwc):
+        """precompute_shared with a `prefc` buffer: the first planes' pre-fusion planes at FULL resolution (rows 0..N-1 of the caller's
+        buffer), where a build exists.  Pass 2's tail then runs on its other planes only, and pass 1 reads its pixels (S i, S j) out of
+        these (the decimated tail returns exactly the full tail's values there:
+        tests/test_gpu_sr_f16.py::test_decimated_output_is_a_subset_of_the_full_frame)."""
+        S = self.upscale_factor
+        pre = precompute.get("prefc")
+        if pre is None or tuple(pre.shape) != (precompute[3].shape[0], 3, S * h, S * w):
+            return
+        cus = getattr(self, "_utd_cus", 256)
+        if S == 4 and self.fold_tail and self.tail_build == 3 and "utd_out_fold" in P:
+            self._tail3_fold(precompute[3], precompute[6], cmap_nhwc, P, pre, N, h, w, cus, False, "sr_tail_f16_p%d" % N)
+        elif S != 4 and self._tail_key(P) and sum(k > 0 for k in live) <= 2:
+            # scale 2 / 3: the one-launch tails of csrc/sr_tail_s2.hip / sr_tail_s3.hip (compress_out of the kept maps inside their LR load
+            # path, or -- cross-check -- as its own launch first)
+            fold = self._fold_tail(P, live, N, h, w, cmap_nhwc)
+            hid = fold[0] if fold else self._hid(P, live, N, h * w, cmap_nhwc).view(N, h, w, _NF)
+            self._tail_raw(hid, P, False, pre[:N], cus=2 * cus, fold=fold)
+        else:
+            return
+        shared["prefc_all"] = pre
+
+    def _tail_f16(self, x, live, P, cmap_nhwc, taps, decimate, pre, n_sh):
+        """The live maps of all planes `x` [N,3,h,w] -> the frame [1,3,.,.]: compress_out, `out` deconvolution, conv_out, skip + add_mean,
+        fusion MLP.  pre: the planes buffer whose first n_sh planes `precompute_shared` evaluated ahead, or None."""
+        N, _, h, w = x.shape
+        dev = x.device
+        hp = h * w
         S = self.upscale_factor
         ho, wo = (h, w) if decimate else (S * h, S * w)
+        nchw = lambda t: t.view(N, h, w, _NF).permute(0, 3, 1, 2).float()
+        n_live = sum(k > 0 for k in live)
         if S != 4:
-            # the shared planes' raw tail output was evaluated ahead (precompute_shared): compress_out + tail on the others only
-            pre = shared.get("prefc_all") if (n0 and shared is not None and shared.get("key") == skey and taps is None) else None
-            nt = n0 if (pre is not None and tuple(pre.shape) == (N, 3, S * h, S * w) and pre.device == dev and len(co(live)["ins"]) <= 2) else 0
+            # the shared planes' raw tail output was evaluated ahead: compress_out + tail on the others only
+            nt = self._planes_ahead(pre, n_sh, N, S, h, w, n_live, dev)
             if nt:
-                live_t = {k: v[nt:] for k, v in live.items()}
-                fold = self._fold_tail(P, live_t, N - nt, h, w, cmap_nhwc)
-                hid = fold[0] if fold else self._chain([co(live_t)], N - nt, hp, keep=[True])[0].view(N - nt, h, w, _NF)
-                return self._tail_unfused(x, hid, P, decimate, taps, pre=pre, fold=fold)
-            fold = self._fold_tail(P, live, N, h, w, cmap_nhwc) if taps is None else None
-            if fold:
-                return self._tail_unfused(x, fold[0], P, decimate, taps, fold=fold)
-            hid = self._chain([co(live)], N, hp, keep=[True])[0] if len(co(live)["ins"]) <= 2 else \
-                self._c1h(co(live)["ins"], P["co_b"], P["co_a"], N, hp, cmap=cmap_nhwc)
+                live = {k: v[nt:] for k, v in live.items()}
+            fold = self._fold_tail(P, live, N - nt, h, w, cmap_nhwc) if taps is None else None
+            hid = fold[0] if fold else self._hid(P, live, N - nt, hp, cmap_nhwc).view(N - nt, h, w, _NF)
             if taps is not None:
                 taps[f"block{self.num_steps - 1}"] = nchw(hid)
-            return self._tail_unfused(x, hid.view(N, h, w, _NF), P, decimate, taps)
+            return self._tail_unfused(x, hid, P, decimate, taps, pre=pre, fold=fold)
         if self.fold_tail and taps is None and self.tail_build == 3 and "utd_out_fold" in P and sorted(k for k in live if k > 0) == [3, 6]:
             # compress_out inside the tail (k_tail3<.., FOLD>): no `hid` tensor, one launch less
             # the shared planes' pre-fusion planes were evaluated ahead (precompute_shared): the tail runs on the others only
-            pre = shared.get("prefc_all") if (n0 and shared is not None and shared.get("key") == skey) else None
-            nt = n0 if (pre is not None and tuple(pre.shape) == (N, 3, S * h, S * w) and pre.device == dev) else 0
-            if nt and not decimate:
-                prefc = pre
-            else:
-                prefc = torch.empty((N, 3, ho, wo), dtype=torch.float32, device=dev)
-                if nt:
-                    prefc[:nt].copy_(pre[:nt, :, ::S, ::S])
-            out = torch.empty((1, 3, ho, wo), dtype=torch.float32, device=dev)
-            tok = L.TIMER.start(("sr_tail_dec_f16" if decimate else "sr_tail_f16") + (f"_p{N - nt}" if nt else ""))
-            L.check(lib.vsr_sr_tail3_fold_f16(L.dptr(live[3][nt:], torch.float16), L.dptr(live[6][nt:], torch.float16), L.dptr(cmap_nhwc),
-                                              L.dptr(P["utd_out_fold"], torch.uint8), L.dptr(P["cv_frags3"], torch.float16),
-                                              L.dptr(P["tail_par"]), L.dptr(prefc[nt:]), N - nt, h, w, self._rows_per_segment(N - nt, h, w),
-                                              int(P["slopes_le_one"]), int(decimate), L.stream()), "sr_tail3_fold_f16")
-            L.TIMER.stop(tok)
-            tok = L.TIMER.start("sr_fc_planes_skip_dec" if decimate else "sr_fc_planes_skip") if L.TIMER.enabled else None
-            L.check(lib.vsr_sr_fc_planes_skip_f32(L.dptr(prefc), L.dptr(x), L.dptr(P["tail_par"]), L.dptr(P["fc_w1"]), L.dptr(P["fc_b1"]),
-                                                  L.dptr(P["fc_w2"]), L.dptr(P["fc_b2"]), N, P["fc_w1"].shape[0], L.dptr(out), h, w,
-                                                  int(decimate), L.stream()), "sr_fc_planes_skip")
-            L.TIMER.stop(tok)
-            return out
-        hid = self._chain([co(live)], N, hp, keep=[True])[0] if len(co(live)["ins"]) <= 2 else \
-            self._c1h(co(live)["ins"], P["co_b"], P["co_a"], N, hp, cmap=cmap_nhwc)
+            nt = self._planes_ahead(pre, n_sh, N, S, h, w, n_live, dev)
+            prefc = self._planes_buffer(pre, nt, N, S, ho, wo, decimate, dev)
+            self._tail3_fold(live[3][nt:], live[6][nt:], cmap_nhwc, P, prefc[nt:], N - nt, h, w, 256, decimate,
+                             ("sr_tail_dec_f16" if decimate else "sr_tail_f16") + (f"_p{N - nt}" if nt else ""))
+            return self._fuse_planes(prefc, x, P, decimate)
+        hid = self._hid(P, live, N, hp, cmap_nhwc)
         if taps is not None:
             taps[f"block{self.num_steps - 1}"] = nchw(hid)
         prefc = torch.empty((N, 3, ho, wo), dtype=torch.float32, device=dev)
         tok = L.TIMER.start("sr_tail_dec_f16" if decimate else "sr_tail_f16")
-        out = torch.empty((1, 3, ho, wo), dtype=torch.float32, device=dev)
         if self.tail_build == 3 and taps is None:
             # k_tail3 (one wave per SIMD, registers) writes the raw planes; skip + add_mean ride on the fusion MLP's read
-            L.check(lib.vsr_sr_tail3_f16(L.dptr(hid, torch.float16), L.dptr(P["utd_out"], torch.uint8), L.dptr(P["cv_frags3"], torch.float16),
-                                         L.dptr(P["tail_par"]), L.dptr(prefc), N, h, w, self._rows_per_segment(N, h, w),
-                                         int(P["slopes_le_one"]), int(decimate), L.stream()), "sr_tail3_f16")
+            L.check(L.load().vsr_sr_tail3_f16(L.dptr(hid, torch.float16), L.dptr(P["utd_out"], torch.uint8), L.dptr(P["cv_frags3"], torch.float16),
+                                              L.dptr(P["tail_par"]), L.dptr(prefc), N, h, w, self._rows_per_segment(N, h, w),
+                                              int(P["slopes_le_one"]), int(decimate), L.stream()), "sr_tail3_f16")
             L.TIMER.stop(tok)
-            tok = L.TIMER.start("sr_fc_planes_skip_dec" if decimate else "sr_fc_planes_skip") if L.TIMER.enabled else None
-            L.check(lib.vsr_sr_fc_planes_skip_f32(L.dptr(prefc), L.dptr(x), L.dptr(P["tail_par"]), L.dptr(P["fc_w1"]), L.dptr(P["fc_b1"]),
-                                                  L.dptr(P["fc_w2"]), L.dptr(P["fc_b2"]), N, P["fc_w1"].shape[0], L.dptr(out), h, w,
-                                                  int(decimate), L.stream()), "sr_fc_planes_skip")
-            L.TIMER.stop(tok)
-            return out
+            return self._fuse_planes(prefc, x, P, decimate)
         # k_tail: two waves per SIMD, LDS ring, skip inside the tail (a superseded build in the cross-check library,
         # include/vsr_hip_xcheck.h; it also serves the prefc tap of the tests)
         lib = L.load_xcheck()
+        out = torch.empty((1, 3, ho, wo), dtype=torch.float32, device=dev)
         tail = lib.vsr_sr_tail_dec_f16 if decimate else lib.vsr_sr_tail_f16
         L.check(tail(L.dptr(hid, torch.float16), L.dptr(P["utd_out"], torch.uint8), L.dptr(P["cv_frags"], torch.float16),
                      L.dptr(P["tail_par"]), L.dptr(x), L.dptr(prefc), N, h, w, self._rows_per_segment(N, h, w),
@@ -975,39 +991,23 @@ class SRProjectionModule(nn.Module):
         lib = L.load()
         N, h, w, _ = hid.shape
         S = self.upscale_factor
-        if S == 3 and "tail_s3" in P:   # scale 3: the same in csrc/sr_tail_s3.hip, a library of its own (planes split by its 4 GiB limit alone)
-            lib3 = L.load_s3t()
-            nbt = max(1, min(N, ((1 << 32) - 32) // (h * w * _NF * 2)))
-            for n0 in range(0, N, nbt):
-                n = min(nbt, N - n0)
-                tok = L.TIMER.start("sr_tail_s3_dec_f16" if decimate else "sr_tail_s3_f16") if L.TIMER.enabled else None
-                rows = self._rows_per_segment(n, h, w, cus=cus, strip=30)
-                if fold:
-                    L.check(lib3.vsr_s3t_sr_tail_fold_f16(L.dptr(fold[0][n0:n0 + n], torch.float16), L.dptr(fold[1][n0:n0 + n], torch.float16), L.dptr(fold[2]),
-                                                          L.dptr(P["tail_s3"], torch.uint8), L.dptr(raw[n0:n0 + n]), n, h, w, rows,
-                                                          int(P["slopes_le_one"]), int(decimate), L.stream()), "sr_tail_s3_fold_f16", lib=lib3)
-                else:
-                    L.check(lib3.vsr_s3t_sr_tail_f16(L.dptr(hid[n0:n0 + n], torch.float16), L.dptr(P["tail_s3"], torch.uint8), L.dptr(raw[n0:n0 + n]),
-                                                     n, h, w, rows, int(P["slopes_le_one"]), int(decimate), L.stream()), "sr_tail_s3_f16", lib=lib3)
-                L.TIMER.stop(tok)
+        key = self._tail_key(P)
+        if key:
+            # deconvolution + conv_out in one launch, the HR map stays in LDS (scale 2: csrc/sr_tail_s2.hip; scale 3: csrc/sr_tail_s3.hip, a
+            # library of its own); planes split by the kernels' 4 GiB limit alone
+            own, entry = (L.load_s3t(), "vsr_s3t_sr_tail") if S == 3 else (None, "vsr_sr_tail_s2")
+            fn = getattr(own or lib, entry + ("_fold_f16" if fold else "_f16"))
+            blob, flags = L.dptr(P[key], torch.uint8), (int(P["slopes_le_one"]), int(decimate), L.stream())
+            if fold:
+                launch = lambda n0, n, rows: fn(L.dptr(fold[0][n0:n0 + n], torch.float16), L.dptr(fold[1][n0:n0 + n], torch.float16), L.dptr(fold[2]),
+                                                blob, L.dptr(raw[n0:n0 + n]), n, h, w, rows, *flags)
+            else:
+                launch = lambda n0, n, rows: fn(L.dptr(hid[n0:n0 + n], torch.float16), blob, L.dptr(raw[n0:n0 + n]), n, h, w, rows, *flags)
+            _launch_chunks(f"sr_tail_s{S}" + ("_dec_f16" if decimate else "_f16"), N, h, w, self._rows_per_segment, cus, 30, launch,
+                           f"sr_tail_s{S}" + ("_fold_f16" if fold else "_f16"), lib=own, planes_in_name=False)
             return
         nb = _planes_per_chunk(N, S * h, S * w)
-        if "tail_s2" in P:   # scale 2: deconvolution + conv_out in one launch, the x2 map stays in LDS (csrc/sr_tail_s2.hip)
-            nbt = max(1, min(N, ((1 << 32) - 32) // (h * w * _NF * 2)))
-            for n0 in range(0, N, nbt):
-                n = min(nbt, N - n0)
-                tok = L.TIMER.start("sr_tail_s2_dec_f16" if decimate else "sr_tail_s2_f16") if L.TIMER.enabled else None
-                rows = self._rows_per_segment(n, h, w, cus=cus, strip=30)
-                if fold:
-                    L.check(lib.vsr_sr_tail_s2_fold_f16(L.dptr(fold[0][n0:n0 + n], torch.float16), L.dptr(fold[1][n0:n0 + n], torch.float16), L.dptr(fold[2]),
-                                                        L.dptr(P["tail_s2"], torch.uint8), L.dptr(raw[n0:n0 + n]), n, h, w, rows,
-                                                        int(P["slopes_le_one"]), int(decimate), L.stream()), "sr_tail_s2_fold_f16")
-                else:
-                    L.check(lib.vsr_sr_tail_s2_f16(L.dptr(hid[n0:n0 + n], torch.float16), L.dptr(P["tail_s2"], torch.uint8), L.dptr(raw[n0:n0 + n]),
-                                                   n, h, w, rows, int(P["slopes_le_one"]), int(decimate), L.stream()), "sr_tail_s2_f16")
-                L.TIMER.stop(tok)
-            nb = 0
-        for n0 in (range(0, N, nb) if nb else ()):
+        for n0 in range(0, N, nb):
             hr = P["out_deconv"](hid[n0:n0 + nb])
             tok = L.TIMER.start("sr_convout_planes_f16") if L.TIMER.enabled else None
             L.check(lib.vsr_sr_convout_planes_f16(L.dptr(hr, torch.float16), L.dptr(P["cv_w"]), L.dptr(P["cv_b"]), L.dptr(raw[n0:n0 + nb]),
@@ -1020,30 +1020,55 @@ class SRProjectionModule(nn.Module):
         (SRProjectionModule.py:142-146): phase convolutions on the generic MFMA kernel, then csrc/sr_scale.hip.  `x`: all planes;
         `hid`: the LAST hid.shape[0] of them -- the first ones' raw tail output is rows 0.. of `pre` [planes,3,Sh,Sw] (evaluated
         ahead at full resolution, precompute_shared)."""
-        lib = L.load()
         N = x.shape[0]
         Nh, h, w, _ = hid.shape
         nt = N - Nh
         S = self.upscale_factor
-        dev = hid.device
         ho, wo = (h, w) if decimate else (S * h, S * w)
-        if nt and not decimate:
-            raw = pre
-        else:
-            raw = torch.empty((N, 3, ho, wo), dtype=torch.float32, device=dev)
-            if nt:
-                raw[:nt].copy_(pre[:nt, :, ::S, ::S])
+        raw = self._planes_buffer(pre, nt, N, S, ho, wo, decimate, hid.device)
         self._tail_raw(hid, P, decimate, raw[nt:], fold=fold)
-        out = torch.empty((1, 3, ho, wo), dtype=torch.float32, device=dev)
-        tok = L.TIMER.start("sr_fc_planes_skip_scale") if L.TIMER.enabled else None
-        L.check(lib.vsr_sr_fc_planes_skip_scale_f32(L.dptr(raw), L.dptr(x), L.dptr(P["tail_par"]), L.dptr(P["fc_w1"]), L.dptr(P["fc_b1"]),
-                                                    L.dptr(P["fc_w2"]), L.dptr(P["fc_b2"]), N, P["fc_w1"].shape[0], L.dptr(out), h, w, S,
-                                                    int(decimate), L.stream()), "sr_fc_planes_skip_scale")
-        L.TIMER.stop(tok)
-        return out
+        return self._fuse_planes(raw, x, P, decimate)
 
     def _reset_state(self):  # API parity with SRProjectionModule.py:149-150; the state never outlives a forward here
         return None
+
+
+def _stage_route(scale, j, G, fold, fuse_uptran, utd_build, use_x, has_post, in_stage_post, in_utd_post):
+    """Which build runs the stage lr[j] -> hr[j+1] -> lr[j+3] of a step, and whether it also returns the next group's uptran slice (POST)
+    -> (build, post).  build: "pre" (P["stage_pre"][0]: x3, the step-opening chain folded in), "utd4" / "utd_post" / "utd" (x4: the pack
+    key and, with a leading underscore, the wrapper), "stage" / "stage_post" (x2, x3: the pack key).  has_post: P["stage"][j] can apply the
+    uptran slice itself; in_stage_post / in_utd_post: j has an entry in P["stage_post"] / P["utd_post"] (another stage follows)."""
+    if fold and j == 0:
+        return "pre", bool(fuse_uptran)
+    plain = "utd" if scale == 4 else "stage"
+    if use_x:   # the cross-check library holds neither k_utd4 nor a POST build
+        return plain, False
+    if scale == 4 and utd_build == 4:
+        return "utd4", bool(fuse_uptran and j + 6 <= G)
+    if not fuse_uptran:
+        return plain, False
+    if scale == 4:
+        return ("utd_post", True) if in_utd_post else (plain, False)
+    if has_post:
+        return "stage", True
+    return ("stage_post", True) if scale == 3 and in_stage_post else (plain, False)
+
+
+def _plane_chunks(N, h, w):
+    """[(n0, n), ..]: the planes [n0, n0 + n) of each launch of a strip-marching stage or tail kernel over N planes of h x w: as many as
+    keep the [n,h,w,32] fp16 tensor below the 4 GiB the kernels' 32-bit byte offsets reach (one plane at the least: the entry refuses)."""
+    nb = max(1, min(N, ((1 << 32) - 32) // (h * w * _NF * 2)))
+    return [(n0, min(nb, N - n0)) for n0 in range(0, N, nb)]
+
+
+def _launch_chunks(name, N, h, w, rows_fn, cus, strip, launch, what, lib=None, side=False, planes_in_name=True):
+    """One launch per chunk of `_plane_chunks`: launch(n0, n, rows_per_segment) -> the entry's return code.  Timer `name`, with the plane
+    count when it is not the full 8 (planes_in_name: the roofline leg prices a stage launch by its planes) and `_side` for the launches
+    that share the chip with the guidance trunks; rows_fn(n, h, w, cus=, strip=): SRProjectionModule._rows_per_segment."""
+    for n0, n in _plane_chunks(N, h, w):
+        tok = L.TIMER.start((name if n == 8 or not planes_in_name else f"{name}_p{n}") + ("_side" if side else "")) if L.TIMER.enabled else None
+        L.check(launch(n0, n, rows_fn(n, h, w, cus=cus, strip=strip)), what, lib=lib)
+        L.TIMER.stop(tok)
 
 
 def _planes_per_chunk(N, H, W):
@@ -1216,37 +1241,28 @@ class _FusedStageS2:
         self.slopes_le_one = bool(slopes_le_one)
         self.post_slopes_le_one = self.slopes_le_one and (post is None or float(post[3]) <= 1.0)
         self.rows_fn = rows_fn
+        self.strip = int(L.load().vsr_sr_query(L.Q_UTD_S2_STRIP_WIDTH))
 
     def __call__(self, a, chain, out=None, side=False, post=False):
         """-> out [N,h,w,32] fp16; post=True (has_post): (out, the next group's uptran slice of it)."""
         N, h, w, _ = a.shape
         if out is None:
             out = torch.empty((N, h, w, _NF), dtype=torch.float16, device=a.device)
+        lib = L.load()
         if post:
             assert self.has_post
             out2 = torch.empty((N, h, w, _NF), dtype=torch.float16, device=a.device)
-            nb = max(1, min(N, ((1 << 32) - 32) // (h * w * _NF * 2)))
-            for n0 in range(0, N, nb):
-                n = min(nb, N - n0)
-                tok = L.TIMER.start(("sr_utd_s2_f16" if n == 8 else f"sr_utd_s2_f16_p{n}") + ("_side" if side else ""))
-                rows = self.rows_fn(n, h, w, cus=512, strip=int(L.load().vsr_sr_query(L.Q_UTD_S2_STRIP_WIDTH)))
-                L.check(L.load().vsr_sr_utd_s2_post_f16(L.dptr(a[n0:n0 + n], torch.float16), L.dptr(self.blob, torch.uint8),
-                                                        L.dptr(out[n0:n0 + n], torch.float16), L.dptr(out2[n0:n0 + n], torch.float16), n, h, w, rows,
-                                                        int(self.post_slopes_le_one), L.stream()), "sr_utd_s2_post_f16")
-                L.TIMER.stop(tok)
-            return out, out2
-        nb = max(1, min(N, ((1 << 32) - 32) // (h * w * _NF * 2)))   # planes per launch: the kernel's 32-bit byte offsets
-        for n0 in range(0, N, nb):
-            n = min(nb, N - n0)
-            tok = L.TIMER.start(("sr_utd_s2_f16" if n == 8 else f"sr_utd_s2_f16_p{n}") + ("_side" if side else ""))
-            # k_utd_s2: two workgroups share a CU (256 registers per wave): twice the slots of the x4 kernel per round; k_utd_s2w: one
-            rows = self.rows_fn(n, h, w, cus=256 if self.wide else 512, strip=int(L.load().vsr_sr_query(L.Q_UTD_S2_STRIP_WIDTH)))
-            fn = L.load().vsr_sr_utd_s2w_f16 if self.wide else L.load().vsr_sr_utd_s2_f16
-            L.check(fn(L.dptr(a[n0:n0 + n], torch.float16), L.dptr(self.blob, torch.uint8),
-                                               L.dptr(out[n0:n0 + n], torch.float16), n, h, w, rows, int(self.slopes_le_one), L.stream()),
-                    "sr_utd_s2_f16")
-            L.TIMER.stop(tok)
-        return out
+            launch = lambda n0, n, rows: lib.vsr_sr_utd_s2_post_f16(
+                L.dptr(a[n0:n0 + n], torch.float16), L.dptr(self.blob, torch.uint8), L.dptr(out[n0:n0 + n], torch.float16),
+                L.dptr(out2[n0:n0 + n], torch.float16), n, h, w, rows, int(self.post_slopes_le_one), L.stream())
+        else:
+            fn = lib.vsr_sr_utd_s2w_f16 if self.wide else lib.vsr_sr_utd_s2_f16
+            launch = lambda n0, n, rows: fn(L.dptr(a[n0:n0 + n], torch.float16), L.dptr(self.blob, torch.uint8), L.dptr(out[n0:n0 + n], torch.float16),
+                                            n, h, w, rows, int(self.slopes_le_one), L.stream())
+        # k_utd_s2: two workgroups share a CU (256 registers per wave): twice the slots of the x4 kernel per round; k_utd_s2w: one
+        _launch_chunks("sr_utd_s2_f16", N, h, w, self.rows_fn, 256 if self.wide and not post else 512, self.strip, launch,
+                       "sr_utd_s2_post_f16" if post else "sr_utd_s2_f16", side=side)
+        return (out, out2) if post else out
 
 
 # the x3 stage's waves own phase SETS of equal tap count (csrc/sr_utd_s3.hip): (HR row phase, HR column phase) per wave, in slot order
@@ -1377,6 +1393,7 @@ class _FusedStageS3:
                                      dn[0].weight, dn[0].bias, float(dn[1].weight.detach()))
         self.slopes_le_one = bool(slopes_le_one)
         self.rows_fn = rows_fn
+        self.strip = int(L.load_s3().vsr_s3_query(L.Q_S3_STRIP_WIDTH))
 
     def __call__(self, a, chain, out=None, side=False, post=False):
         """-> out [N,h,w,32] fp16."""
@@ -1385,16 +1402,11 @@ class _FusedStageS3:
         if out is None:
             out = torch.empty((N, h, w, _NF), dtype=torch.float16, device=a.device)
         lib = L.load_s3()
-        nb = max(1, min(N, ((1 << 32) - 32) // (h * w * _NF * 2)))   # planes per launch: the kernel's 32-bit byte offsets
-        for n0 in range(0, N, nb):
-            n = min(nb, N - n0)
-            tok = L.TIMER.start(("sr_utd_s3_f16" if n == 8 else f"sr_utd_s3_f16_p{n}") + ("_side" if side else ""))
-            # k_utd_s3: one wave per SIMD (its weights fill the register file), one workgroup per CU
-            rows = self.rows_fn(n, h, w, cus=256, strip=int(lib.vsr_s3_query(L.Q_S3_STRIP_WIDTH)))
-            L.check(lib.vsr_s3_sr_utd_f16(L.dptr(a[n0:n0 + n], torch.float16), L.dptr(self.blob, torch.uint8),
-                                          L.dptr(out[n0:n0 + n], torch.float16), n, h, w, rows, int(self.slopes_le_one), L.stream()),
-                    "sr_utd_s3_f16", lib=lib)
-            L.TIMER.stop(tok)
+        # k_utd_s3: one wave per SIMD (its weights fill the register file), one workgroup per CU
+        _launch_chunks("sr_utd_s3_f16", N, h, w, self.rows_fn, 256, self.strip,
+                       lambda n0, n, rows: lib.vsr_s3_sr_utd_f16(L.dptr(a[n0:n0 + n], torch.float16), L.dptr(self.blob, torch.uint8),
+                                                                 L.dptr(out[n0:n0 + n], torch.float16), n, h, w, rows, int(self.slopes_le_one), L.stream()),
+                       "sr_utd_s3_f16", lib=lib, side=side)
         return out
 
 
@@ -1437,6 +1449,7 @@ class _FusedStageS3Post:
         self.slopes_le_one = stage.slopes_le_one
         self.post_slopes_le_one = self.slopes_le_one and float(post[3]) <= 1.0
         self.rows_fn = rows_fn
+        self.strip = int(L.load_s3p().vsr_s3p_query(L.Q_S3P_STRIP_WIDTH))
 
     def __call__(self, a, chain, out=None, side=False, post=True):
         """-> (out, the next group's uptran slice of it), both [N,h,w,32] fp16."""
@@ -1446,15 +1459,11 @@ class _FusedStageS3Post:
             out = torch.empty((N, h, w, _NF), dtype=torch.float16, device=a.device)
         out2 = torch.empty((N, h, w, _NF), dtype=torch.float16, device=a.device)
         lib = L.load_s3p()
-        nb = max(1, min(N, ((1 << 32) - 32) // (h * w * _NF * 2)))   # planes per launch: the kernel's 32-bit byte offsets
-        for n0 in range(0, N, nb):
-            n = min(nb, N - n0)
-            tok = L.TIMER.start(("sr_utd_s3_post_f16" if n == 8 else f"sr_utd_s3_post_f16_p{n}") + ("_side" if side else ""))
-            rows = self.rows_fn(n, h, w, cus=256, strip=int(lib.vsr_s3p_query(L.Q_S3P_STRIP_WIDTH)))
-            L.check(lib.vsr_s3p_sr_utd_post_f16(L.dptr(a[n0:n0 + n], torch.float16), L.dptr(self.blob, torch.uint8),
-                                                L.dptr(out[n0:n0 + n], torch.float16), L.dptr(out2[n0:n0 + n], torch.float16), n, h, w, rows,
-                                                int(self.post_slopes_le_one), L.stream()), "sr_utd_s3_post_f16", lib=lib)
-            L.TIMER.stop(tok)
+        _launch_chunks("sr_utd_s3_post_f16", N, h, w, self.rows_fn, 256, self.strip,
+                       lambda n0, n, rows: lib.vsr_s3p_sr_utd_post_f16(L.dptr(a[n0:n0 + n], torch.float16), L.dptr(self.blob, torch.uint8),
+                                                                       L.dptr(out[n0:n0 + n], torch.float16), L.dptr(out2[n0:n0 + n], torch.float16),
+                                                                       n, h, w, rows, int(self.post_slopes_le_one), L.stream()),
+                       "sr_utd_s3_post_f16", lib=lib, side=side)
         return out, out2
 
 
@@ -1504,6 +1513,7 @@ class _FusedStageS3Pre:
         self.slopes_le_one = stage_post.slopes_le_one and pre_le_one             # without POST: its slope is not read
         self.post_slopes_le_one = stage_post.post_slopes_le_one and pre_le_one
         self.rows_fn = rows_fn
+        self.strip = int(L.load_s3f().vsr_s3f_query(L.Q_S3F_STRIP_WIDTH))
 
     def __call__(self, feat, a, b, cmap, out=None, side=False, post=True):
         """feat [N,h,w,32] fp16; a, b: the two live maps of the previous step and cmap [h w, 32] fp32, or all None (step 0)
@@ -1513,17 +1523,13 @@ class _FusedStageS3Pre:
             out = torch.empty((N, h, w, _NF), dtype=torch.float16, device=feat.device)
         out2 = torch.empty((N, h, w, _NF), dtype=torch.float16, device=feat.device) if post else None
         lib = L.load_s3f()
-        nb = max(1, min(N, ((1 << 32) - 32) // (h * w * _NF * 2)))   # planes per launch: the kernel's 32-bit byte offsets
         sl = lambda t, n0, n: None if t is None else t[n0:n0 + n]
-        for n0 in range(0, N, nb):
-            n = min(nb, N - n0)
-            tok = L.TIMER.start(("sr_utd_s3_pre_f16" if n == 8 else f"sr_utd_s3_pre_f16_p{n}") + ("_side" if side else ""))
-            rows = self.rows_fn(n, h, w, cus=256, strip=int(lib.vsr_s3f_query(L.Q_S3F_STRIP_WIDTH)))
-            L.check(lib.vsr_s3f_sr_utd_pre_f16(L.dptr(feat[n0:n0 + n], torch.float16), L.optr(sl(a, n0, n), torch.float16), L.optr(sl(b, n0, n), torch.float16),
-                                               L.optr(cmap), L.dptr(self.blob, torch.uint8), L.dptr(out[n0:n0 + n], torch.float16),
-                                               L.optr(sl(out2, n0, n), torch.float16), n, h, w, rows,
-                                               int(self.post_slopes_le_one if post else self.slopes_le_one), L.stream()), "sr_utd_s3_pre_f16", lib=lib)
-            L.TIMER.stop(tok)
+        _launch_chunks("sr_utd_s3_pre_f16", N, h, w, self.rows_fn, 256, self.strip,
+                       lambda n0, n, rows: lib.vsr_s3f_sr_utd_pre_f16(
+                           L.dptr(feat[n0:n0 + n], torch.float16), L.optr(sl(a, n0, n), torch.float16), L.optr(sl(b, n0, n), torch.float16), L.optr(cmap),
+                           L.dptr(self.blob, torch.uint8), L.dptr(out[n0:n0 + n], torch.float16), L.optr(sl(out2, n0, n), torch.float16), n, h, w, rows,
+                           int(self.post_slopes_le_one if post else self.slopes_le_one), L.stream()),
+                       "sr_utd_s3_pre_f16", lib=lib, side=side)
         return (out, out2) if post else out
 
 
