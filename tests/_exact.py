@@ -11,6 +11,8 @@ This module holds
   * float64 references on stock torch.nn.functional operators, each CHECKING its budget (`conv_ref`, `deconv_ref`, `stage_ref`, and for
     the two ends of the SR net `head_ref`, `chain_ref`, `fold_ref`, `tail_ref`, `bilinear_up_ref`, `fusion_ref`;
     `BudgetError` names the offending coordinate: a case outside its budget is a mistake in the test, never a reason for a tolerance),
+  * float64 references of the train step's GRADIENTS by autograd over the same stock operators (`grads_ref`, `prelu_grads_ref`,
+    `mlp_grads_ref`), every backward sum under the same budget,
   * `assert_exact` / `diff_mask` / `bbox`, which report the number of differing elements, the first one and their bounding box.
 
 The sign of a zero is not compared (`-0.0 == +0.0`): `0 * negative` in a PReLU with slope 0 is -0.0 in one formulation and +0.0 in
@@ -337,6 +339,66 @@ def fusion_ref(raw, x, sub, add, fc, S, decimate=False, live=True):
     Choose the MeanShift values dyadic (mean (0.5, 0.25, 0.375), std 1: 255 * mean is a multiple of 1/8) and the MLP's weights small
     integers or eighths, so that every float32 product and sum is exact in any order."""
     return mlp_ref(planes_ref(raw, x, sub, add, S, decimate), fc, live=live)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the train step's gradients
+def grads_ref(fn, operands, gy, what="operator"):
+    """Forward and every gradient of a multilinear stock operator in float64.  `fn`: a closure over F.conv2d / F.conv_transpose2d taking
+    the operands (float64 tensors, e.g. x, w, b) in order; `gy`: the incoming gradient.  -> (y, [gradient per operand]).
+    The same `fn` on |operands| with |gy| gives, for such an operator, exactly the sum of |terms| of every forward and backward sum; each
+    is held below 2^24 of the product of all granularities (a multiple of which every term of every sum is), so float32 evaluates all of
+    them without rounding in any order."""
+    _threads()
+    gran = granularity(gy)
+    for t in operands:
+        gran *= granularity(t)
+
+    def run(ops, g):
+        leaves = [t.detach().clone().requires_grad_() for t in ops]
+        y = fn(*leaves)
+        return y.detach(), [t.detach() for t in torch.autograd.grad(y, leaves, g)]
+
+    y, grads = run(operands, gy)
+    ya, ga = run([t.abs() for t in operands], gy.abs())
+    check_sum_budget(ya, gran, f"{what} forward")
+    for i, a in enumerate(ga):
+        check_sum_budget(a, gran, f"{what} gradient of operand {i}")
+    return y, grads
+
+
+def prelu_grads_ref(v, g, slope, what="PReLU backward"):
+    """gv = g where v > 0, else g * slope; dslope = sum g * min(v, 0): ATen's conventions (v == 0 is on the slope side).
+    -> (gv, dslope [1]), float64.  sum |g||v| below 2^24 granularities: the slope gradient is exact in any order; gv a float32 value."""
+    _slope_ok(slope, dtype=torch.float32)
+    gv = check_storable(torch.where(v > 0, g, g * float(slope)), torch.float32, f"{what}: input gradient")
+    check_sum_budget((g.abs() * v.abs()).sum().reshape(1), granularity(g) * granularity(v), f"{what}: slope gradient")
+    return gv, (g * v.clamp(max=0.0)).sum().reshape(1)
+
+
+def mlp_grads_ref(planes, fc, go, live=True):
+    """Gradients of `mlp_ref`'s formulation relu(w2 . relu(W1 v + b1) + b2) by float64 autograd (a ReLU passes nothing at 0).  planes
+    [n,3,H,W], fc = (w1 [hidden, n], b1, w2 [hidden], b2 [1]), go [1,3,H,W] -> dv [n,3,H,W], dW1 [hidden, n], db1, dw2 [hidden], db2 [1].
+    The forward budget is `mlp_ref`'s; each of the five backward sums is held below 2^24 granularities by its absolute-value counterpart."""
+    mlp_ref(planes, fc, live=live)
+    leaves = [t.detach().clone().requires_grad_() for t in (planes,) + tuple(fc)]
+    v, w1, b1, w2, b2 = leaves
+    hs = torch.einsum("jn,ncyx->jcyx", w1, v) + b1.view(-1, 1, 1, 1)
+    hid = F.relu(hs)
+    out = F.relu(torch.einsum("j,jcyx->cyx", w2, hid) + b2.view(1, 1, 1)).unsqueeze(0)
+    grads = [t.detach() for t in torch.autograd.grad(out, leaves, go)]
+    with torch.no_grad():
+        w1a, w2a, va = fc[0].abs(), fc[2].abs(), planes.abs()
+        ago = go[0].abs() * (out[0] > 0)                                     # |go| behind the output gate [3,H,W]
+        agh = ago.unsqueeze(0) * w2a.view(-1, 1, 1, 1) * (hs > 0)            # |gh| [hidden,3,H,W]
+        g_go, g_gh = granularity(go), granularity(go) * granularity(fc[2])
+        g_hid = min(granularity(fc[0]) * granularity(planes), granularity(fc[1]))
+        check_storable(agh, torch.float32, "fusion MLP hidden gradient")
+        check_sum_budget(torch.einsum("jcyx,jn->ncyx", agh, w1a), g_gh * granularity(fc[0]), "fusion MLP dv")
+        check_sum_budget(torch.einsum("jcyx,ncyx->jn", agh, va), g_gh * granularity(planes), "fusion MLP dW1")
+        check_sum_budget(agh.sum((1, 2, 3)), g_gh, "fusion MLP db1")
+        check_sum_budget(torch.einsum("cyx,jcyx->j", ago, hid.detach()), g_go * g_hid, "fusion MLP dw2")
+        check_sum_budget(ago.sum().reshape(1), g_go, "fusion MLP db2")
+    return grads
 
 
 # ---------------------------------------------------------------------------------------------------------------- comparison

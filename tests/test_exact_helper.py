@@ -442,3 +442,123 @@ def test_fusion_ref_budget_checks_fire():
         E.fusion_ref(**dict(c, raw=c["raw"] + 2.0 ** -20 + 2.0 ** 10))
     with pytest.raises(E.BudgetError, match="non-zero|one sign|distinct"):
         E.fusion_ref(**dict(c, fc=(w1 * 0.0, b1 * 0.0 - 1.0, w2, b2)))          # a dead hidden layer
+
+
+# ------------------------------------------------------------------------------------------------ the train step's gradient references
+def _f32_autograd(fn, operands, gy):
+    leaves = [t.to(torch.float32).requires_grad_() for t in operands]
+    y = fn(*leaves)
+    return y.detach(), [g.detach() for g in torch.autograd.grad(y, leaves, gy.to(torch.float32))]
+
+
+@pytest.mark.parametrize("case", [("conv", 2, 5, 6, 70, 7, 3, 1, 1), ("conv", 2, 6, 21, 30, 4, 8, 4, 2), ("conv", 1, 9, 5, 7, 3, 1, 1, 0),
+                                  ("deconv", 2, 4, 3, 9, 5, 8, 4, 2), ("deconv", 1, 5, 6, 7, 3, 7, 3, 2), ("deconv", 2, 3, 5, 8, 4, 6, 2, 2)])
+def test_grads_ref_equals_float32_stock_autograd(case):
+    """Inside the budget the float32 CPU operator and its autograd equal the float64 evaluation bit for bit: forward, dX, dW, db."""
+    F = torch.nn.functional
+    kind, N, cin, H, W, cout, K, s, p = case
+    rs = np.random.RandomState(cin * 100 + K)
+    x, b = E.ints(rs, (N, cin, H, W), -3, 3), E.ints(rs, (cout,), -4, 4)
+    if kind == "conv":
+        w = E.ints(rs, (cout, cin, K, K), -2, 2)
+        fn = lambda x, w, b: F.conv2d(x, w, b, stride=s, padding=p)             # noqa: E731
+    else:
+        w = E.ints(rs, (cin, cout, K, K), -2, 2)
+        fn = lambda x, w, b: F.conv_transpose2d(x, w, b, stride=s, padding=p)   # noqa: E731
+    gy = E.ints(rs, tuple(fn(x, w, b).shape), -3, 3)
+    y, grads = E.grads_ref(fn, (x, w, b), gy, kind)
+    y32, g32 = _f32_autograd(fn, (x, w, b), gy)
+    assert y32.dtype == torch.float32 and torch.equal(y32.double(), y)
+    for a, r in zip(g32, grads):
+        assert a.shape == r.shape and torch.equal(a.double(), r)
+    assert torch.equal(y, (E.conv_ref if kind == "conv" else E.deconv_ref)(x, w, b, stride=s, padding=p))
+    y2, g2 = E.grads_ref(lambda x, w: fn(x, w, None), (x, w), gy, kind)          # without a bias: two operands
+    assert len(g2) == 2 and torch.equal(g2[0], grads[0]) and torch.equal(g2[1], grads[1])
+
+
+def test_grads_ref_budget_checks_fire_with_coordinate():
+    F = torch.nn.functional
+    fn = lambda x, w: F.conv2d(x, w)                                            # noqa: E731
+    x = torch.full((1, 4, 3, 3), 1024.0, dtype=torch.float64)
+    w = torch.zeros((2, 4, 1, 1), dtype=torch.float64)
+    gy = torch.ones((1, 2, 3, 3), dtype=torch.float64)
+    w[1] = 4096.0                                     # forward: 4 x 1024 x 4096 = 2^24 at out-channel 1
+    with pytest.raises(E.BudgetError, match=r"forward.*\(0, 1, 0, 0\)"):
+        E.grads_ref(fn, (x, w), gy)
+    w[1] = 1024.0
+    E.grads_ref(fn, (x, w), gy)                       # forward 2^22, dX 2^10, dW 9 x 1024: inside
+    gy[0, 1, 2, 2] = 2.0 ** 14                        # dX = gy w: 2^24 at that pixel only; forward untouched
+    with pytest.raises(E.BudgetError, match=r"gradient of operand 0.*\(0, 0, 2, 2\)"):
+        E.grads_ref(fn, (x, w), gy)
+    gy[0, 1, 2, 2] = 2.0 ** 13
+    gy[0, 0] = 2.0 ** 11                              # dW[0] = sum of 9 pixels x 1024 x 2^11 > 2^24; dX = 2^11 x 0 + ... inside
+    with pytest.raises(E.BudgetError, match=r"gradient of operand 1.*\(0, 0, 0, 0\)"):
+        E.grads_ref(fn, (x, w), gy)
+    with pytest.raises(E.BudgetError):                # a granularity of 1/4 in one operand shrinks every budget with it
+        E.grads_ref(fn, (x + 0.25, w * 4), torch.ones_like(gy))
+
+
+def test_prelu_grads_ref_equals_float32_stock_autograd_and_its_convention_at_zero():
+    F = torch.nn.functional
+    rs = np.random.RandomState(5)
+    v, g = E.ints(rs, (3, 4, 9, 11), -3, 3), E.ints(rs, (3, 4, 9, 11), -3, 3)
+    g[g == 0] = 1.0
+    assert int((v == 0).sum()) > 50
+    for slope in E.SLOPES_LE_ONE + E.SLOPES_SELECT:
+        gv, da = E.prelu_grads_ref(v, g, slope)
+        v32 = v.float().requires_grad_()
+        a32 = torch.tensor([slope], dtype=torch.float32, requires_grad=True)
+        y32 = F.prelu(v32, a32)
+        y32.backward(g.float())
+        assert torch.equal(y32.detach().double(), E.prelu_ref(v, slope))
+        assert torch.equal(v32.grad.double(), gv) and torch.equal(a32.grad.double(), da)
+        assert torch.equal(gv[v == 0], g[v == 0] * slope)                  # the slope side at v == 0
+    gv, da = E.prelu_grads_ref(torch.tensor([0.0, 2.0, -2.0], dtype=torch.float64), torch.tensor([3.0, 3.0, 3.0], dtype=torch.float64), 0.25)
+    assert gv.tolist() == [0.75, 3.0, 0.75] and da.tolist() == [-6.0]
+
+
+def test_prelu_grads_ref_budget_checks_fire():
+    v = torch.full((4096,), -64.0, dtype=torch.float64)
+    g = torch.full((4096,), 64.0, dtype=torch.float64)
+    with pytest.raises(E.BudgetError, match="slope gradient"):             # 4096 x 64 x 64 = 2^24
+        E.prelu_grads_ref(v, g, 0.5)
+    E.prelu_grads_ref(v[:2048], g[:2048], 0.5)
+    with pytest.raises(E.BudgetError, match="input gradient"):             # (2^24 + 2) * 0.75 needs 25 bits
+        E.prelu_grads_ref(torch.tensor([-1.0], dtype=torch.float64), torch.tensor([2.0 ** 24 + 2.0], dtype=torch.float64), 0.75)
+    with pytest.raises(E.BudgetError, match="slope"):
+        E.prelu_grads_ref(v[:8], g[:8], 0.1)
+
+
+def _mlp_case(seed, n=8, hidden=32, shape=(3, 7)):
+    rs = np.random.RandomState(seed)
+    planes = E.ints(rs, (n, 3) + shape, -24, 24, step=0.125)
+    w1 = E.sparse_weights(rs, (hidden, n), 0.7, 2)
+    w2 = torch.from_numpy(rs.randint(1, 5, size=hidden) * 0.5 * np.where(np.arange(hidden) % 2 == 0, 1.0, -1.0))
+    return planes, (w1, E.ints(rs, (hidden,), -2, 2), w2, E.ints(rs, (1,), 0, 2)), E.ints(rs, (1, 3) + shape, -3, 3)
+
+
+@pytest.mark.parametrize("n,hidden", [(8, 32), (1, 5), (16, 32), (3, 7)])
+def test_mlp_grads_ref_equals_float32_stock_autograd(n, hidden):
+    F = torch.nn.functional
+    planes, fc, go = _mlp_case(n, n, hidden)
+    grads = E.mlp_grads_ref(planes, fc, go, live=False)
+    h, w1, b1, w2, b2 = (t.float().requires_grad_() for t in (planes,) + fc)
+    y = F.relu(F.linear(F.relu(F.linear(h.permute(1, 2, 3, 0), w1, b1)), w2.view(1, -1), b2)).permute(3, 0, 1, 2)
+    assert torch.equal(y.detach().double(), E.mlp_ref(planes, fc, live=False))
+    y.backward(go.float())
+    for a, r in zip((h, w1, b1, w2, b2), grads):
+        assert a.grad.shape == r.shape and torch.equal(a.grad.double(), r)
+    assert all(bool(g.any()) for g in grads[:4])                                # (db2, one sum of signed integers, may well be 0)
+
+
+def test_mlp_grads_ref_budget_checks_fire():
+    planes, fc, go = _mlp_case(0)
+    w1, b1, w2, b2 = fc
+    E.mlp_grads_ref(planes, fc, go, live=False)
+    with pytest.raises(E.BudgetError, match="layer 1"):
+        E.mlp_grads_ref(planes, (w1 * 2.0 ** 20 + 1.0, b1, w2, b2), go, live=False)
+    with pytest.raises(E.BudgetError, match="dW1|db1|dv|hidden gradient"):     # forward inside, the gradient 2^22 times larger
+        E.mlp_grads_ref(planes, fc, go * 2.0 ** 22 + 1.0, live=False)
+    big = torch.full_like(go, 2.0 ** 19) + 1.0                                  # 63 pixels x 2^19 > 2^24: the sum over pixels alone
+    with pytest.raises(E.BudgetError, match="fusion MLP d"):
+        E.mlp_grads_ref(planes, (w1, b1, w2, b2 + 500.0), big, live=False)

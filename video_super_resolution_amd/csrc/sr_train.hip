@@ -333,7 +333,7 @@ int vsr_train_prelu_f32(const float* v, const float* slope, float* y, size_t n, 
 
 size_t vsr_train_prelu_bwd_ws_floats(size_t n) { return (n + (size_t)kB * 16 - 1) / ((size_t)kB * 16); }
 
-/* gv = g * (v >= 0 ? 1 : slope); dslope[0] = sum g * min(v, 0) */
+/* gv = g * (v > 0 ? 1 : slope); dslope[0] = sum g * min(v, 0) */
 int vsr_train_prelu_bwd_f32(const float* v, const float* g, const float* slope, float* gv, float* dslope, float* ws, size_t n, vsr_stream_t stream) {
     VSR_REQUIRE(v && g && slope && gv && dslope && ws && n > 0, "train_prelu_bwd: bad arguments");
     const size_t blocks = vsr_train_prelu_bwd_ws_floats(n);
