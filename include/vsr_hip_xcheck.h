@@ -28,8 +28,22 @@ extern "C" {
  * split count; 6000 + m k_conv_patch_lw 0 never, 1 heuristic (default), 2 wherever a build exists; 7000 + m k_conv1x1_t 0 never
  * (default), 1 where legal; 8000 + m the gather kernel's five-set ring 0 never (default), 1 launches of at most one workgroup
  * per CU, 2 always; 9000 + m k_conv_patch_pf 0 never, 1 heuristic (default), 2 / 3 wherever a build exists (64 / at most 32
- * out-channels per workgroup).  Returns the previous mode. */
+ * out-channels per workgroup).  Returns the previous mode.  What each mode below 1000 switches: the table at `decode_patch_mode`
+ * (csrc/conv_igemm.hip), the one place the code is decoded. */
 int vsr_conv2d_tuning(int patch_mode);
+
+/* The route the convolution launchers WOULD take for a layer, without a launch, a HIP call or a pointer: the argument checks of
+ * the entry (kind 0 vsr_conv2d_nhwc_sx_f16, 1 vsr_conv2d_stem_f16, 2 vsr_deconv4s2_nhwc_f16) that read no pointer, then the entry's
+ * plan function, under the current vsr_conv2d_tuning switches and vsr_conv2d_route_batch.  The route string goes to
+ * vsr_last_route(); returns VSR_OK or the entry's argument error (text in vsr_last_error()).  It answers for ONE launch: a batch
+ * whose input exceeds 4 GiB runs as sub-batches of whole images, each planned like this with its own N.
+ * Of the entries' arguments the list leaves out the pointers, the stream and what no decision reads: in_coff (taken as 0), act,
+ * slope.  The output window (outH .. ox_off) is in it because the streaming 1x1 requires a dense destination.  Ignored for kind 1:
+ * in_ld, cin, stride_x and the output window (the stem's are 4, 32, stride, dense); for kind 2: Ho, Wo, kh, kw, stride, stride_x,
+ * pad_y, pad_x and the output window (2 x 2 taps per phase onto 2H x 2W).  has_ws / ws_bytes: the split-K workspace. */
+int vsr_conv2d_plan(int kind, int in_ld, int N, int H, int W, int cin, int Ho, int Wo, int cout, int cout_pad, int kh, int kw, int stride,
+                    int stride_x, int pad_y, int pad_x, int out_ld, int out_coff, int outH, int outW, int oy_mul, int oy_off, int ox_mul,
+                    int ox_off, int has_ws, size_t ws_bytes);
 
 /* vsr_flownet_up_warp_concat16_f16: 1 (default) thread-per-pixel gathers, 0 the LDS-staged tile + DPP neighbour hand-over
  * (1.0 - 1.9 x slower; bit-identical). */

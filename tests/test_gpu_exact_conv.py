@@ -391,6 +391,97 @@ def test_pool_and_layout_conversions_equal_float64(shape, mode):
     E.assert_exact(E.nchw64(got), ref, f"pool2x2 mode {mode}")
 
 
+# ---------------------------------------------------------------------------------------------------------------- the route plan
+def _plan(kind, conv, N, H, W, in_ld, out_ld, out_coff=0, out_hw=None, stride_x=0):
+    """The route vsr_conv2d_plan names for the launch `conv` (an HConv, an HConvStem or phase 0 of an HDeconv4s2) is about to make."""
+    from test_conv_route_plan import plan_route
+    if kind == 1:
+        Ho, Wo = (H + 2 * conv.pad - conv.kh) // conv.stride + 1, (W + 2 * conv.pad - conv.kw) // conv.stride + 1
+        args = (4, N, H, W, 32, Ho, Wo, conv.cout, conv.cout_pad, conv.kh, conv.kw, conv.stride, 0, conv.pad, conv.pad, out_ld, out_coff, Ho, Wo, 1, 0, 1, 0)
+    else:
+        Ho, Wo = out_hw or conv.out_hw(H, W)
+        args = (in_ld, N, H, W, conv.cin_pad, Ho, Wo, conv.cout, conv.cout_pad, conv.kh, conv.kw, conv.stride, stride_x, conv.pad_y, conv.pad_x, out_ld, out_coff,
+                Ho * conv.oy[0], Wo * conv.ox[0], conv.oy[0], conv.oy[1], conv.ox[0], conv.ox[1])
+    return plan_route(L.load(), kind, args, 1, igemm._WS_BYTES)
+
+
+PLAN_CONV = ([(SHAPES[i], m) for i, m in ((3, ()), (4, ()), (7, ()), (12, ()), (13, ()), (14, ()), (12, (2000, 11)), (13, (2000, 10)), (9, (8,)), (12, (2000, 11, 1300)))]
+             + [(TILE_SHAPES[i], m) for i, m in ((0, (2003,)), (4, (2003, 4128, 5003)), (9, (2003, 4064, 5001)))]
+             + [(PATCH_SHAPES[i] + (1, PATCH_SHAPES[i][5] // 2), PATCH_ROUTES[r][0]) for i, r in ((0, "patch_r8"), (6, "patch_lw"), (8, "patch_lw"), (7, "patch_pf64"),
+                                                                                                (3, "patch_pf32"), (4, "patch_rows"), (1, "patch_rows"), (5, "patch"), (10, "patch_r8"))]
+             + [((2, 64, 128, 240, 16, 3, 1, 1), ()), ((2, 32, 128, 240, 64, 3, 1, 1), ()),      # the smallest map with the patch family by heuristic: H * W >= 8192
+                ((1, 128, 259, 271, 208, 1, 1, 0), ()), ((1, 128, 259, 271, 208, 1, 1, 0), (7001,))])
+
+
+@pytest.mark.xcheck
+@pytest.mark.parametrize("i", range(len(PLAN_CONV)))
+def test_plan_names_the_route_the_convolution_takes(i):
+    """vsr_conv2d_plan (no launch) and vsr_last_route() after the launch of the same layer, under the same switches: one string; the
+    launch equals float64."""
+    shape, modes = PLAN_CONV[i]
+    c = make_conv(600 + i, *shape, act=ACTS[i % 4][0], slope=ACTS[i % 4][1])
+    conv = igemm.HConv(c["w"].float().cuda(), c["b"].float().cuda(), stride=c["stride"], pad=c["pad"], act=c["act"], slope=c["slope"])
+    N, cin, H, W = c["x"].shape
+    with _switches(*modes):
+        planned = _plan(0, conv, N, H, W, igemm.pad32(cin), igemm.pad32(c["cout"]))
+        got, r = run_hconv(c, conv=conv)
+    assert planned == r, (planned, r)
+    check_nhwc(got, c, f"{shape} {r}")
+
+
+@pytest.mark.xcheck
+def test_plan_routes_cover_split_k_and_every_family():
+    """The case list itself: the plan of PLAN_CONV's layers under their switches (no launch here; that each launch takes the planned route is
+    the test above) names gather with and without split-K, the tile kernel with and without, each patch build and both 1x1 builds."""
+    seen = set()
+    for shape, modes in PLAN_CONV:
+        N, cin, H, W, cout, k, stride, pad = shape
+        conv = igemm.HConv(torch.zeros(cout, cin, k, k), None, stride=stride, pad=pad)   # (host tensors: only its geometry is read)
+        with _switches(*modes):
+            seen.add(re.sub(r"<.*?>|(?<=splitk)\d+", "", _plan(0, conv, N, H, W, igemm.pad32(cin), igemm.pad32(cout))))
+    assert seen >= {"gather", "gather+splitk", "tile", "tile+splitk", "patch_pf", "patch_lw", "patch_r8", "patch_rows", "patch", "conv1x1_stream", "conv1x1_t"}, seen
+
+
+@pytest.mark.xcheck
+@pytest.mark.parametrize("case", [(2, 3, 13, 17, 128, 7, 1, 3), (2, 3, 20, 30, 64, 7, 2, 3), (1, 3, 270, 250, 128, 7, 1, 3)])
+def test_plan_names_the_route_the_stem_takes(case):
+    N, cin, H, W, cout, k, s, p = case
+    c = make_conv(cout + k, N, cin, H, W, cout, k, s, p, act=RELU, mag_x=8)
+    stem = igemm.HConvStem(c["w"].float().cuda(), c["b"].float().cuda(), stride=s, pad=p, act=RELU)
+    planned = _plan(1, stem, N, H, W, 4, igemm.pad32(cout))
+    got = stem(E.nhwc(c["x"], torch.float16, 4).cuda())
+    assert planned == _route() and planned == ("stem7_rows" if H * W * N >= 65536 else f"gather<{min(64, igemm._cout_pad(cout))},stem>"), (planned, _route())
+    check_nhwc(got, c, f"stem {case} {planned}")
+
+
+@pytest.mark.xcheck
+@pytest.mark.parametrize("shape,modes", [((1, 64, 7, 9, 32), ()), ((2, 1026, 4, 5, 129), ()), ((2, 1026, 4, 5, 129), (1,)), ((2, 96, 11, 13, 192), (2003,)), ((1, 32, 97, 130, 2), ())])
+def test_plan_names_the_route_the_transposed_convolution_takes(shape, modes):
+    N, cin, H, W, cout = shape
+    c = make_conv(cin + cout, N, cin, H, W, cout, 4, 2, 1, act=LEAKY, slope=0.1, transposed=True)
+    dc = igemm.HDeconv4s2(c["w"].float().cuda(), c["b"].float().cuda(), act=LEAKY, slope=0.1)
+    xs = E.nhwc(c["x"], torch.float16, igemm.pad32(cin)).cuda()
+    with _switches(*modes):
+        planned = _plan(2, dc.phases[0], N, H, W, igemm.pad32(cin), igemm.pad32(cout))
+        got = dc(xs)
+        torch.cuda.synchronize()
+        r = _route()
+    assert planned == r and r.startswith("deconv4s2"), (planned, r)
+    check_nhwc(got, c, f"deconv4s2 {shape} {r}")
+
+
+@pytest.mark.xcheck
+def test_plan_names_the_route_the_pair_convolution_takes():
+    N, cin, H, W, cout, k, pad = 2, 12, 16, 24, 64, 7, 3
+    c = make_conv(cin + k + W, N, cin, H, W, cout, k, 2, pad, act=LEAKY, slope=0.1)
+    conv = igemm.HConvPairS2(c["w"].float().cuda(), c["b"].float().cuda(), pad=pad, act=LEAKY, slope=0.1)
+    planned = _plan(0, conv.inner, N, H, W // 2, 32, igemm.pad32(cout), out_hw=((H + 2 * pad - k) // 2 + 1, (W + 2 * pad - k) // 2 + 1), stride_x=1)
+    got = conv(E.nhwc(c["x"], torch.float16, 16).cuda())
+    r = _route()
+    assert planned == r, (planned, r)
+    check_nhwc(got, c, f"pair {r}")
+
+
 # ---------------------------------------------------------------------------------------------------------------- the FlowNetC cost volume
 def _corr_ref(a, b):
     """[B,C,H,W] float64 -> [B,441,H,W]: sum_c a(y, x) b(y + 2 dy, x + 2 dx) / C for dy, dx in -10..10 (zero outside), dy major."""

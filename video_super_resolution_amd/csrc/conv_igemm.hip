@@ -1130,32 +1130,6 @@ __global__ void __launch_bounds__(256, 2) k_conv_patch_lw(const ConvP p) {
                              [&](int r, int li) { return r < rows_ok && li < cols_ok ? wbase + r * rstride + li * cstride : -1ll; });
 }
 
-template <int KH, int MT>
-static void launch_patch_lw(const ConvP& p, int N, hipStream_t stream) {
-    const int lds_patch = (P8_H + KH - 1) * (P8_W + KH - 1) * 64 + KH * KH * 16 * MT * 64, lds_out = 4 * P8_R * 16 * 32 * MT;
-    const int lds = lds_patch > lds_out ? lds_patch : lds_out;
-    static unsigned long long raised = 0;
-    if (lds > 64 * 1024 && !vsr::device_marked(raised)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_patch_lw<KH, MT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        vsr::mark_device(raised);
-    }
-    const unsigned tiles = vsr::cdiv(p.Ho, P8_H) * vsr::cdiv(p.Wo, P8_W);
-    hipLaunchKernelGGL((k_conv_patch_lw<KH, MT>), dim3(tiles, N, p.cout_pad / (16 * MT)), dim3(256), lds, stream, p);
-}
-
-template <int KH, int MT>
-static void launch_patch_r8(const ConvP& p, int N, hipStream_t stream) {
-    const int lds_patch = (P8_H + KH - 1) * (P8_W + p.kw - 1) * 64, lds_out = 4 * P8_R * 16 * 32 * MT;
-    const int lds = lds_patch > lds_out ? lds_patch : lds_out;
-    static unsigned long long raised = 0;   // (per instantiation; one bit per device: the attribute is per device)
-    if (lds > 64 * 1024 && !vsr::device_marked(raised)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_patch_r8<KH, MT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        vsr::mark_device(raised);
-    }
-    const unsigned tiles = vsr::cdiv(p.Ho, P8_H) * vsr::cdiv(p.Wo, P8_W);
-    hipLaunchKernelGGL((k_conv_patch_r8<KH, MT>), dim3(tiles, N, p.cout_pad / (16 * MT)), dim3(256), lds, stream, p);
-}
-
 // The hourglass stem (7x7, 3 -> 128, stride 1, at full resolution): 531 MB of output per 4-frame batch against 0.12
 // TFLOP, i.e. a store-bound layer; through k_conv_igemm<.., STEM> it ran at 0.62 ms, gather-bound (49 x 8-byte pieces per
 // output pixel).  Here a persistent workgroup keeps ALL its weights in registers (wave w: out-channels 32w..32w+31, 7
@@ -1579,14 +1553,61 @@ VSR_TUNABLE g_tile_mode = 1;   // conv_tile.hip (two-operand LDS-DMA tile): 0 ne
 VSR_TUNABLE g_lw_mode = 1;     // k_conv_patch_lw (weight block in LDS): 0 never, 1 heuristic, 2 wherever a build exists (vsr_conv2d_tuning(6000 + n))
 VSR_TUNABLE g_tile_bn = 0, g_tile_splits = 0;   // experiments: force the tile width (64 / 128) / the split count (vsr_conv2d_tuning(4000 + bn), (5000 + n)); 0 = heuristic
 VSR_TUNABLE g_pf_mode = 1;     // k_conv_patch_pf (persistent, prefetching; conv_patch_pf.hip): 0 never, 1 heuristic, 2 wherever a build exists (64 out-channels per workgroup where the count allows), 3 as 2 with at most 32 per workgroup (vsr_conv2d_tuning(9000 + n))
-VSR_TUNABLE g_patch_mode = 0;  // 0: heuristic, 1: never use the LDS-patch kernel, 2: whenever legal, 3: heuristic without the row-reuse builds, 5: heuristic without k_conv_patch_r8, 6 / 7: as 2 without r8 / without r8 and rows, 8: gather layers through the first build k_conv_igemm, 10 / 11: 128-channel gather tiles always / never (tuning hook)
+// The kernel-selection mode (vsr_conv2d_tuning(n), n < 1000) is decoded HERE, once, into the names the plan functions read:
+//   code | no_patch force_patch no_r8 no_rows first_gather wide_always wide_never | meaning
+//      0 |    .         .         .      .         .            .          .      | the heuristics (default; the only row of libvsr_hip.so)
+//      1 |    x         .         .      .         .            .          .      | never an LDS-patch kernel, the tile kernel, the streaming 1x1, stem7_rows
+//      2 |    .         x         .      .         .            .          .      | the patch kernels whenever legal
+//      3 |    .         .         x      x         .            .          .      | heuristic without the row-reuse builds (r8 -- and pf / lw, which sit behind it -- and rows)
+//      5 |    .         .         x      .         .            .          .      | heuristic without k_conv_patch_r8 (pf / lw with it)
+//      6 |    .         x         x      .         .            .          .      | as 2 without r8
+//      7 |    .         x         x      x         .            .          .      | as 2 without r8 and rows
+//      8 |    .         .         .      .         x            .          .      | gather layers through the first build k_conv_igemm; no tile kernel, no deconv patch, no 128-wide tile
+//     10 |    .         .         .      .         .            x          .      | 128-channel gather tiles always
+//     11 |    .         .         .      .         .            .          x      | 128-channel gather tiles never
+struct PatchSw {
+    bool no_patch, force_patch, no_r8, no_rows, first_gather, wide_always, wide_never;
+};
+constexpr PatchSw decode_patch_mode(int m) {
+    return PatchSw{m == 1, m == 2 || m == 6 || m == 7, m == 3 || m == 5 || m == 6 || m == 7, m == 3 || m == 7, m == 8, m == 10, m == 11};
+}
+#if VSR_X
+static int g_patch_mode = 0;   // the code as set (what vsr_conv2d_tuning returns as the previous mode)
+static PatchSw g_sw = decode_patch_mode(0);
+#else
+static constexpr PatchSw g_sw = decode_patch_mode(0);
+#endif
 
 // byte range a gather kernel's buffer resource and its 32-bit offsets cover (0xFFFFFFFF marks "outside the image")
 static constexpr unsigned long long kGatherLimit = 0xFFFFFFFFull;
 
-// The tile kernel (conv_tile.hip) for a layer the launchers prepared in `p` (everything but splits / ws): picks the tile width,
-// splits K when the launch cannot fill two workgroups per CU, launches it and the split-K finish.  nph = 4: the four phases of a
-// k4 s2 transposed convolution in one launch.
+// ---- the route of one launch: decided by plan_conv / plan_stem / plan_deconv (pure: no HIP call, no pointer read, no state beyond the
+// tunables above), named by route_name, launched by launch_route.  Decisions count by Mr / gxr (the route batch Nr); launches use M / gx.
+enum class Kind { gather, gather_stem, tile, deconv4s2_patch, stem7_rows, patch_pf, patch_lw, patch_r8, patch, patch_rows, conv1x1_stream, conv1x1_t };
+struct ConvRoute {
+    Kind kind;
+    int bn;       // gather / tile: out-channels per workgroup
+    int mt;       // patch family: 16-channel tiles per workgroup
+    int splits;   // split-K factor (gather / tile; 1 elsewhere)
+    bool first_build;   // gather through k_conv_igemm (cross-check library)
+};
+
+// kernel sizes with a row-reuse build (k_conv_patch_r8 / k_conv_patch_rows): their slot in the kernel tables, -1: none
+static int kh_slot(int kh) { return kh == 3 ? 0 : kh == 5 ? 1 : kh == 7 ? 2 : kh == 11 ? 3 : -1; }
+#if VSR_X   // k_conv1x1_t's LDS: weights + bias + two slots per wave
+static size_t c1t_lds(const ConvP& p) { return (size_t)(p.cin >> 5) * p.cout_pad * 64 + (size_t)p.cout_pad * 4 + (size_t)4 * 2 * C1T_SLOT; }
+#endif
+
+// The tail every split-K rule ends with: at least 4 K steps per split, at most 32 splits, none without a workspace, partial sums
+// [splits][nph][max(M, Mr)][cout_pad] fp32 inside the workspace.
+static int clamp_splits(int splits, int nk_all, int nph, long long M, long long Mr, int cout_pad, bool has_ws, size_t ws_bytes) {
+    if (splits > nk_all / 4) splits = nk_all / 4;
+    if (splits > 32) splits = 32;
+    if (!has_ws) splits = 1;
+    while (splits > 1 && (size_t)splits * nph * (M > Mr ? M : Mr) * cout_pad * sizeof(float) > ws_bytes) --splits;
+    return splits < 1 ? 1 : splits;
+}
+
 // Where the tile kernel (conv_tile.hip) replaces the gather kernel -- from per-layer device times INSIDE the three trunks at the
 // benchmark size, both kernels on the same layers in one process (tools/trunk_layers.sh; profiles/r03_tile_vs_gather_layers.txt):
 //   * 128-channel tiles with >= 384 workgroups (two per CU cover each other's DMA waits), no split-K: FlowNet's 5x5 / 3x3
@@ -1598,7 +1619,7 @@ static constexpr unsigned long long kGatherLimit = 0xFFFFFFFFull;
 //     32 KB through LDS per 2.1 MFLOP step and measures ~55 GB/s per CU of L2 -> LDS fill, 3/4 of what LDS-DMA gathers reach
 //     on this chip: it is fill-bound, and narrower tiles only lower its FLOP per byte), the LDS-patch kernels keep the
 //     stride-1 k x k layers (they stage the input once per 32-channel chunk for all k x k taps).
-// -> 0: not the tile kernel; 64 / 128: tile width, *splits set.
+// -> 0: not the tile kernel; 64 / 128: tile width, *splits set.  nph = 4: the four phases of a k4 s2 transposed convolution in one launch.
 static int tile_choice(const ConvP& p, long long M, int nk_all, int nph, int* splits) {
     *splits = 1;
     const long long gx = vsr::cdiv(M, BM);
@@ -1611,6 +1632,20 @@ static int tile_choice(const ConvP& p, long long M, int nk_all, int nph, int* sp
         return 128;
     }
     return 0;
+}
+
+// The tile kernel's route from tile_choice's answer (bn, splits): bn = 0 is a layer the heuristic leaves to the other kernels
+// (mode 3 / experiments), which gets the widest tile and splits towards 320 workgroups below 200.
+static ConvRoute plan_tile(const ConvP& p, long long M, long long Mr, int nk_all, int nph, int bn, int splits, bool has_ws, size_t ws_bytes) {
+    const bool can128 = (p.cout_pad & 127) == 0;
+    if (bn == 0) {
+        const long long nwg = vsr::cdiv(Mr, BM) * (long long)(p.cout_pad / (can128 ? 128 : 64)) * nph;
+        bn = can128 ? 128 : 64;
+        if (nwg < 200) splits = (int)((320 + nwg - 1) / nwg);
+    }
+    if (g_tile_bn == 64 || (g_tile_bn == 128 && can128)) bn = g_tile_bn;   // (experiments)
+    if (g_tile_splits > 0) splits = g_tile_splits;
+    return ConvRoute{Kind::tile, bn, 0, clamp_splits(splits, nk_all, nph, M, Mr, p.cout_pad, has_ws, ws_bytes), false};
 }
 
 // Where k_conv_patch_pf replaces k_conv_patch_r8 / _lw: -> 0 (not) or the out-channel tiles (16 each) per workgroup.
@@ -1631,34 +1666,368 @@ static int pf_choice(const ConvP& p, int N) {
     return 0;
 }
 
-// Mr: the pixel count the DECISIONS are taken by (vsr::route_batch: = M unless a route batch is set); M: the pixels launched
-static int run_tile(ConvP& p, long long M, long long Mr, int nk_all, int nph, void* splitk_ws, size_t splitk_ws_bytes, hipStream_t st, const char* what) {
-    const bool can128 = (p.cout_pad & 127) == 0;
-    int splits = 1;
-    int bn = tile_choice(p, Mr, nk_all, nph, &splits);
-    if (bn == 0) {   // (mode 3 / experiments: a layer the heuristic leaves to the other kernels)
-        const long long nwg = vsr::cdiv(Mr, BM) * (long long)(p.cout_pad / (can128 ? 128 : 64)) * nph;
-        bn = can128 ? 128 : 64;
-        if (nwg < 200) splits = (int)((320 + nwg - 1) / nwg);
+static ConvRoute plan_conv(const ConvP& p, int Nr, bool has_ws, size_t ws_bytes) {
+    const int kh = p.kh, kw = p.kw, cin = p.cin, cout_pad = p.cout_pad, Ho = p.Ho, Wo = p.Wo;
+    const long long M = (long long)p.N * Ho * Wo, Mr = (long long)Nr * Ho * Wo;
+    const int nk_all = (kh * kw * (cin >> 5) + 1) >> 1;
+    const bool unit_stride = p.stride == 1 && p.stride_x == 1;
+    // stride-1 layers with a real spatial kernel and enough pixels: the 2-D LDS patch kernel (stages the input once per
+    // 32-channel chunk instead of gathering it kh*kw times from L2).  Measured on MI355X (tools/conv_microbench.py).
+    const int patch_lds = (PT_H + kh - 1) * (PT_W + kw - 1) * 64;
+    const bool patch_legal = unit_stride && Ho >= 4 && Wo >= 16 && patch_lds <= 64 * 1024 && p.N <= 65535 && (cout_pad & 15) == 0 &&
+                             (unsigned long long)(kh + 16) * p.W * p.in_ld * 2 < (1ull << 31);   // (staging: 32-bit byte offsets from the patch's first row)
+    const bool patch_pays = (long long)Ho * Wo >= 8192 && kh * kw >= 9 && ((cout_pad == 16 && (cin >> 5) <= 8) || cout_pad >= 32);
+    // the tile kernel (conv_tile.hip) where it wins (tile_choice); mode 3: every layer it can run, also the patch kernels' (tests)
+    int tile_splits = 1;
+    const int tile_bn = tile_choice(p, Mr, nk_all, 1, &tile_splits);
+    const bool tile_can = g_tile_mode >= 1 && !g_sw.first_gather && !g_sw.no_patch && (cout_pad & 63) == 0;
+    const bool tile_ok = tile_can && (g_tile_mode >= 3 || (tile_bn != 0 && !(kh == 1 && kw == 1 && Mr >= 65536)));
+    if (tile_can && g_tile_mode >= 3 && !g_sw.force_patch) return plan_tile(p, M, Mr, nk_all, 1, tile_bn, tile_splits, has_ws, ws_bytes);
+    if (patch_legal && !g_sw.no_patch && (patch_pays || g_sw.force_patch)) {
+        // 16 x 32 tiles, 8 rows per wave (k_conv_patch_r8) where a build exists and the patch fits the LDS: 32 out-channels
+        // per workgroup (grid.z walks the blocks; measured against 64 per workgroup on the 8 x 32 tile, tools/patch_exp.py:
+        // 3x3 32->64 at 2x512x960 93 -> 75 us, 64->128 at 2x256x480 80 -> 67 us) or the layer's 16
+        const int r8_lds = (P8_H + kh - 1) * (P8_W + kw - 1) * 64;
+        const int r8_mt = (cout_pad & 31) == 0 ? 2 : (cout_pad == 16 ? 1 : 0);
+        if (!g_sw.no_r8 && r8_mt && r8_lds <= 80 * 1024 && Ho >= 12 && kh_slot(kh) >= 0) {
+            // the persistent, prefetching build (conv_patch_pf.hip): see pf_choice
+            if (g_pf_mode >= 1 && kh == kw) {
+                const int pf_mt = pf_choice(p, Nr);
+                if (pf_mt) return ConvRoute{Kind::patch_pf, 0, pf_mt, 1, false};
+            }
+            // 3x3 layers on many pixels: the build with the weight block in LDS (k_conv_patch_lw), 64 out-channels per workgroup
+            // (32 for a 32-channel layer with >= 64 inputs).  Measured per layer inside the trunks (tools/trunk_layers.sh,
+            // profiles/r03_patch_lw_layers.txt): 540 x 960 64 -> 64 130 -> 97 us, 270 x 480 128 -> 128 110 -> 79, 64 -> 128 68 -> 54,
+            // 256 x 480 64 -> 128 60 -> 51, 270 x 480 64 -> 32 42 -> 36; it LOSES below ~500 workgroups (128 x 240 224 -> 64 29 -> 37:
+            // half as many workgroups as the 32-channel build) and for 5x5 / 7x7 (their weight block leaves one workgroup per CU).
+            // g_lw_mode: 0 never, 1 this heuristic, 2 wherever a build exists (tests / A-B).
+            if (g_lw_mode >= 1 && kh == kw) {
+                const int lw_mt = (kh == 3 && (cout_pad & 63) == 0) ? 4 : ((cout_pad & 31) == 0 && (kh == 3 || kh == 5 || kh == 7) ? 2 : 0);
+                const long long lw_wgs = lw_mt ? (long long)vsr::cdiv(Ho, P8_H) * vsr::cdiv(Wo, P8_W) * Nr * (cout_pad / (16 * lw_mt)) : 0;
+                const bool lw_pays = g_lw_mode >= 2 || (kh == 3 && lw_wgs >= 500 && (lw_mt == 4 || (cin >> 5) >= 2));
+                if (lw_mt && lw_pays) return ConvRoute{Kind::patch_lw, 0, lw_mt, 1, false};
+            }
+            return ConvRoute{Kind::patch_r8, 0, r8_mt, 1, false};
+        }
+        if ((cout_pad & 31) == 0) return ConvRoute{Kind::patch, 0, (cout_pad & 63) == 0 ? 4 : 2, 1, false};
+        return ConvRoute{cout_pad == 16 && !g_sw.no_rows && kh_slot(kh) >= 0 ? Kind::patch_rows : Kind::patch, 0, 1, 1, false};
     }
-    if (g_tile_bn == 64 || (g_tile_bn == 128 && can128)) bn = g_tile_bn;   // (experiments)
-    if (g_tile_splits > 0) splits = g_tile_splits;
-    if (splits > nk_all / 4) splits = nk_all / 4;
-    if (splits > 32) splits = 32;
-    if (!splitk_ws) splits = 1;
-    while (splits > 1 && (size_t)splits * nph * (M > Mr ? M : Mr) * p.cout_pad * sizeof(float) > splitk_ws_bytes) --splits;
-    if (splits < 1) splits = 1;
-    p.ws = splits > 1 ? (float*)splitk_ws : nullptr;
-    p.splits = splits;
-    vsr::route(splits > 1 ? "%stile<%d>+splitk%d" : "%stile<%d>", nph > 1 ? "deconv4s2 " : "", bn, splits);
-    int rc = vsrc::launch_conv_tile(p, bn, st);
+    // 1x1 over many pixels with more than one 64-channel block of outputs: the streaming kernel (input read once)
+    if (kh == 1 && kw == 1 && unit_stride && p.pad_y == 0 && p.pad_x == 0 && p.oy_mul == 1 && p.ox_mul == 1 && p.oy_off == 0 && p.ox_off == 0 &&
+        p.outH == Ho && p.outW == Wo && (cin >> 5) <= C1_MAX_CHUNKS && (size_t)(cin >> 5) * cout_pad * 64 <= 128 * 1024 && cout_pad > 64 && Mr >= 65536 &&
+        !g_sw.no_patch) {
+#if VSR_X
+        // 128 input channels, 8-aligned output slice: the build with contiguous KiB accesses on both sides (k_conv1x1_t)
+        if (g_c1t_mode >= 1 && cin == 128 && (p.cout & 7) == 0 && (p.out_ld & 7) == 0 && (p.out_coff & 7) == 0 && c1t_lds(p) <= 160 * 1024 &&
+            (unsigned long long)M * p.in_ld * 2 < kGatherLimit && (unsigned long long)M * p.out_ld * 2 < kGatherLimit && p.cout <= 256)
+            return ConvRoute{Kind::conv1x1_t, 0, 0, 1, false};
+#endif
+        return ConvRoute{Kind::conv1x1_stream, 0, 0, 1, false};
+    }
+    if (tile_ok) return plan_tile(p, M, Mr, nk_all, 1, tile_bn, tile_splits, has_ws, ws_bytes);
+    const unsigned gxr = vsr::cdiv(Mr, BM);   // (the workgroups the decisions count)
+    // widest tile the padded count fills; 128 out-channels per workgroup (half the pixel-operand traffic per FLOP: these
+    // layers run at the L2's bandwidth, 43 FLOP per byte with the 128 x 64 tile) when that still leaves 128 workgroups
+    // before split-K (measured per layer, tools/probe_layers.py with VSR_TUNING=10 / 11)
+    const bool wide = (cout_pad & 127) == 0 && !g_sw.first_gather && !g_sw.wide_never && (g_sw.wide_always || (long long)gxr * (cout_pad / 128) >= 128);
+    const int bn = wide ? 128 : (cout_pad & 63) == 0 ? 64 : ((cout_pad & 31) == 0 ? 32 : 16);
+    // split-K when the launch cannot fill the chip and K is long
+    const long long wgs = (long long)gxr * (cout_pad / bn);
+    int splits = 1;
+    if (has_ws && wgs < g_splitk_fill && nk_all >= 8) splits = clamp_splits((int)((g_splitk_fill * 2 + wgs - 1) / wgs), nk_all, 1, M, Mr, cout_pad, has_ws, ws_bytes);
+    return ConvRoute{Kind::gather, bn, 0, splits, g_sw.first_gather};
+}
+
+static ConvRoute plan_stem(const ConvP& p, int Nr, bool, size_t) {
+    const long long Mr = (long long)Nr * p.Ho * p.Wo;
+    // the hourglass stem's shape: persistent row-walking kernel with register-resident weights and full-line stores
+    if (!g_sw.no_patch && p.kh == 7 && p.kw == 7 && p.stride == 1 && p.pad_y == 3 && p.pad_x == 3 && p.cout == 128 && p.cout_pad == 128 && p.Ho == p.H &&
+        p.Wo == p.W && (p.out_ld & 7) == 0 && (p.out_coff & 7) == 0 && (unsigned long long)p.N * p.H * p.W * 8 < (1ull << 31) && Mr >= 65536 &&
+        (long long)p.N * vsr::cdiv(p.Wo, ST_C) * vsr::cdiv(p.Ho, ST_R) < (1ll << 30))
+        return ConvRoute{Kind::stem7_rows, 0, 0, 1, false};
+    return ConvRoute{Kind::gather_stem, (p.cout_pad & 63) == 0 ? 64 : ((p.cout_pad & 31) == 0 ? 32 : 16), 0, 1, g_sw.first_gather};
+}
+
+static ConvRoute plan_deconv(const ConvP& p, int Nr, bool has_ws, size_t ws_bytes) {
+    const int cout_pad = p.cout_pad, H = p.H, W = p.W;
+    const long long M = (long long)p.N * H * W, Mr = (long long)Nr * H * W;
+    const int nk_all = (4 * (p.cin >> 5) + 1) >> 1;
+    const bool patch_on = !g_sw.no_patch && !g_sw.first_gather;
+    // few out-channels on many pixels: all four phases from one staged input patch (k_deconv4s2_patch)
+    if (patch_on && cout_pad <= 32 && (long long)H * W >= 8192 && H >= 4 && W >= 16 && p.N <= 65535 &&
+        (unsigned long long)(PT_H + 18) * W * p.in_ld * 2 < (1ull << 31))
+        return ConvRoute{Kind::deconv4s2_patch, 0, 0, 1, false};
+    int tile_splits = 1;
+    const int tile_bn = tile_choice(p, Mr, nk_all, 4, &tile_splits);
+    if (g_tile_mode >= 1 && patch_on && (cout_pad & 63) == 0 && (g_tile_mode >= 3 || tile_bn != 0))
+        return plan_tile(p, M, Mr, nk_all, 4, tile_bn, tile_splits, has_ws, ws_bytes);
+    const int bn = (cout_pad & 63) == 0 ? 64 : ((cout_pad & 31) == 0 ? 32 : 16);
+    const long long wgs = (long long)vsr::cdiv(Mr, BM) * (cout_pad / bn) * 4;   // (counted by the route batch)
+    int splits = 1;
+    if (has_ws && wgs < 128 && nk_all >= 8) splits = clamp_splits((int)(256 / wgs), nk_all, 4, M, Mr, cout_pad, has_ws, ws_bytes);
+    return ConvRoute{Kind::gather, bn, 0, splits, g_sw.first_gather};
+}
+
+// The one place a route is spelled (vsr_last_route(); tests and tools parse these strings).
+static void route_name(const ConvRoute& r, const ConvP& p) {
+    const char* dc = p.nphase > 1 ? "deconv4s2 " : "";
+    switch (r.kind) {
+    case Kind::gather: vsr::route(r.splits > 1 ? "%sgather<%d>+splitk%d" : "%sgather<%d>", dc, r.bn, r.splits); break;
+    case Kind::gather_stem: vsr::route("gather<%d,stem>", r.bn); break;
+    case Kind::tile: vsr::route(r.splits > 1 ? "%stile<%d>+splitk%d" : "%stile<%d>", dc, r.bn, r.splits); break;
+    case Kind::deconv4s2_patch: vsr::route("deconv4s2_patch"); break;
+    case Kind::stem7_rows: vsr::route("stem7_rows"); break;
+    case Kind::patch_pf: vsr::route("patch_pf<%d,%d>", p.kh, r.mt); break;
+    case Kind::patch_lw: vsr::route("patch_lw<%d,%d>", p.kh, r.mt); break;
+    case Kind::patch_r8: vsr::route("patch_r8<%d,%d>", p.kh, r.mt); break;
+    case Kind::patch: vsr::route("patch<%d>", r.mt); break;
+    case Kind::patch_rows: vsr::route("patch_rows<%d>", p.kh); break;
+    case Kind::conv1x1_stream: vsr::route("conv1x1_stream<%d>", p.cin >> 5); break;
+    case Kind::conv1x1_t: vsr::route("conv1x1_t"); break;
+    }
+}
+
+// What vsr::launched calls a launch of the route in vsr_last_error(): the entry's name and, for every kind but the gather, the kernel family.
+static const char* launch_name(const ConvRoute& r, const ConvP& p) {
+    const bool dc = p.nphase > 1;
+    switch (r.kind) {
+    case Kind::gather: return dc ? "deconv4s2_nhwc_f16" : "conv2d_nhwc_f16";
+    case Kind::gather_stem: return "conv2d_stem_f16";
+    case Kind::tile: return dc ? "deconv4s2_nhwc_f16/tile" : "conv2d_nhwc_f16/tile";
+    case Kind::deconv4s2_patch: return "deconv4s2_nhwc_f16/patch";
+    case Kind::stem7_rows: return "conv2d_stem_f16/rows";
+    case Kind::patch_pf: return "conv2d_nhwc_f16/patch_pf";
+    case Kind::patch_lw: return "conv2d_nhwc_f16/patch_lw";
+    case Kind::patch_r8: return "conv2d_nhwc_f16/patch_r8";
+    case Kind::patch:
+    case Kind::patch_rows: return "conv2d_nhwc_f16/patch";
+    case Kind::conv1x1_stream: return "conv2d_nhwc_f16/1x1";
+    case Kind::conv1x1_t: return "conv2d_nhwc_f16/1x1t";
+    }
+    return "conv2d";
+}
+
+// The gather kernels' one width-to-template switch (128 only without STEM; the first build has no 128).
+// launch_gather_wide is defined below launch_route, and the kernel tables of launch_route list their kernels in the order the old
+// ladder mentioned them, for one reason only: a code object holds its kernels in the order of their first mention, and this layout
+// let the refactor be checked with a plain diff of the device assembly.  The order carries NO meaning: nothing indexes by it beyond
+// the expressions next to each table, and a later change may reorder the tables (and move launch_gather_wide up here) freely.
+static int launch_gather_wide(const ConvP& p, dim3 grid, hipStream_t st);
+template <bool STEM>
+static int launch_gather_bn(const ConvP& p, const ConvRoute& r, dim3 grid, hipStream_t st) {
+#if VSR_X
+    if (r.first_build)   // (pixel operand through LDS): cross-check / A-B
+        return r.bn == 64 ? launch_gather_lds<64, STEM>(p, grid, st) : r.bn == 32 ? launch_gather_lds<32, STEM>(p, grid, st) : launch_gather_lds<16, STEM>(p, grid, st);
+#endif
+    if (!STEM && r.bn == 128) return launch_gather_wide(p, grid, st);
+    return r.bn == 64 ? launch_gather<64, STEM>(p, grid, st) : r.bn == 32 ? launch_gather<32, STEM>(p, grid, st) : launch_gather<16, STEM>(p, grid, st);
+}
+
+typedef void (*conv_kernel_t)(const ConvP);
+struct BigLds {   // a kernel whose dynamic LDS can exceed 64 KB: the limit is raised once per device (one bit each)
+    conv_kernel_t k;
+    unsigned long long raised;
+};
+static void raise_lds(BigLds& e) {
+    if (vsr::device_marked(e.raised)) return;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(e.k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    vsr::mark_device(e.raised);
+}
+
+// Launches the route `r` of the layer in `p` (p.splits / p.ws set from r) and, after a split-K launch, the finish.
+static int launch_route(const ConvP& p, const ConvRoute& r, hipStream_t st) {
+    const long long M = (long long)p.N * p.Ho * p.Wo;
+    const int kh = p.kh, nph = p.nphase > 1 ? p.nphase : 1;
+    int rc = VSR_OK;
+    switch (r.kind) {
+    case Kind::gather:
+    case Kind::gather_stem: {
+        const dim3 grid(vsr::cdiv(M, BM), p.cout_pad / r.bn, nph * r.splits);
+        rc = r.kind == Kind::gather ? launch_gather_bn<false>(p, r, grid, st) : launch_gather_bn<true>(p, r, grid, st);
+        break;
+    }
+    case Kind::tile:
+        rc = vsrc::launch_conv_tile(p, r.bn, st);
+        break;
+    case Kind::deconv4s2_patch:
+        hipLaunchKernelGGL(k_deconv4s2_patch, dim3(vsr::cdiv(p.H, PT_H) * vsr::cdiv(p.W, PT_W), p.N, p.cout_pad / 16), dim3(256), (PT_H + 2) * (PT_W + 2) * 64, st, p);
+        break;
+    case Kind::stem7_rows: {
+        const int tiles_x = (int)vsr::cdiv(p.Wo, ST_C), tiles_y = (int)vsr::cdiv(p.Ho, ST_R);
+        const long long ntiles = (long long)p.N * tiles_x * tiles_y;
+        const unsigned grid1 = (unsigned)(ntiles < 256 * 2 ? ntiles : 256 * 2);   // two 4-wave workgroups resident per CU (registers)
+        hipLaunchKernelGGL(k_stem7_rows, dim3(grid1), dim3(256), 0, st, p, tiles_x, tiles_y, (int)ntiles);
+        break;
+    }
+    case Kind::patch_pf:
+        rc = vsrc::launch_conv_patch_pf(p, r.mt, st);
+        break;
+    case Kind::patch_lw:
+    case Kind::patch_r8: {   // 16 x 32 tiles: the patch (lw: + the weight block), then the output tile
+        static BigLds lw[4] = {{k_conv_patch_lw<3, 4>, 0}, {k_conv_patch_lw<3, 2>, 0}, {k_conv_patch_lw<5, 2>, 0}, {k_conv_patch_lw<7, 2>, 0}};
+        static BigLds r8[4][2] = {{{k_conv_patch_r8<3, 2>, 0}, {k_conv_patch_r8<3, 1>, 0}}, {{k_conv_patch_r8<5, 2>, 0}, {k_conv_patch_r8<5, 1>, 0}},
+                                  {{k_conv_patch_r8<7, 2>, 0}, {k_conv_patch_r8<7, 1>, 0}}, {{k_conv_patch_r8<11, 2>, 0}, {k_conv_patch_r8<11, 1>, 0}}};
+        const bool is_lw = r.kind == Kind::patch_lw;
+        BigLds& e = is_lw ? lw[r.mt == 4 ? 0 : 1 + kh_slot(kh)] : r8[kh_slot(kh)][2 - r.mt];
+        const int lds_patch = is_lw ? (P8_H + kh - 1) * (P8_W + kh - 1) * 64 + kh * kh * 16 * r.mt * 64 : (P8_H + kh - 1) * (P8_W + p.kw - 1) * 64;
+        const int lds_out = 4 * P8_R * 16 * 32 * r.mt, lds = lds_patch > lds_out ? lds_patch : lds_out;
+        if (lds > 64 * 1024) raise_lds(e);
+        hipLaunchKernelGGL(e.k, dim3(vsr::cdiv(p.Ho, P8_H) * vsr::cdiv(p.Wo, P8_W), p.N, p.cout_pad / (16 * r.mt)), dim3(256), lds, st, p);
+        break;
+    }
+    case Kind::patch:
+    case Kind::patch_rows: {   // 8 x 32 tiles: the patch, then the output tile
+        const int lds_patch = (PT_H + kh - 1) * (PT_W + p.kw - 1) * 64, lds_out = 4 * 4 * 16 * 32 * r.mt;
+        static const conv_kernel_t ks[7] = {k_conv_patch<4>, k_conv_patch<2>, k_conv_patch_rows<3>, k_conv_patch_rows<5>, k_conv_patch_rows<7>,
+                                            k_conv_patch_rows<11>, k_conv_patch<1>};
+        const conv_kernel_t k = ks[r.kind == Kind::patch_rows ? 2 + kh_slot(kh) : r.mt == 4 ? 0 : r.mt == 2 ? 1 : 6];
+        hipLaunchKernelGGL(k, dim3(vsr::cdiv(p.Ho, PT_H) * vsr::cdiv(p.Wo, PT_W), p.N, p.cout_pad / (16 * r.mt)), dim3(256), lds_patch > lds_out ? lds_patch : lds_out, st, p);
+        break;
+    }
+    case Kind::conv1x1_stream: {
+        static const conv_kernel_t k1[C1_MAX_CHUNKS] = {k_conv1x1_stream<1>, k_conv1x1_stream<2>, k_conv1x1_stream<3>, k_conv1x1_stream<4>,
+                                                        k_conv1x1_stream<5>, k_conv1x1_stream<6>, k_conv1x1_stream<7>, k_conv1x1_stream<8>};
+        const conv_kernel_t k = k1[(p.cin >> 5) - 1];
+        const size_t k_lds = (size_t)(p.cin >> 5) * p.cout_pad * 64 + (size_t)p.cout_pad * 4;   // weights + bias
+        if (k_lds > 48 * 1024 &&
+            hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k_lds) != hipSuccess)
+            return vsr::fail(VSR_E_LAUNCH, "conv2d/1x1: cannot reserve %zu bytes of LDS", k_lds);
+        const int per_cu = (int)((160 * 1024) / k_lds) < 2 ? 1 : 2;   // 512-thread workgroups resident per CU
+        const long long nblk = (M + 255) / 256;
+        hipLaunchKernelGGL(k, dim3((unsigned)(nblk < 256LL * per_cu ? nblk : 256LL * per_cu)), dim3(512), k_lds, st, p);
+        break;
+    }
+    case Kind::conv1x1_t: {
+#if VSR_X
+        static BigLds t = {k_conv1x1_t, 0};
+        raise_lds(t);
+        const size_t t_lds = c1t_lds(p);
+        const int per_cu = (int)((160 * 1024) / t_lds) < 2 ? 1 : 2;
+        const long long nblk = (M + 127) / 128;
+        hipLaunchKernelGGL(k_conv1x1_t, dim3((unsigned)(nblk < 256LL * per_cu ? nblk : 256LL * per_cu)), dim3(256), t_lds, st, p);
+#endif
+        break;
+    }
+    }
     if (rc) return rc;
-    if (splits > 1) {
-        rc = vsr::launched(what);
+    if (r.splits > 1) {
+        rc = vsr::launched(launch_name(r, p));
         if (rc) return rc;
         hipLaunchKernelGGL(k_splitk_finish, dim3(vsr::cdiv(M * (p.cout_pad >> 2), 256), nph), dim3(256), 0, st, p);
     }
-    return vsr::launched(what);
+    return vsr::launched(launch_name(r, p));
+}
+// (down here: see launch_gather_bn)
+static int launch_gather_wide(const ConvP& p, dim3 grid, hipStream_t st) { return launch_gather<128, false>(p, grid, st); }
+
+// ---- what the three entries share: fill, argument checks (no pointer is read), sub-batches, plan + name + launch
+static ConvP make_convp(const void* in, int in_ld, int in_coff, const void* w_packed, const float* bias, void* out, int out_ld, int out_coff, int N, int H,
+                        int W, int cin, int Ho, int Wo, int cout, int cout_pad, int kh, int kw, int stride, int stride_x, int pad_y, int pad_x, int outH,
+                        int outW, int oy_mul, int oy_off, int ox_mul, int ox_off, int act, float slope) {
+    ConvP p = {};
+    p.in = (const _Float16*)in; p.wpk = (const _Float16*)w_packed; p.bias = bias; p.out = (_Float16*)out;
+    p.in_ld = in_ld; p.in_coff = in_coff; p.out_ld = out_ld; p.out_coff = out_coff;
+    p.N = N; p.H = H; p.W = W; p.cin = cin; p.Ho = Ho; p.Wo = Wo; p.cout = cout; p.cout_pad = cout_pad;
+    p.kh = kh; p.kw = kw; p.stride = stride; p.stride_x = stride_x > 0 ? stride_x : stride; p.pad_y = pad_y; p.pad_x = pad_x;
+    p.outH = outH; p.outW = outW; p.oy_mul = oy_mul; p.oy_off = oy_off; p.ox_mul = ox_mul; p.ox_off = ox_off;
+    p.act = act; p.slope = slope; p.ws = nullptr; p.splits = 1; p.nphase = 0;
+    return p;
+}
+// the stem reads [N,H,W,4] pixels as one 32-wide K chunk per kernel row
+static ConvP make_stem(const void* in4, const void* w_packed, const float* bias, void* out, int out_ld, int out_coff, int N, int H, int W, int Ho, int Wo,
+                       int cout, int cout_pad, int kh, int kw, int stride, int pad_y, int pad_x, int act, float slope) {
+    return make_convp(in4, 4, 0, w_packed, bias, out, out_ld, out_coff, N, H, W, 32, Ho, Wo, cout, cout_pad, kh, kw, stride, 0, pad_y, pad_x, Ho, Wo, 1, 0, 1, 0,
+                      act, slope);
+}
+// k4 s2 transposed convolution: four 2x2-tap phases in one launch; phase (py, px) writes output (2y + py, 2x + px), py = 0 gathers
+// input rows y-1, y (HDeconv4s2).  w_packed4: the phases' packed weights, or null (a plan without a launch)
+static ConvP make_deconv(const void* in, int in_ld, int in_coff, const void* const* w_packed4, const float* bias, void* out, int out_ld, int out_coff, int N,
+                         int H, int W, int cin, int cout, int cout_pad, int act, float slope) {
+    ConvP p = make_convp(in, in_ld, in_coff, nullptr, bias, out, out_ld, out_coff, N, H, W, cin, H, W, cout, cout_pad, 2, 2, 1, 1, 0, 0, 2 * H, 2 * W, 2, 0, 2, 0,
+                         act, slope);
+    p.nphase = 4;
+    for (int ph = 0; ph < 4; ++ph) {
+        const int py = ph >> 1, px = ph & 1;
+        p.wpk_ph[ph] = w_packed4 ? (const _Float16*)w_packed4[ph] : nullptr;
+        p.pad_y_ph[ph] = py == 0 ? 1 : 0; p.pad_x_ph[ph] = px == 0 ? 1 : 0;
+        p.oy_off_ph[ph] = py; p.ox_off_ph[ph] = px;
+    }
+    return p;
+}
+
+static int check_conv(const ConvP& p) {
+    VSR_REQUIRE(p.N > 0 && p.H > 0 && p.W > 0 && p.Ho > 0 && p.Wo > 0 && p.cout > 0 && p.kh > 0 && p.kw > 0 && p.stride > 0, "conv2d: bad shape");
+    VSR_REQUIRE(p.cin > 0 && (p.cin & 31) == 0, "conv2d: input channels %d must be padded to a multiple of 32", p.cin);
+    VSR_REQUIRE((p.in_ld & 7) == 0 && (p.in_coff & 7) == 0 && p.in_coff + p.cin <= p.in_ld, "conv2d: input slice [%d,+%d) of %d channels", p.in_coff, p.cin, p.in_ld);
+    VSR_REQUIRE(p.out_coff >= 0 && p.out_coff + p.cout <= p.out_ld, "conv2d: output slice [%d,+%d) of %d channels", p.out_coff, p.cout, p.out_ld);
+    VSR_REQUIRE(p.cout_pad >= p.cout && (p.cout_pad & 15) == 0, "conv2d: cout_pad %d", p.cout_pad);
+    VSR_REQUIRE((p.Ho - 1) * p.oy_mul + p.oy_off < p.outH && (p.Wo - 1) * p.ox_mul + p.ox_off < p.outW && p.oy_off >= 0 && p.ox_off >= 0,
+                "conv2d: output window exceeds the destination tensor");
+    VSR_REQUIRE(p.act >= 0 && p.act <= 2, "conv2d: activation %d", p.act);
+    VSR_REQUIRE((unsigned long long)p.H * p.W * p.in_ld * 2 < kGatherLimit, "conv2d: one %dx%dx%d fp16 image exceeds the 4 GiB the kernels address", p.H, p.W, p.in_ld);
+    return VSR_OK;
+}
+static int check_stem(const ConvP& p) {
+    VSR_REQUIRE(p.N > 0 && p.H > 0 && p.W > 0 && p.Ho > 0 && p.Wo > 0 && p.cout > 0 && p.kh > 0 && p.kw > 0 && p.kw <= 8 && p.stride > 0, "conv2d_stem: bad shape");
+    VSR_REQUIRE(p.out_coff >= 0 && p.out_coff + p.cout <= p.out_ld && p.cout_pad >= p.cout && (p.cout_pad & 15) == 0, "conv2d_stem: output slice");
+    VSR_REQUIRE(p.act >= 0 && p.act <= 2, "conv2d_stem: activation %d", p.act);
+    VSR_REQUIRE((unsigned long long)p.N * p.H * p.W * 8 < kGatherLimit, "conv2d_stem: input batch beyond the 4 GiB the kernel addresses");
+    return VSR_OK;
+}
+static int check_deconv(const ConvP& p) {
+    VSR_REQUIRE(p.N > 0 && p.H > 0 && p.W > 0 && p.cout > 0 && p.cin > 0 && (p.cin & 31) == 0, "deconv4s2: bad shape");
+    VSR_REQUIRE((p.in_ld & 7) == 0 && (p.in_coff & 7) == 0 && p.in_coff + p.cin <= p.in_ld, "deconv4s2: input slice");
+    VSR_REQUIRE(p.out_coff >= 0 && p.out_coff + p.cout <= p.out_ld && p.cout_pad >= p.cout && (p.cout_pad & 15) == 0, "deconv4s2: output slice");
+    VSR_REQUIRE(p.act >= 0 && p.act <= 2, "deconv4s2: activation %d", p.act);
+    VSR_REQUIRE((unsigned long long)p.H * p.W * p.in_ld * 2 < kGatherLimit, "deconv4s2: one %dx%dx%d fp16 image exceeds the 4 GiB the kernel addresses", p.H, p.W, p.in_ld);
+    return VSR_OK;
+}
+
+// The gather kernels address the whole input batch through one buffer resource with 32-bit byte offsets (0xFFFFFFFF = "out of image"):
+// a batch beyond that runs as sub-batches of whole images (images are independent).  run(q): q = p narrowed to one sub-batch;
+// img_out: output elements per image (the input's follow from p: one image is below the limit, check_conv / check_deconv).
+template <class F>
+static int for_sub_batches(const ConvP& p, size_t img_out, F&& run) {
+    const unsigned long long img_in = (unsigned long long)p.H * p.W * p.in_ld;
+    const int per = img_in * 2 * p.N >= kGatherLimit ? (int)((kGatherLimit - 1) / (img_in * 2)) : p.N;
+    for (int n0 = 0; n0 < p.N; n0 += per) {
+        ConvP q = p;
+        q.in = p.in + (size_t)n0 * img_in; q.out = p.out + (size_t)n0 * img_out; q.N = p.N - n0 < per ? p.N - n0 : per;
+        const int rc = run(q);
+        if (rc) return rc;
+    }
+    return VSR_OK;
+}
+
+// The three entries (the `kind` codes of vsr_conv2d_plan): their argument checks, their plan function and their words for too many pixels.
+enum Entry { kConv = 0, kStem = 1, kDeconv = 2 };
+struct EntryDef {
+    int (*check)(const ConvP&);
+    ConvRoute (*plan)(const ConvP&, int Nr, bool has_ws, size_t ws_bytes);
+    const char* too_many;
+};
+static const EntryDef kEntries[3] = {
+    {check_conv, plan_conv, "conv2d: %lld output pixels exceed the kernels' 32-bit pixel index"},
+    {check_stem, plan_stem, "conv2d_stem: %lld output pixels exceed the kernels' 32-bit pixel index"},
+    {check_deconv, plan_deconv, "deconv4s2: %lld output pixels per phase exceed the kernel's 32-bit pixel index"}};
+
+// The route of `p` through the plan function of its entry, decided by the route batch (vsr_conv2d_route_batch) and written to
+// vsr_last_route().
+static int plan_named(Entry entry, const ConvP& p, bool has_ws, size_t ws_bytes, ConvRoute* r) {
+    const long long M = (long long)p.N * p.Ho * p.Wo;
+    if (M >= (1ll << 31)) return vsr::fail(VSR_E_ARG, kEntries[entry].too_many, M);
+    *r = kEntries[entry].plan(p, vsr::route_batch(p.N), has_ws, ws_bytes);
+    route_name(*r, p);
+    return VSR_OK;
+}
+
+static int run_planned(Entry entry, ConvP& p, void* splitk_ws, size_t splitk_ws_bytes, vsr_stream_t stream) {
+    ConvRoute r;
+    const int rc = plan_named(entry, p, splitk_ws != nullptr, splitk_ws_bytes, &r);
+    if (rc) return rc;
+    p.splits = r.splits;
+    p.ws = r.splits > 1 ? (float*)splitk_ws : nullptr;
+    return launch_route(p, r, vsr::S(stream));
 }
 
 extern "C" {
@@ -1678,6 +2047,7 @@ int vsr_conv2d_tuning(int patch_mode) {
         return old;
     }
     g_patch_mode = patch_mode;
+    g_sw = decode_patch_mode(patch_mode);
     return old;
 }
 #endif  // VSR_X
@@ -1769,137 +2139,22 @@ int vsr_deconv4s2_nhwc_f16(const void* in, int in_ld, int in_coff, const void* c
                            int out_ld, int out_coff, int N, int H, int W, int cin, int cout, int cout_pad, int act, float slope,
                            void* splitk_ws, size_t splitk_ws_bytes, vsr_stream_t stream) {
     VSR_REQUIRE(in && w_packed4 && out, "deconv4s2: null pointer");
-    VSR_REQUIRE(N > 0 && H > 0 && W > 0 && cout > 0 && cin > 0 && (cin & 31) == 0, "deconv4s2: bad shape");
-    VSR_REQUIRE((in_ld & 7) == 0 && (in_coff & 7) == 0 && in_coff + cin <= in_ld, "deconv4s2: input slice");
-    VSR_REQUIRE(out_coff >= 0 && out_coff + cout <= out_ld && cout_pad >= cout && (cout_pad & 15) == 0, "deconv4s2: output slice");
-    VSR_REQUIRE(act >= 0 && act <= 2, "deconv4s2: activation %d", act);
-    {   // 32-bit input offsets in the gather kernel: sub-batches of whole images beyond 4 GiB (see vsr_conv2d_nhwc_sx_f16)
-        const unsigned long long img_in = (unsigned long long)H * W * in_ld * 2;
-        if (img_in * N >= kGatherLimit) {
-            VSR_REQUIRE(img_in < kGatherLimit, "deconv4s2: one %dx%dx%d fp16 image exceeds the 4 GiB the kernel addresses", H, W, in_ld);
-            const int per = (int)((kGatherLimit - 1) / img_in);
-            for (int n0 = 0; n0 < N; n0 += per) {
-                const int rc = vsr_deconv4s2_nhwc_f16((const _Float16*)in + (size_t)n0 * (img_in / 2), in_ld, in_coff, w_packed4, bias,
-                                                      (_Float16*)out + (size_t)n0 * 4 * H * W * out_ld, out_ld, out_coff,
-                                                      N - n0 < per ? N - n0 : per, H, W, cin, cout, cout_pad, act, slope, splitk_ws,
-                                                      splitk_ws_bytes, stream);
-                if (rc) return rc;
-            }
-            return VSR_OK;
-        }
-    }
-    ConvP p;
-    p.in = (const _Float16*)in; p.wpk = nullptr; p.bias = bias; p.out = (_Float16*)out;
-    p.in_ld = in_ld; p.in_coff = in_coff; p.out_ld = out_ld; p.out_coff = out_coff;
-    p.N = N; p.H = H; p.W = W; p.cin = cin; p.Ho = H; p.Wo = W; p.cout = cout; p.cout_pad = cout_pad;
-    p.kh = 2; p.kw = 2; p.stride = 1; p.stride_x = 1; p.pad_y = 0; p.pad_x = 0;
-    p.outH = 2 * H; p.outW = 2 * W; p.oy_mul = 2; p.oy_off = 0; p.ox_mul = 2; p.ox_off = 0;
-    p.act = act; p.slope = slope;
-    p.nphase = 4;
-    for (int ph = 0; ph < 4; ++ph) {   // phase (py, px): output (2y + py, 2x + px); py = 0 gathers input rows y-1, y (HDeconv4s2)
-        const int py = ph >> 1, px = ph & 1;
-        VSR_REQUIRE(w_packed4[ph], "deconv4s2: phase %d weights", ph);
-        p.wpk_ph[ph] = (const _Float16*)w_packed4[ph];
-        p.pad_y_ph[ph] = py == 0 ? 1 : 0; p.pad_x_ph[ph] = px == 0 ? 1 : 0;
-        p.oy_off_ph[ph] = py; p.ox_off_ph[ph] = px;
-    }
-    const long long M = (long long)N * H * W, Mr = (long long)vsr::route_batch(N) * H * W;
-    VSR_REQUIRE(M < (1ll << 31), "deconv4s2: %lld output pixels per phase exceed the kernel's 32-bit pixel index", M);
-    // few out-channels on many pixels: all four phases from one staged input patch (k_deconv4s2_patch)
-    if (g_patch_mode != 1 && g_patch_mode != 8 && cout_pad <= 32 && (long long)H * W >= 8192 && H >= 4 && W >= 16 && N <= 65535 &&
-        (unsigned long long)(PT_H + 18) * W * in_ld * 2 < (1ull << 31)) {
-        p.ws = nullptr; p.splits = 1;
-        const unsigned tiles = vsr::cdiv(H, PT_H) * vsr::cdiv(W, PT_W);
-        vsr::route("deconv4s2_patch");
-        hipLaunchKernelGGL(k_deconv4s2_patch, dim3(tiles, N, cout_pad / 16), dim3(256), (PT_H + 2) * (PT_W + 2) * 64, vsr::S(stream), p);
-        return vsr::launched("deconv4s2_nhwc_f16/patch");
-    }
-    int ts_ = 1;
-    if (g_tile_mode >= 1 && g_patch_mode != 8 && g_patch_mode != 1 && (cout_pad & 63) == 0 &&
-        (g_tile_mode >= 3 || tile_choice(p, Mr, (4 * (cin >> 5) + 1) >> 1, 4, &ts_) != 0))
-        return run_tile(p, M, Mr, (4 * (cin >> 5) + 1) >> 1, 4, splitk_ws, splitk_ws_bytes, vsr::S(stream), "deconv4s2_nhwc_f16/tile");
-    const unsigned gx = vsr::cdiv(M, BM), gxr = vsr::cdiv(Mr, BM);   // (gxr: the workgroups the decisions count)
-    const int bn = (cout_pad & 63) == 0 ? 64 : ((cout_pad & 31) == 0 ? 32 : 16);
-    const unsigned gy = cout_pad / bn;
-    const int nk_all = (4 * (cin >> 5) + 1) >> 1;
-    int splits = 1;
-    if (splitk_ws && (long long)gxr * gy * 4 < 128 && nk_all >= 8) {
-        splits = (int)(256 / ((long long)gxr * gy * 4));
-        if (splits > nk_all / 4) splits = nk_all / 4;
-        if (splits > 32) splits = 32;
-        while (splits > 1 && (size_t)splits * 4 * (M > Mr ? M : Mr) * cout_pad * sizeof(float) > splitk_ws_bytes) --splits;
-        if (splits < 1) splits = 1;
-    }
-    p.ws = splits > 1 ? (float*)splitk_ws : nullptr;
-    p.splits = splits;
-    const dim3 grid(gx, gy, 4 * splits);
-    vsr::route(splits > 1 ? "deconv4s2 gather<%d>+splitk%d" : "deconv4s2 gather<%d>", bn, splits);
-#if VSR_X
-    if (g_patch_mode == 8) {   // the first gather build (pixel operand through LDS): cross-check / A-B
-        const int rc = bn == 64 ? launch_gather_lds<64, false>(p, grid, vsr::S(stream)) : bn == 32 ? launch_gather_lds<32, false>(p, grid, vsr::S(stream))
-                                                                                                     : launch_gather_lds<16, false>(p, grid, vsr::S(stream));
-        if (rc) return rc;
-    } else
-#endif
-    {
-        const int rc = bn == 64 ? launch_gather<64, false>(p, grid, vsr::S(stream)) : bn == 32 ? launch_gather<32, false>(p, grid, vsr::S(stream))
-                                                                                                 : launch_gather<16, false>(p, grid, vsr::S(stream));
-        if (rc) return rc;
-    }
-    if (splits > 1) {
-        int rc = vsr::launched("deconv4s2_nhwc_f16");
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_splitk_finish, dim3(vsr::cdiv(M * (cout_pad >> 2), 256), 4), dim3(256), 0, vsr::S(stream), p);
-    }
-    return vsr::launched("deconv4s2_nhwc_f16");
+    const ConvP p = make_deconv(in, in_ld, in_coff, w_packed4, bias, out, out_ld, out_coff, N, H, W, cin, cout, cout_pad, act, slope);
+    const int rc = check_deconv(p);
+    if (rc) return rc;
+    for (int ph = 0; ph < 4; ++ph) VSR_REQUIRE(p.wpk_ph[ph], "deconv4s2: phase %d weights", ph);
+    return for_sub_batches(p, (size_t)4 * H * W * out_ld,
+                           [&](ConvP& q) { return run_planned(kDeconv, q, splitk_ws, splitk_ws_bytes, stream); });
 }
 
 int vsr_conv2d_stem_f16(const void* in4, const void* w_packed, const float* bias, void* out, int out_ld, int out_coff, int N,
                         int H, int W, int Ho, int Wo, int cout, int cout_pad, int kh, int kw, int stride, int pad_y, int pad_x,
                         int act, float slope, vsr_stream_t stream) {
     VSR_REQUIRE(in4 && w_packed && out, "conv2d_stem: null pointer");
-    VSR_REQUIRE(N > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && cout > 0 && kh > 0 && kw > 0 && kw <= 8 && stride > 0, "conv2d_stem: bad shape");
-    VSR_REQUIRE(out_coff >= 0 && out_coff + cout <= out_ld && cout_pad >= cout && (cout_pad & 15) == 0, "conv2d_stem: output slice");
-    VSR_REQUIRE(act >= 0 && act <= 2, "conv2d_stem: activation %d", act);
-    VSR_REQUIRE((unsigned long long)N * H * W * 8 < kGatherLimit, "conv2d_stem: input batch beyond the 4 GiB the kernel addresses");
-    const int stride_x = 0;
-    ConvP p;
-    p.in = (const _Float16*)in4; p.wpk = (const _Float16*)w_packed; p.bias = bias; p.out = (_Float16*)out;
-    p.in_ld = 4; p.in_coff = 0; p.out_ld = out_ld; p.out_coff = out_coff;
-    p.N = N; p.H = H; p.W = W; p.cin = 32; p.Ho = Ho; p.Wo = Wo; p.cout = cout; p.cout_pad = cout_pad;
-    p.kh = kh; p.kw = kw; p.stride = stride; p.stride_x = stride_x > 0 ? stride_x : stride; p.pad_y = pad_y; p.pad_x = pad_x;
-    p.outH = Ho; p.outW = Wo; p.oy_mul = 1; p.oy_off = 0; p.ox_mul = 1; p.ox_off = 0;
-    p.act = act; p.slope = slope; p.ws = nullptr; p.splits = 1; p.nphase = 0;
-    const long long M = (long long)N * Ho * Wo, Mr = (long long)vsr::route_batch(N) * Ho * Wo;
-    VSR_REQUIRE(M < (1ll << 31), "conv2d_stem: %lld output pixels exceed the kernels' 32-bit pixel index", M);
-    // the hourglass stem's shape: persistent row-walking kernel with register-resident weights and full-line stores
-    if (g_patch_mode != 1 && kh == 7 && kw == 7 && stride == 1 && pad_y == 3 && pad_x == 3 && cout == 128 && cout_pad == 128 && Ho == H &&
-        Wo == W && (out_ld & 7) == 0 && (out_coff & 7) == 0 && (unsigned long long)N * H * W * 8 < (1ull << 31) && Mr >= 65536) {
-        const int tiles_x = (int)vsr::cdiv(Wo, ST_C), tiles_y = (int)vsr::cdiv(Ho, ST_R);
-        const long long ntiles = (long long)N * tiles_x * tiles_y;
-        if (ntiles < (1ll << 30)) {
-            const unsigned grid1 = (unsigned)(ntiles < 256 * 2 ? ntiles : 256 * 2);   // two 4-wave workgroups resident per CU (registers)
-            vsr::route("stem7_rows");
-            hipLaunchKernelGGL(k_stem7_rows, dim3(grid1), dim3(256), 0, vsr::S(stream), p, tiles_x, tiles_y, (int)ntiles);
-            return vsr::launched("conv2d_stem_f16/rows");
-        }
-    }
-    const int bn = (cout_pad & 63) == 0 ? 64 : ((cout_pad & 31) == 0 ? 32 : 16);
-    const dim3 grid(vsr::cdiv(M, BM), cout_pad / bn, 1);
-    vsr::route("gather<%d,stem>", bn);
-#if VSR_X
-    if (g_patch_mode == 8) {   // the first gather build (pixel operand through LDS): cross-check / A-B
-        const int rc = bn == 64 ? launch_gather_lds<64, true>(p, grid, vsr::S(stream)) : bn == 32 ? launch_gather_lds<32, true>(p, grid, vsr::S(stream))
-                                                                                                    : launch_gather_lds<16, true>(p, grid, vsr::S(stream));
-        if (rc) return rc;
-    } else
-#endif
-    {
-        const int rc = bn == 64 ? launch_gather<64, true>(p, grid, vsr::S(stream)) : bn == 32 ? launch_gather<32, true>(p, grid, vsr::S(stream))
-                                                                                                : launch_gather<16, true>(p, grid, vsr::S(stream));
-        if (rc) return rc;
-    }
-    return vsr::launched("conv2d_stem_f16");
+    ConvP p = make_stem(in4, w_packed, bias, out, out_ld, out_coff, N, H, W, Ho, Wo, cout, cout_pad, kh, kw, stride, pad_y, pad_x, act, slope);
+    const int rc = check_stem(p);
+    if (rc) return rc;
+    return run_planned(kStem, p, nullptr, 0, stream);
 }
 
 int vsr_conv2d_nhwc_sx_f16(const void* in, int in_ld, int in_coff, const void* w_packed, const float* bias, void* out,
@@ -1908,202 +2163,28 @@ int vsr_conv2d_nhwc_sx_f16(const void* in, int in_ld, int in_coff, const void* w
                            int ox_mul, int ox_off, int act, float slope, void* splitk_ws, size_t splitk_ws_bytes,
                            vsr_stream_t stream) {
     VSR_REQUIRE(in && w_packed && out, "conv2d: null pointer");
-    VSR_REQUIRE(N > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && cout > 0 && kh > 0 && kw > 0 && stride > 0, "conv2d: bad shape");
-    VSR_REQUIRE(cin > 0 && (cin & 31) == 0, "conv2d: input channels %d must be padded to a multiple of 32", cin);
-    VSR_REQUIRE((in_ld & 7) == 0 && (in_coff & 7) == 0 && in_coff + cin <= in_ld, "conv2d: input slice [%d,+%d) of %d channels", in_coff, cin, in_ld);
-    VSR_REQUIRE(out_coff >= 0 && out_coff + cout <= out_ld, "conv2d: output slice [%d,+%d) of %d channels", out_coff, cout, out_ld);
-    VSR_REQUIRE(cout_pad >= cout && (cout_pad & 15) == 0, "conv2d: cout_pad %d", cout_pad);
-    VSR_REQUIRE((Ho - 1) * oy_mul + oy_off < outH && (Wo - 1) * ox_mul + ox_off < outW && oy_off >= 0 && ox_off >= 0,
-                "conv2d: output window exceeds the destination tensor");
-    VSR_REQUIRE(act >= 0 && act <= 2, "conv2d: activation %d", act);
-    {   // the gather kernels address the whole input batch through one buffer resource with 32-bit byte offsets
-        // (0xFFFFFFFF = "out of image"): a batch beyond that is run as sub-batches of whole images (images are independent)
-        const unsigned long long img_in = (unsigned long long)H * W * in_ld * 2;
-        if (img_in * N >= kGatherLimit) {
-            VSR_REQUIRE(img_in < kGatherLimit, "conv2d: one %dx%dx%d fp16 image exceeds the 4 GiB the kernels address", H, W, in_ld);
-            const int per = (int)((kGatherLimit - 1) / img_in);
-            const size_t img_out = (size_t)outH * outW * out_ld;
-            for (int n0 = 0; n0 < N; n0 += per) {
-                const int rc = vsr_conv2d_nhwc_sx_f16((const _Float16*)in + (size_t)n0 * (img_in / 2), in_ld, in_coff, w_packed, bias,
-                                                      (_Float16*)out + (size_t)n0 * img_out, out_ld, out_coff, N - n0 < per ? N - n0 : per, H, W,
-                                                      cin, Ho, Wo, cout, cout_pad, kh, kw, stride, stride_x, pad_y, pad_x, outH, outW, oy_mul,
-                                                      oy_off, ox_mul, ox_off, act, slope, splitk_ws, splitk_ws_bytes, stream);
-                if (rc) return rc;
-            }
-            return VSR_OK;
-        }
-    }
-    ConvP p;
-    p.in = (const _Float16*)in; p.wpk = (const _Float16*)w_packed; p.bias = bias; p.out = (_Float16*)out;
-    p.in_ld = in_ld; p.in_coff = in_coff; p.out_ld = out_ld; p.out_coff = out_coff;
-    p.N = N; p.H = H; p.W = W; p.cin = cin; p.Ho = Ho; p.Wo = Wo; p.cout = cout; p.cout_pad = cout_pad;
-    p.kh = kh; p.kw = kw; p.stride = stride; p.stride_x = stride_x > 0 ? stride_x : stride; p.pad_y = pad_y; p.pad_x = pad_x;
-    p.outH = outH; p.outW = outW; p.oy_mul = oy_mul; p.oy_off = oy_off; p.ox_mul = ox_mul; p.ox_off = ox_off;
-    p.act = act; p.slope = slope; p.nphase = 0;
-    const int Nr = vsr::route_batch(N);   // the batch the kernel / tile / split-K decisions below count (= N unless vsr_conv2d_route_batch is set)
-    const long long M = (long long)N * Ho * Wo, Mr = (long long)Nr * Ho * Wo;
-    VSR_REQUIRE(M < (1ll << 31), "conv2d: %lld output pixels exceed the kernels' 32-bit pixel index", M);
-    // stride-1 layers with a real spatial kernel and enough pixels: the 2-D LDS patch kernel (stages the input once per
-    // 32-channel chunk instead of gathering it kh*kw times from L2).  Measured on MI355X (tools/conv_microbench.py).
-    const int patch_lds = (PT_H + kh - 1) * (PT_W + kw - 1) * 64;
-    const bool patch_legal = stride == 1 && (stride_x <= 0 || stride_x == 1) && Ho >= 4 && Wo >= 16 && patch_lds <= 64 * 1024 && N <= 65535 && (cout_pad & 15) == 0 &&
-                             (unsigned long long)(kh + 16) * W * in_ld * 2 < (1ull << 31);   // (staging: 32-bit byte offsets from the patch's first row)
-    const bool patch_pays = (long long)Ho * Wo >= 8192 && kh * kw >= 9 && ((cout_pad == 16 && (cin >> 5) <= 8) || cout_pad >= 32);
-    const bool force = g_patch_mode == 2 || g_patch_mode == 6 || g_patch_mode == 7;
-    const bool no_r8 = g_patch_mode == 3 || g_patch_mode == 5 || g_patch_mode == 6 || g_patch_mode == 7, no_rows = g_patch_mode == 3 || g_patch_mode == 7;
-    // the tile kernel (conv_tile.hip) where it wins (tile_choice); mode 3: every layer it can run, also the patch kernels' (tests)
-    int ts_ = 1;
-    const int nk_all_ = (kh * kw * (cin >> 5) + 1) >> 1;
-    const bool tile_can = g_tile_mode >= 1 && g_patch_mode != 8 && g_patch_mode != 1 && (cout_pad & 63) == 0;
-    const bool tile_ok = tile_can && (g_tile_mode >= 3 || (tile_choice(p, Mr, nk_all_, 1, &ts_) != 0 && !(kh == 1 && kw == 1 && Mr >= 65536)));
-    if (tile_can && g_tile_mode >= 3 && !force)
-        return run_tile(p, M, Mr, nk_all_, 1, splitk_ws, splitk_ws_bytes, vsr::S(stream), "conv2d_nhwc_f16/tile");
-    if (patch_legal && g_patch_mode != 1 && (patch_pays || force)) {
-        p.ws = nullptr;
-        p.splits = 1;
-        const unsigned tiles = vsr::cdiv(Ho, PT_H) * vsr::cdiv(Wo, PT_W);
-        // 16 x 32 tiles, 8 rows per wave (k_conv_patch_r8) where a build exists and the patch fits the LDS: 32 out-channels
-        // per workgroup (grid.z walks the blocks; measured against 64 per workgroup on the 8 x 32 tile, tools/patch_exp.py:
-        // 3x3 32->64 at 2x512x960 93 -> 75 us, 64->128 at 2x256x480 80 -> 67 us) or the layer's 16
-        const int r8_lds = (P8_H + kh - 1) * (P8_W + kw - 1) * 64;
-        const int r8_mt = (cout_pad & 31) == 0 ? 2 : (cout_pad == 16 ? 1 : 0);
-        if (!no_r8 && r8_mt && r8_lds <= 80 * 1024 && Ho >= 12 && (kh == 3 || kh == 5 || kh == 7 || kh == 11)) {
-            hipStream_t st = vsr::S(stream);
-            // the persistent, prefetching build (conv_patch_pf.hip): see pf_choice
-            if (g_pf_mode >= 1 && kh == kw && g_patch_mode != 5) {
-                const int pf_mt = pf_choice(p, Nr);
-                if (pf_mt) {
-                    vsr::route("patch_pf<%d,%d>", kh, pf_mt);
-                    const int rc = vsrc::launch_conv_patch_pf(p, pf_mt, st);
-                    if (rc) return rc;
-                    return vsr::launched("conv2d_nhwc_f16/patch_pf");
-                }
-            }
-            // 3x3 layers on many pixels: the build with the weight block in LDS (k_conv_patch_lw), 64 out-channels per workgroup
-            // (32 for a 32-channel layer with >= 64 inputs).  Measured per layer inside the trunks (tools/trunk_layers.sh,
-            // profiles/r03_patch_lw_layers.txt): 540 x 960 64 -> 64 130 -> 97 us, 270 x 480 128 -> 128 110 -> 79, 64 -> 128 68 -> 54,
-            // 256 x 480 64 -> 128 60 -> 51, 270 x 480 64 -> 32 42 -> 36; it LOSES below ~500 workgroups (128 x 240 224 -> 64 29 -> 37:
-            // half as many workgroups as the 32-channel build) and for 5x5 / 7x7 (their weight block leaves one workgroup per CU).
-            // g_lw_mode: 0 never, 1 this heuristic, 2 wherever a build exists (tests / A-B).
-            if (g_lw_mode >= 1 && kh == kw && g_patch_mode != 5) {
-                const int lw_mt = (kh == 3 && (cout_pad & 63) == 0) ? 4 : ((cout_pad & 31) == 0 && (kh == 3 || kh == 5 || kh == 7) ? 2 : 0);
-                const long long lw_wgs = lw_mt ? (long long)vsr::cdiv(Ho, P8_H) * vsr::cdiv(Wo, P8_W) * Nr * (cout_pad / (16 * lw_mt)) : 0;
-                const bool lw_pays = g_lw_mode >= 2 || (kh == 3 && lw_wgs >= 500 && (lw_mt == 4 || (cin >> 5) >= 2));
-                if (lw_mt && lw_pays) {
-                    vsr::route("patch_lw<%d,%d>", kh, lw_mt);
-                    if (kh == 3 && lw_mt == 4) launch_patch_lw<3, 4>(p, N, st);
-                    else if (kh == 3) launch_patch_lw<3, 2>(p, N, st);
-                    else if (kh == 5) launch_patch_lw<5, 2>(p, N, st);
-                    else launch_patch_lw<7, 2>(p, N, st);
-                    return vsr::launched("conv2d_nhwc_f16/patch_lw");
-                }
-            }
-            vsr::route("patch_r8<%d,%d>", kh, r8_mt);
-#define VSR_R8(KH_) \
-            if (kh == KH_) { if (r8_mt == 2) launch_patch_r8<KH_, 2>(p, N, st); else launch_patch_r8<KH_, 1>(p, N, st); }
-            VSR_R8(3) VSR_R8(5) VSR_R8(7) VSR_R8(11)
-#undef VSR_R8
-            return vsr::launched("conv2d_nhwc_f16/patch_r8");
-        }
-        vsr::route((cout_pad & 63) == 0 ? "patch<4>" : (cout_pad & 31) == 0 ? "patch<2>" : (cout_pad == 16 && !no_rows && (kh == 3 || kh == 5 || kh == 7 || kh == 11)) ? "patch_rows<%d>" : "patch<1>", kh);
-        const auto lds_for = [&](int mt) { const int o = 4 * 4 * 16 * 32 * mt; return patch_lds > o ? patch_lds : o; };   // patch, then the output tile
-        if ((cout_pad & 63) == 0)
-            hipLaunchKernelGGL(k_conv_patch<4>, dim3(tiles, N, cout_pad / 64), dim3(256), lds_for(4), vsr::S(stream), p);
-        else if ((cout_pad & 31) == 0)
-            hipLaunchKernelGGL(k_conv_patch<2>, dim3(tiles, N, cout_pad / 32), dim3(256), lds_for(2), vsr::S(stream), p);
-        else if (cout_pad == 16 && kh == 3 && !no_rows)
-            hipLaunchKernelGGL(k_conv_patch_rows<3>, dim3(tiles, N, 1), dim3(256), lds_for(1), vsr::S(stream), p);
-        else if (cout_pad == 16 && kh == 5 && !no_rows)
-            hipLaunchKernelGGL(k_conv_patch_rows<5>, dim3(tiles, N, 1), dim3(256), lds_for(1), vsr::S(stream), p);
-        else if (cout_pad == 16 && kh == 7 && !no_rows)
-            hipLaunchKernelGGL(k_conv_patch_rows<7>, dim3(tiles, N, 1), dim3(256), lds_for(1), vsr::S(stream), p);
-        else if (cout_pad == 16 && kh == 11 && !no_rows)
-            hipLaunchKernelGGL(k_conv_patch_rows<11>, dim3(tiles, N, 1), dim3(256), lds_for(1), vsr::S(stream), p);
-        else
-            hipLaunchKernelGGL(k_conv_patch<1>, dim3(tiles, N, cout_pad / 16), dim3(256), lds_for(1), vsr::S(stream), p);
-        return vsr::launched("conv2d_nhwc_f16/patch");
-    }
-    // 1x1 over many pixels with more than one 64-channel block of outputs: the streaming kernel (input read once)
-    const size_t w_lds = (size_t)(cin >> 5) * cout_pad * 64;
-    if (kh == 1 && kw == 1 && stride == 1 && (stride_x <= 0 || stride_x == 1) && pad_y == 0 && pad_x == 0 && oy_mul == 1 && ox_mul == 1 && oy_off == 0 && ox_off == 0 &&
-        outH == Ho && outW == Wo && (cin >> 5) <= C1_MAX_CHUNKS && w_lds <= 128 * 1024 && cout_pad > 64 && Mr >= 65536 &&
-        g_patch_mode != 1) {
-        p.ws = nullptr;
-        p.splits = 1;
-#if VSR_X
-        // 128 input channels, 8-aligned output slice: the build with contiguous KiB accesses on both sides (k_conv1x1_t)
-        const size_t t_lds = w_lds + (size_t)cout_pad * 4 + (size_t)4 * 2 * C1T_SLOT;
-        if (g_c1t_mode >= 1 && cin == 128 && (cout & 7) == 0 && (out_ld & 7) == 0 && (out_coff & 7) == 0 && t_lds <= 160 * 1024 &&
-            (unsigned long long)M * in_ld * 2 < kGatherLimit && (unsigned long long)M * out_ld * 2 < kGatherLimit && cout <= 256) {
-            static unsigned long long raised = 0;
-            if (!vsr::device_marked(raised)) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv1x1_t), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                vsr::mark_device(raised);
-            }
-            const int per_cu = (int)((160 * 1024) / t_lds) < 2 ? 1 : 2;
-            const long long nblk = (M + 127) / 128;
-            const unsigned grid = (unsigned)(nblk < 256LL * per_cu ? nblk : 256LL * per_cu);
-            vsr::route("conv1x1_t");
-            hipLaunchKernelGGL(k_conv1x1_t, dim3(grid), dim3(256), t_lds, vsr::S(stream), p);
-            return vsr::launched("conv2d_nhwc_f16/1x1t");
-        }
-#endif  // VSR_X
-        typedef void (*k1_t)(const ConvP);
-        static const k1_t k1[C1_MAX_CHUNKS] = {k_conv1x1_stream<1>, k_conv1x1_stream<2>, k_conv1x1_stream<3>, k_conv1x1_stream<4>,
-                                               k_conv1x1_stream<5>, k_conv1x1_stream<6>, k_conv1x1_stream<7>, k_conv1x1_stream<8>};
-        const k1_t k = k1[(cin >> 5) - 1];
-        const size_t k_lds = w_lds + (size_t)cout_pad * 4;   // weights + bias
-        if (k_lds > 48 * 1024 &&
-            hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k_lds) != hipSuccess)
-            return vsr::fail(VSR_E_LAUNCH, "conv2d/1x1: cannot reserve %zu bytes of LDS", k_lds);
-        const int per_cu = (int)((160 * 1024) / k_lds) < 2 ? 1 : 2;   // 512-thread workgroups resident per CU
-        const long long nblk = (M + 255) / 256;
-        const unsigned grid = (unsigned)(nblk < 256LL * per_cu ? nblk : 256LL * per_cu);
-        vsr::route("conv1x1_stream<%d>", cin >> 5);
-        hipLaunchKernelGGL(k, dim3(grid), dim3(512), k_lds, vsr::S(stream), p);
-        return vsr::launched("conv2d_nhwc_f16/1x1");
-    }
-    if (tile_ok) return run_tile(p, M, Mr, nk_all_, 1, splitk_ws, splitk_ws_bytes, vsr::S(stream), "conv2d_nhwc_f16/tile");
-    const unsigned gx = vsr::cdiv(M, BM), gxr = vsr::cdiv(Mr, BM);   // (gxr: the workgroups the decisions count)
-    // widest tile the padded count fills; 128 out-channels per workgroup (half the pixel-operand traffic per FLOP: these
-    // layers run at the L2's bandwidth, 43 FLOP per byte with the 128 x 64 tile) when that still leaves 128 workgroups
-    // before split-K (measured per layer, tools/probe_layers.py with VSR_TUNING=10 / 11)
-    const bool wide = (cout_pad & 127) == 0 && g_patch_mode != 8 && g_patch_mode != 11 &&
-                      (g_patch_mode == 10 || (long long)gxr * (cout_pad / 128) >= 128);
-    const int bn = wide ? 128 : (cout_pad & 63) == 0 ? 64 : ((cout_pad & 31) == 0 ? 32 : 16);
-    const unsigned gy = cout_pad / bn;
-    // split-K when the launch cannot fill the chip and K is long
-    const int nk_all = (kh * kw * (cin >> 5) + 1) >> 1;
-    int splits = 1;
-    if (splitk_ws && (long long)gxr * gy < g_splitk_fill && nk_all >= 8) {
-        splits = (int)((g_splitk_fill * 2 + (long long)gxr * gy - 1) / ((long long)gxr * gy));
-        if (splits > nk_all / 4) splits = nk_all / 4;
-        if (splits > 32) splits = 32;
-        while (splits > 1 && (size_t)splits * (M > Mr ? M : Mr) * cout_pad * sizeof(float) > splitk_ws_bytes) --splits;
-        if (splits < 1) splits = 1;
-    }
-    p.ws = splits > 1 ? (float*)splitk_ws : nullptr;
-    p.splits = splits;
-    const dim3 grid(gx, gy, splits);
-    vsr::route(splits > 1 ? "gather<%d>+splitk%d" : "gather<%d>", bn, splits);
-#if VSR_X
-    if (g_patch_mode == 8) {   // the first gather build (pixel operand through LDS): cross-check / A-B
-        const int rc = bn == 64 ? launch_gather_lds<64, false>(p, grid, vsr::S(stream)) : bn == 32 ? launch_gather_lds<32, false>(p, grid, vsr::S(stream))
-                                                                                                     : launch_gather_lds<16, false>(p, grid, vsr::S(stream));
-        if (rc) return rc;
-    } else
-#endif
-    {
-        const int rc = bn == 128 ? launch_gather<128, false>(p, grid, vsr::S(stream)) : bn == 64 ? launch_gather<64, false>(p, grid, vsr::S(stream))
-                     : bn == 32 ? launch_gather<32, false>(p, grid, vsr::S(stream)) : launch_gather<16, false>(p, grid, vsr::S(stream));
-        if (rc) return rc;
-    }
-    if (splits > 1) {
-        int rc = vsr::launched("conv2d_nhwc_f16");
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_splitk_finish, dim3(vsr::cdiv(M * (cout_pad >> 2), 256)), dim3(256), 0, vsr::S(stream), p);
-    }
-    return vsr::launched("conv2d_nhwc_f16");
+    const ConvP p = make_convp(in, in_ld, in_coff, w_packed, bias, out, out_ld, out_coff, N, H, W, cin, Ho, Wo, cout, cout_pad, kh, kw, stride, stride_x,
+                               pad_y, pad_x, outH, outW, oy_mul, oy_off, ox_mul, ox_off, act, slope);
+    const int rc = check_conv(p);
+    if (rc) return rc;
+    return for_sub_batches(p, (size_t)outH * outW * out_ld,
+                           [&](ConvP& q) { return run_planned(kConv, q, splitk_ws, splitk_ws_bytes, stream); });
 }
+
+#if VSR_X
+int vsr_conv2d_plan(int kind, int in_ld, int N, int H, int W, int cin, int Ho, int Wo, int cout, int cout_pad, int kh, int kw, int stride,
+                    int stride_x, int pad_y, int pad_x, int out_ld, int out_coff, int outH, int outW, int oy_mul, int oy_off, int ox_mul, int ox_off,
+                    int has_ws, size_t ws_bytes) {
+    VSR_REQUIRE(kind >= 0 && kind <= 2, "conv2d_plan: kind %d", kind);
+    const ConvP p = kind == 0 ? make_convp(nullptr, in_ld, 0, nullptr, nullptr, nullptr, out_ld, out_coff, N, H, W, cin, Ho, Wo, cout, cout_pad, kh, kw, stride,
+                                           stride_x, pad_y, pad_x, outH, outW, oy_mul, oy_off, ox_mul, ox_off, 0, 0.0f)
+                  : kind == 1 ? make_stem(nullptr, nullptr, nullptr, nullptr, out_ld, out_coff, N, H, W, Ho, Wo, cout, cout_pad, kh, kw, stride, pad_y, pad_x, 0, 0.0f)
+                              : make_deconv(nullptr, in_ld, 0, nullptr, nullptr, nullptr, out_ld, out_coff, N, H, W, cin, cout, cout_pad, 0, 0.0f);
+    const int rc = kEntries[kind].check(p);
+    if (rc) return rc;
+    ConvRoute r;
+    return plan_named((Entry)kind, p, has_ws != 0, ws_bytes, &r);
+}
+#endif  // VSR_X
 
 }  // extern "C"
