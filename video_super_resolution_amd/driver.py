@@ -11,6 +11,12 @@ feeds it, on the GPU path and without OpenCV:
                             estimated_image); estimated_image = output` (main.py:196-203) -> HR frames (+ losses)
     frames_to_u8            HR write-out, float32 -> uint8 NHWC on the device (the step after the path; the reference never
                             writes its frames)
+    read_clip_yuv / ingest_item_yuv / frames_to_yuv     the same three steps for what decoders emit: packed Y'CbCr 4:2:0 frames
+                            (yuv420p, nv12, yuv420p10le, p010le), converted on the device (include/vsr_hip_yuv.h); the matrix
+                            coefficients come from `yuv_coefficients` alone
+    ClipRunner              a clip streamed through the model: every source frame uploaded once from pinned memory on a copy stream,
+                            converted once into a three-slot LR ring, the window formed on the device, the HR frame written out as
+                            4:2:0 and copied back on a second copy stream
     save_checkpoint / load_checkpoint   utils/tools.py:68-73 and main.py:108-122,233-237: {'arch','epoch','state_dict':
                             SRmodel.model.state_dict(),'optimizer'} -- files interchange with the reference's
 
@@ -18,7 +24,7 @@ feeds it, on the GPU path and without OpenCV:
 main-like plumbing) on the GPU path (`tools/c1_check.py` runs the CPU checker beside it and reports the PSNR between the two:
 the package itself never touches the checker).
 Decoding compressed video (cv2.VideoCapture, video_utils.py:17-23) is out of scope: a clip enters as a uint8 RGB array
-(`.npy`, raw rgb24, or synthetic).
+(`.npy`, raw rgb24, or synthetic) or as raw 4:2:0 frames (`ffmpeg -f rawvideo`; transfer functions, 4:2:2 / 4:4:4 stay out too).
 """
 from __future__ import annotations
 
@@ -119,6 +125,140 @@ def frames_to_u8(frames: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# ------------------------------------------------------------------------------------------------ Y'CbCr 4:2:0 in and out
+YUV_FORMATS = {"yuv420p": 0, "nv12": 1, "yuv420p10le": 2, "p010le": 3}      # the `fmt` codes of include/vsr_hip_yuv.h
+YUV_SITINGS = {"left": 0, "center": 1}
+_YUV_KR_KB = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722), "bt2020": (0.2627, 0.0593)}   # bt2020: non-constant luminance
+
+
+def _yuv_depth(fmt: str) -> int:
+    if fmt not in YUV_FORMATS:
+        raise ValueError(f"unknown pixel format {fmt!r} (known: {', '.join(YUV_FORMATS)})")
+    return 10 if fmt in ("yuv420p10le", "p010le") else 8
+
+
+def yuv_frame_bytes(fmt: str, H: int, W: int) -> int:
+    """Bytes of one packed 4:2:0 frame: 3/2 samples per pixel, 1 byte (8-bit formats) or 2 bytes (10-bit formats) per sample."""
+    d = _yuv_depth(fmt)
+    if H <= 0 or W <= 0 or H % 2 or W % 2:
+        raise ValueError(f"4:2:0 needs positive even H and W, got {H} x {W}")
+    return H * W * 3 // 2 * (2 if d == 10 else 1)
+
+
+def yuv_coefficients(fmt: str, matrix: str = "bt709", full_range: bool = False, inverse: bool = False, dtype=np.float32) -> np.ndarray:
+    """The 12 values the device entries take: a row-major 3x3 matrix, then 3 offsets.  Forward (`inverse=False`): the model's R'G'B'
+    in 0..255 -> the code values (Y, Cb, Cr) of `fmt`, what `frames_to_yuv` applies; `inverse=True`: code values -> R'G'B' in 0..255,
+    what `ingest_item_yuv` applies.  With (Kr, Kb) of `matrix`, Kg = 1 - Kr - Kb, E'Y = Kr R + Kg G + Kb B, E'Cb = (B - E'Y) / (2 (1 - Kb)),
+    E'Cr = (R - E'Y) / (2 (1 - Kr)) on R'G'B' in 0..1 and d the bit depth: limited range Y = (16 + 219 E'Y) 2^(d-8),
+    C = (128 + 224 E'C) 2^(d-8); full range Y = (2^d - 1) E'Y, C = 2^(d-1) + (2^d - 1) E'C.  Computed in float64 and rounded once to
+    `dtype`; this is the single source of the coefficients (the C side computes none)."""
+    d = _yuv_depth(fmt)
+    if matrix not in _YUV_KR_KB:
+        raise ValueError(f"unknown matrix {matrix!r} (known: {', '.join(_YUV_KR_KB)})")
+    kr, kb = _YUV_KR_KB[matrix]
+    kg = 1.0 - kr - kb
+    if full_range:
+        sy = sc = float(2 ** d - 1)
+        oy, oc = 0.0, float(2 ** (d - 1))
+    else:
+        m = float(2 ** (d - 8))
+        sy, sc, oy, oc = 219.0 * m, 224.0 * m, 16.0 * m, 128.0 * m
+    gy, gc = sy / 255.0, sc / 255.0
+    if not inverse:
+        A = np.array([[gy * kr, gy * kg, gy * kb],
+                      [-gc * kr / (2 * (1 - kb)), -gc * kg / (2 * (1 - kb)), gc * 0.5],
+                      [gc * 0.5, -gc * kg / (2 * (1 - kr)), -gc * kb / (2 * (1 - kr))]], dtype=np.float64)
+        o = np.array([oy, oc, oc], dtype=np.float64)
+    else:
+        A = np.array([[1 / gy, 0.0, 2 * (1 - kr) / gc],
+                      [1 / gy, -2 * (1 - kb) * kb / kg / gc, -2 * (1 - kr) * kr / kg / gc],
+                      [1 / gy, 2 * (1 - kb) / gc, 0.0]], dtype=np.float64)
+        o = -A @ np.array([oy, oc, oc], dtype=np.float64)
+    return np.concatenate([A.reshape(-1), o]).astype(dtype)
+
+
+def read_clip_yuv(path: str, shape: Tuple[int, int], fmt: str) -> np.ndarray:
+    """A headerless 4:2:0 clip (`ffmpeg -f rawvideo -pix_fmt <fmt>`) as uint8 [T, frame_bytes]; `shape` = (H, W)."""
+    fb = yuv_frame_bytes(fmt, shape[0], shape[1])
+    a = np.fromfile(path, dtype=np.uint8)
+    if a.size == 0 or a.size % fb:
+        raise ValueError(f"{path}: {a.size} bytes is not a whole number of {fmt} frames of {shape[0]}x{shape[1]} ({fb} bytes each)")
+    return a.reshape(-1, fb)
+
+
+def _coef12(coef12) -> np.ndarray:
+    c = np.ascontiguousarray(np.asarray(coef12, dtype=np.float32).reshape(-1))
+    if c.size != 12:
+        raise ValueError(f"expected 12 coefficients (3x3 matrix, 3 offsets), got {c.size}")
+    return c
+
+
+@L.on_device
+def yuv_ingest(frames: torch.Tensor, shape: Tuple[int, int], fmt: str, coef12, siting: str = "left", lr_shape: Optional[Tuple[int, int]] = None,
+               want_hr: bool = False, lr_out: Optional[torch.Tensor] = None):
+    """The low-level call (vsr_yuv_ingest) with any 12 coefficients: uint8 [..., frame_bytes] on the device -> float32 RGB
+    (lr [..., h, w, 3], hr [..., H, W, 3] | None); `lr_shape` = (h, w), default the full size; `lr_out`: write lr there."""
+    import ctypes
+    H, W = int(shape[0]), int(shape[1])
+    fb = yuv_frame_bytes(fmt, H, W)
+    if frames.dtype != torch.uint8 or frames.dim() < 1 or frames.shape[-1] != fb:
+        raise ValueError(f"expected uint8 [..., {fb}] ({fmt} {H}x{W}), got {frames.dtype} {tuple(frames.shape)}")
+    h, w = (H, W) if lr_shape is None else (int(lr_shape[0]), int(lr_shape[1]))
+    lead = tuple(frames.shape[:-1])
+    F = int(np.prod(lead)) if lead else 1
+    c = _coef12(coef12)
+    lr = torch.empty(lead + (h, w, 3), dtype=torch.float32, device=frames.device) if lr_out is None else lr_out
+    if tuple(lr.shape) != lead + (h, w, 3):
+        raise ValueError(f"lr_out must be {lead + (h, w, 3)}, got {tuple(lr.shape)}")
+    hr = torch.empty(lead + (H, W, 3), dtype=torch.float32, device=frames.device) if want_hr else None
+    Y = L.load_yuv()
+    L.check(Y.vsr_yuv_ingest(L.dptr(frames, torch.uint8), YUV_FORMATS[fmt], c.ctypes.data_as(ctypes.c_void_p), YUV_SITINGS[siting], L.dptr(lr),
+                             L.optr(hr), F, H, W, h, w, L.stream()), "yuv_ingest", lib=Y)
+    return lr, hr
+
+
+@L.on_device
+def yuv_write(frames: torch.Tensor, fmt: str, coef12, siting: str = "left", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The low-level call (vsr_yuv_write) with any 12 coefficients: float32 [..., H, W, 3] -> uint8 [..., frame_bytes]."""
+    import ctypes
+    if frames.dim() < 3 or frames.shape[-1] != 3:
+        raise ValueError(f"expected float32 [..., H, W, 3], got {tuple(frames.shape)}")
+    f = frames.detach().to(torch.float32).contiguous()
+    H, W = int(f.shape[-3]), int(f.shape[-2])
+    fb = yuv_frame_bytes(fmt, H, W)
+    lead = tuple(f.shape[:-3])
+    F = int(np.prod(lead)) if lead else 1
+    c = _coef12(coef12)
+    if out is None:
+        out = torch.empty(lead + (fb,), dtype=torch.uint8, device=f.device)
+    elif tuple(out.shape) != lead + (fb,):
+        raise ValueError(f"out must be {lead + (fb,)}, got {tuple(out.shape)}")
+    Y = L.load_yuv()
+    L.check(Y.vsr_yuv_write(L.dptr(f), L.dptr(out, torch.uint8), YUV_FORMATS[fmt], c.ctypes.data_as(ctypes.c_void_p), YUV_SITINGS[siting],
+                            F, H, W, L.stream()), "yuv_write", lib=Y)
+    return out
+
+
+def ingest_item_yuv(frames: torch.Tensor, shape: Tuple[int, int], fmt: str, scale: int = 4, want_hr: bool = True, matrix: str = "bt709",
+                    full_range: bool = False, siting: str = "left"):
+    """`ingest_item` for 4:2:0 frames: uint8 [T,3,frame_bytes] on the device -> (data [T,3,H//s,W//s,3], target [T,1,H,W,3] | None,
+    high_frames [T,3,H,W,3] | None), float32 R'G'B' in 0..255."""
+    if frames.dim() != 3 or frames.shape[1] != 3:
+        raise ValueError(f"expected uint8 [T,3,frame_bytes], got {frames.dtype} {tuple(frames.shape)}")
+    H, W = shape
+    lr, hr = yuv_ingest(frames.contiguous(), shape, fmt, yuv_coefficients(fmt, matrix, full_range, inverse=True), siting,
+                        (int(H / scale), int(W / scale)), want_hr)
+    if hr is None:
+        return lr, None, None
+    return lr, hr[:, 1:2].clone(), hr   # (the clone: as in ingest_item)
+
+
+def frames_to_yuv(frames: torch.Tensor, fmt: str, matrix: str = "bt709", full_range: bool = False, siting: str = "left") -> torch.Tensor:
+    """float32 HR frames [...,H,W,3] (R'G'B' in 0..255) -> packed 4:2:0 frames uint8 [...,frame_bytes]: values clamped to 0..255, chroma
+    from the filtered R'G'B', round half to even, clamped to the code range."""
+    return yuv_write(frames, fmt, yuv_coefficients(fmt, matrix, full_range), siting)
+
+
 # ------------------------------------------------------------------------------------------------ the per-item loop
 def run_item(model, data, target, high_frames, train: bool = False, estimated_image=None):
     """main.py:196-203 for one dataset item: windows in order, the output of one fed back as the next `estimated_image`.
@@ -136,6 +276,110 @@ def run_item(model, data, target, high_frames, train: bool = False, estimated_im
             if loss is not None:
                 losses.append(loss.data)
     return torch.stack(outs), losses, estimated_image
+
+
+class ClipRunner:
+    """A 4:2:0 clip streamed through `model` frame by frame.  `shape` = (H, W) of the source frames in `fmt_in`; the model sees them
+    decimated by `scale_down` (1: as they are) and returns frames of (S * (H // scale_down), S * (W // scale_down)), written out as
+    `fmt_out`.  `run(frames)`: host array [T, frame_bytes] -> host array [T-2, out_frame_bytes] (one frame per 3-frame window).
+
+    Per source frame: one upload from one of two pinned slots on the copy-in stream, one conversion into a slot of a three-slot LR
+    ring; per window: the ring's slots stacked on the device, `model(x, None, None, est, train=False)` on the current stream with the
+    estimate fed back (as `run_item`), `frames_to_yuv`'s kernel into one of two device slots, the copy back into one of two pinned
+    slots on the copy-out stream.  Events order every reuse of a slot; the host waits on events only, never on the device.
+    `overlap=False`: both copy streams ARE the current stream -- the same work in one stream's order (the cross-check).
+    `h2d_bytes`, `d2h_bytes`, `frames_in`, `frames_out` count what the last `run()` moved (reset when a run starts)."""
+
+    def __init__(self, model, shape: Tuple[int, int], fmt_in: str, fmt_out: str, scale_down: int = 1, overlap: bool = True,
+                 matrix: str = "bt709", full_range: bool = False, siting: str = "left"):
+        self.model, self.fmt_in, self.fmt_out, self.overlap, self.siting = model, fmt_in, fmt_out, bool(overlap), siting
+        H, W = int(shape[0]), int(shape[1])
+        self.shape = (H, W)
+        self.lr_shape = (int(H / scale_down), int(W / scale_down))
+        S = int(model.model.upscale_factor)
+        self.out_shape = (S * self.lr_shape[0], S * self.lr_shape[1])
+        self.in_bytes = yuv_frame_bytes(fmt_in, H, W)
+        self.out_bytes = yuv_frame_bytes(fmt_out, *self.out_shape)
+        self.coef_in = yuv_coefficients(fmt_in, matrix, full_range, inverse=True)
+        self.coef_out = yuv_coefficients(fmt_out, matrix, full_range)
+        self.device = next(model.parameters()).device
+        dev = self.device
+        self._pin_in = [torch.empty(self.in_bytes, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+        self._pin_out = [torch.empty(self.out_bytes, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+        self._dev_in = [torch.empty(self.in_bytes, dtype=torch.uint8, device=dev) for _ in range(2)]
+        self._dev_out = [torch.empty(self.out_bytes, dtype=torch.uint8, device=dev) for _ in range(2)]
+        self._ring = [torch.empty(self.lr_shape + (3,), dtype=torch.float32, device=dev) for _ in range(3)]
+        self._s_in = torch.cuda.Stream(dev) if self.overlap else None
+        self._s_out = torch.cuda.Stream(dev) if self.overlap else None
+        self.h2d_bytes = self.d2h_bytes = self.frames_in = self.frames_out = 0   # of the last run()
+
+    @property
+    def h2d_bytes_per_frame(self) -> float:
+        return self.h2d_bytes / max(self.frames_in, 1)
+
+    def run(self, frames: np.ndarray) -> np.ndarray:
+        frames = np.asarray(frames)
+        if frames.dtype != np.uint8 or frames.ndim != 2 or frames.shape[1] != self.in_bytes or frames.shape[0] < 3:
+            raise ValueError(f"expected uint8 [T >= 3, {self.in_bytes}], got {frames.dtype} {frames.shape}")
+        T = frames.shape[0]
+        out = np.empty((T - 2, self.out_bytes), dtype=np.uint8)
+        self.h2d_bytes = self.d2h_bytes = self.frames_in = self.frames_out = 0
+        with torch.cuda.device(self.device), torch.no_grad():
+            main = torch.cuda.current_stream(self.device)
+            s_in, s_out = (self._s_in, self._s_out) if self.overlap else (main, main)
+            uploaded = [None, None]    # per input slot: the upload from its pinned buffer has finished (event on s_in)
+            converted = [None, None]   # per input slot: the conversion has read its device buffer (event on main)
+            copied = [None, None]      # per output slot: (frame index, event on s_out: the copy into its pinned buffer has finished)
+            est = None
+            for i in range(T):
+                a = i % 2
+                if uploaded[a] is not None:
+                    uploaded[a].synchronize()   # the pinned slot is free again (host wait on one event)
+                self._pin_in[a].numpy()[:] = frames[i]
+                if converted[a] is not None:
+                    s_in.wait_event(converted[a])
+                with torch.cuda.stream(s_in):
+                    self._dev_in[a].copy_(self._pin_in[a], non_blocking=True)
+                    uploaded[a] = torch.cuda.Event()
+                    uploaded[a].record(s_in)
+                self.h2d_bytes += self.in_bytes
+                self.frames_in += 1
+                main.wait_event(uploaded[a])
+                # (ring slot i % 3 was last read by the window of frames i-3 .. i-1, stacked on this stream)
+                yuv_ingest(self._dev_in[a], self.shape, self.fmt_in, self.coef_in, self.siting, self.lr_shape, lr_out=self._ring[i % 3])
+                converted[a] = torch.cuda.Event()
+                converted[a].record(main)
+                if i < 2:
+                    continue
+                j = i - 2          # the output frame
+                b = j % 2
+                x = torch.stack([self._ring[(i - 2) % 3], self._ring[(i - 1) % 3], self._ring[i % 3]])
+                est, _ = self.model(x, None, None, est, train=False)
+                if copied[b] is not None:   # frame j-2 leaves the slot pair: wait for its copy, take it from the pinned buffer
+                    jj, ev = copied[b]
+                    ev.synchronize()
+                    out[jj] = self._pin_out[b].numpy()
+                    main.wait_event(ev)
+                yuv_write(est[0], self.fmt_out, self.coef_out, self.siting, out=self._dev_out[b])
+                ready = torch.cuda.Event()
+                ready.record(main)
+                s_out.wait_event(ready)
+                with torch.cuda.stream(s_out):
+                    self._pin_out[b].copy_(self._dev_out[b], non_blocking=True)
+                    ev = torch.cuda.Event()
+                    ev.record(s_out)
+                copied[b] = (j, ev)
+                self.d2h_bytes += self.out_bytes
+                self.frames_out += 1
+            for b in range(2):
+                if copied[b] is not None:
+                    jj, ev = copied[b]
+                    ev.synchronize()
+                    out[jj] = self._pin_out[b].numpy()
+            for ev in uploaded + converted:   # the slots are idle when run() returns
+                if ev is not None:
+                    ev.synchronize()
+        return out
 
 
 # ------------------------------------------------------------------------------------------------ checkpoints
@@ -210,6 +454,30 @@ def run_c1(lr: int = 128, frames: int = 3, scale: int = 4, precision: str = "fp3
     return line, model, datas, outs
 
 
+def run_c1_yuv(pix_fmt: str, lr: int = 128, frames: int = 3, scale: int = 4, precision: str = "fp32"):
+    """Config C1 with a 4:2:0 boundary: the synthetic clip as `pix_fmt` frames on the host, streamed through `ClipRunner`
+    (decimated by `scale`, super-resolved by `scale`).  -> (result line, output frames uint8 [T-2, frame_bytes] on the host)."""
+    import time
+    from . import VSR
+    from .weights import fill_module_
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    S = scale
+    model = fill_module_(VSR(upscale_factor=S).eval(), seed=0).to(dev)
+    model.precision = model.model.precision = precision
+    video = synthetic_video(frames, S * lr, S * lr)
+    clip = frames_to_yuv(torch.from_numpy(video).to(dev).float(), pix_fmt).cpu().numpy()
+    runner = ClipRunner(model, (S * lr, S * lr), pix_fmt, pix_fmt, scale_down=S)
+    runner.run(clip)                                                      # warm-up (packing, allocator)
+    t0 = time.perf_counter()
+    out = runner.run(clip)
+    dt = time.perf_counter() - t0
+    line = dict(config=f"C1: {frames}-frame {lr}x{lr} LR synthetic clip, x{S}, {pix_fmt} in and out, streamed clip runner, GPU path",
+                precision=precision, windows=frames - 2, frames_per_s=round((frames - 2) / dt, 3), out_shape=list(out.shape),
+                h2d_bytes_per_frame=runner.in_bytes, d2h_bytes_per_frame=runner.out_bytes)
+    return line, out
+
+
 def main(argv=None):
     import argparse
     import json
@@ -218,8 +486,13 @@ def main(argv=None):
     ap.add_argument("--frames", type=int, default=3, help="frames of the clip (3 = one window)")
     ap.add_argument("--scale", type=int, default=4, choices=[2, 3, 4], help="4 = the reference's geometry; 2 = C1's label")
     ap.add_argument("--precision", default="fp32", choices=["fp16", "fp32"])
+    ap.add_argument("--pix-fmt", default=None, choices=sorted(YUV_FORMATS),
+                    help="the clip enters and leaves as 4:2:0 frames of this format through ClipRunner (default: the RGB path)")
     args = ap.parse_args(argv)
-    line, _, _, _ = run_c1(args.lr, args.frames, args.scale, args.precision)
+    if args.pix_fmt is not None:
+        line, _ = run_c1_yuv(args.pix_fmt, args.lr, args.frames, args.scale, args.precision)
+    else:
+        line, _, _, _ = run_c1(args.lr, args.frames, args.scale, args.precision)
     print(json.dumps(line))
 
 
