@@ -13,6 +13,8 @@ This module holds
     `BudgetError` names the offending coordinate: a case outside its budget is a mistake in the test, never a reason for a tolerance),
   * float64 references of the train step's GRADIENTS by autograd over the same stock operators (`grads_ref`, `prelu_grads_ref`,
     `mlp_grads_ref`), every backward sum under the same budget,
+  * the trunk glue: `osvos_head_ref` (OSVOS's four transposed convolutions, crops, concat and fuse as stock float64 operators, the budget
+    of the FOLDED sum the kernel forms checked) and `nearest_resize_ref` (pure data movement: ATen's float32 nearest resize on the CPU),
   * `assert_exact` / `diff_mask` / `bbox`, which report the number of differing elements, the first one and their bounding box.
 
 The sign of a zero is not compared (`-0.0 == +0.0`): `0 * negative` in a PReLU with slope 0 is -0.0 in one formulation and +0.0 in
@@ -399,6 +401,75 @@ def mlp_grads_ref(planes, fc, go, live=True):
         check_sum_budget(torch.einsum("cyx,jcyx->j", ago, hid.detach()), g_go * g_hid, "fusion MLP dw2")
         check_sum_budget(ago.sum().reshape(1), g_go, "fusion MLP db2")
     return grads
+
+
+# ---------------------------------------------------------------------------------------------------------------- the trunk glue
+def osvos_sizes(h, w, nbranch=4):
+    """Side-map sizes of an h x w frame: MaxPool2d(2, 2, ceil_mode=True) once per VGG stage, branch b behind b + 1 of them."""
+    out = []
+    for _ in range(nbranch):
+        h, w = (h + 1) // 2, (w + 1) // 2
+        out.append((h, w))
+    return out
+
+
+def osvos_head_ref(sides, up_w, fuse_w, bias, hw, dweff=None, live=True):
+    """OSVOS's head in float64 as vos.OSVOS.forward words it: per branch F.conv_transpose2d(side_b, up_b, stride = k_b / 2) -> centre crop
+    to hw (vos._center_crop) -> cat -> F.conv2d with the fuse row + bias.  sides [N,16,hs_b,ws_b], up_w [16 (in),16 (out),k_b,k_b], fuse_w
+    [16 nb], bias a number -> [N,1,h,w].
+    The kernel does not evaluate that composition: it sums side * weff over 2 x 2 source pixels x 16 channels per branch, with
+    weff_b[ci][ky][kx] = sum_co fuse[16 b + co] * up_b[ci][co][ky][kx] stored as fp16.  So the budget is the folded sum's: every side
+    value and every folded weight an fp16 value, and sum |side| |weff| + |bias| (the folded weights as 16 -> 1 transposed convolutions of
+    |side|, cropped alike) below 2^24 granularities.
+    `dweff`: per branch None or a [16,1,k_b,k_b] term ADDED to the folded weight (a planted defect): its own transposed convolution is
+    added to the result and enters both budget checks."""
+    from video_super_resolution_amd.vos import _center_crop
+    _threads()
+    h, w = hw
+    nb = len(sides)
+    assert len(up_w) == nb and fuse_w.numel() == 16 * nb
+    ups, mags, gran = [], [], granularity(torch.tensor([float(bias)], dtype=torch.float64))
+    extra = torch.zeros((sides[0].shape[0], 1, h, w), dtype=torch.float64)
+    for b in range(nb):
+        s = up_w[b].shape[-1] // 2
+        assert tuple(up_w[b].shape) == (16, 16, 2 * s, 2 * s) and sides[b].shape[1] == 16
+        check_storable(sides[b], torch.float16, f"side map {b}")
+        ups.append(_center_crop(F.conv_transpose2d(sides[b], up_w[b], stride=s), h, w))
+        weff = torch.einsum("iokl,o->ikl", up_w[b], fuse_w[16 * b:16 * b + 16]).unsqueeze(1)      # [16,1,k,k]: for the budget only
+        if dweff is not None and dweff[b] is not None:
+            extra = extra + _center_crop(F.conv_transpose2d(sides[b], dweff[b], stride=s), h, w)
+            weff = weff + dweff[b]
+        check_storable(weff, torch.float16, f"folded weight of branch {b}")
+        mags.append(_center_crop(F.conv_transpose2d(sides[b].abs(), weff.abs(), stride=s), h, w))
+        gran = min(gran, granularity(sides[b]) * granularity(weff))
+        if tuple(ups[-1].shape[2:]) != (h, w):
+            raise BudgetError(f"branch {b}: a {tuple(sides[b].shape[2:])} side map upsamples to less than {h}x{w}")
+    check_sum_budget(sum(mags) + abs(float(bias)), gran, "OSVOS head")
+    out = F.conv2d(torch.cat(ups, 1), fuse_w.reshape(1, 16 * nb, 1, 1), torch.tensor([float(bias)], dtype=torch.float64)) + extra
+    if live:
+        check_live(out, "OSVOS head sum", min_distinct=50)
+    return check_storable(out, torch.float32, "OSVOS logit")
+
+
+def nearest_resize_ref(x, size):
+    """F.interpolate(x, size) in its default mode (nearest) on the CPU in FLOAT32: pure data movement, so the values come back in x's
+    dtype unchanged.  float32 on purpose: ATen forms the source index as floor(dst * (in / out)) in the tensor's compute type, which is
+    what the kernels restate; at some sizes (26 -> 22, 14 -> 46, 21 -> 69 among them) that is not the rational floor(dst * in / out), and
+    an operator computing its scale in double need not agree either.  x [N,C,H,W]."""
+    y = F.interpolate(x.detach().cpu().to(torch.float32), size=tuple(size))
+    return y.to(x.dtype)
+
+
+def nearest_sources(n_in, n_out, dtype=torch.float32):
+    """The source index per destination index that ATen's nearest resize picks along one axis, read off the operator itself."""
+    ramp = torch.arange(n_in, dtype=dtype).view(1, 1, n_in, 1)
+    return F.interpolate(ramp, size=(n_out, 1))[0, 0, :, 0].long()
+
+
+def nearest_differs_from_rational(n_in, n_out):
+    """True where the float32 operator's source differs from floor(dst * n_in / n_out) in integers, at one destination or more."""
+    exact = (torch.arange(n_out, dtype=torch.int64) * n_in) // n_out
+    return bool((nearest_sources(n_in, n_out) != exact).any())
 
 
 # ---------------------------------------------------------------------------------------------------------------- comparison

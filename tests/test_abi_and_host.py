@@ -62,6 +62,44 @@ def test_conv_launcher_refuses_an_image_beyond_its_32_bit_offsets():
     assert rc == -1 and b"4 GiB" in lib.vsr_last_error()
 
 
+def test_osvos_fuse_refuses_bad_branch_lists_before_any_launch():
+    """vsr_osvos_fuse_f16: 0 or 5 branches, a leading dimension of 12, a branch whose upsampled size (hs + 1) s is below the output -- each
+    is VSR_E_ARG with its own text (a launch would have returned 0 or VSR_E_LAUNCH)."""
+    lib = _lib.load()
+    vp, ip = ctypes.c_void_p * 5, ctypes.c_int * 5
+    ptrs, out = vp(*[0x1000] * 5), ctypes.c_void_p(0x1000)   # never dereferenced on the host
+    hs, ws, st = ip(9, 5, 3, 2, 1), ip(17, 9, 5, 3, 2), ip(2, 4, 8, 16, 32)
+
+    def call(nb, ld=16, h=17, w=33, hs=hs):
+        return lib.vsr_osvos_fuse_f16(ptrs, hs, ws, ld, ptrs, st, nb, ctypes.c_float(0.0), out, 2, h, w, None)
+    for nb in (0, 5):
+        assert call(nb) == -1 and b"osvos_fuse: bad arguments" in lib.vsr_last_error()
+    assert call(4, ld=12) == -1 and b"osvos_fuse: bad arguments" in lib.vsr_last_error()
+    assert call(4, hs=ip(9, 3, 3, 2, 1)) == -1 and b"branch 1 upsamples to 16x40 < 17x33" in lib.vsr_last_error()
+    assert call(4, w=37) == -1 and b"branch 0 upsamples to 20x36 < 17x37" in lib.vsr_last_error()
+
+
+def test_resize_add_segs_refuses_bad_segment_lists_before_any_launch():
+    """vsr_resize_add_segs_nhwc_f16: an upsampled addend with an odd output size or without an addend, 5 segments, a segment width that is
+    not a multiple of 8, a channel offset beyond the leading dimension -- each is VSR_E_ARG with its own text, nothing launched."""
+    lib = _lib.load()
+    vp, ip = ctypes.c_void_p * 5, ctypes.c_int * 5
+    ptrs, out = vp(*[0x1000] * 5), ctypes.c_void_p(0x1000)
+
+    def call(a_nseg=2, b_nseg=2, b_up2=0, H=10, W=12, C=32, a_lds=ip(*[24] * 5), a_coffs=ip(*[8] * 5), b_lds=ip(*[40] * 5), b_coffs=ip(*[16] * 5)):
+        return lib.vsr_resize_add_segs_nhwc_f16(ptrs, a_lds, a_coffs, a_nseg, 5, 6, 0, ptrs if b_nseg else None, b_lds if b_nseg else None,
+                                                b_coffs if b_nseg else None, b_nseg, b_up2, out, 1, H, W, C, None)
+    for kw in (dict(b_up2=1, H=11), dict(b_up2=1, W=13), dict(b_up2=1, b_nseg=0)):
+        assert call(**kw) == -1 and b"resize_add_segs: up2 flags" in lib.vsr_last_error(), kw
+    for kw in (dict(a_nseg=5), dict(b_nseg=5)):
+        assert call(**kw) == -1 and b"resize_add_segs: bad segment lists" in lib.vsr_last_error(), kw
+    for kw in (dict(a_nseg=4, C=48), dict(b_nseg=4, C=48), dict(a_nseg=1, b_nseg=1, C=20)):
+        assert call(**kw) == -1 and b"multiple of 8" in lib.vsr_last_error(), kw
+    assert call(a_coffs=ip(8, 16, 8, 8, 8)) == -1 and b"resize_add_segs: segment 1 of a" in lib.vsr_last_error()      # 16 + 16 > 24
+    assert call(b_coffs=ip(32, 16, 16, 16, 16)) == -1 and b"resize_add_segs: segment 0 of b" in lib.vsr_last_error()  # 32 + 16 > 40
+    assert call(a_lds=ip(24, 24, 24, 24, 24), a_coffs=ip(8, 32, 8, 8, 8)) == -1 and b"segment 1 of a" in lib.vsr_last_error()  # coff beyond ld
+
+
 def test_sr_state_dict_has_the_reference_layout(cpu_vsr):
     sd = cpu_vsr.model.state_dict()
     expect = {"sub_mean.weight": (3, 3, 1, 1), "conv_in.0.weight": (128, 3, 3, 3), "conv_in.1.weight": (1,),

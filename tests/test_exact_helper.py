@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import _exact as E
+import _glue_cases as G
 
 
 # ------------------------------------------------------------------------------------------------ int64 restatements
@@ -562,3 +563,178 @@ def test_mlp_grads_ref_budget_checks_fire():
     big = torch.full_like(go, 2.0 ** 19) + 1.0                                  # 63 pixels x 2^19 > 2^24: the sum over pixels alone
     with pytest.raises(E.BudgetError, match="fusion MLP d"):
         E.mlp_grads_ref(planes, (w1, b1, w2, b2 + 500.0), big, live=False)
+
+
+# ------------------------------------------------------------------------------------------------ the trunk glue (tests/_glue_cases.py)
+
+def test_osvos_fold_equals_a_plain_loop_for_non_symmetric_weights():
+    """weff_b[ky][kx][ci] = sum_co fuse[16 b + co] * up_b[ci][co][ky][kx], tap by tap in int64: an (in, out) swap in the einsum, a fuse
+    row read at the wrong branch or a transposed tap would change it (the weights are dense and not symmetric)."""
+    from video_super_resolution_amd.trunk_exec import osvos_fold
+    c = G.gen_osvos(17, 33)
+    got = osvos_fold([u.float() for u in c["up_w"]], c["fuse_w"].float().view(1, 64, 1, 1))
+    fuse = _i(c["fuse_w"])
+    for b, u in enumerate(c["up_w"]):
+        u, k = _i(u), u.shape[-1]
+        assert not np.array_equal(u, u.transpose(1, 0, 2, 3))
+        want = np.zeros((k, k, 16), dtype=np.int64)
+        for ci in range(16):
+            for co in range(16):
+                for ky in range(k):
+                    for kx in range(k):
+                        want[ky, kx, ci] += fuse[16 * b + co] * u[ci, co, ky, kx]
+        assert got[b].dtype == torch.float16 and tuple(got[b].shape) == (k, k, 16) and got[b].is_contiguous()
+        assert np.array_equal(got[b].double().numpy(), want.astype(np.float64)), b
+        swapped = np.einsum("oikl,o->kli", u, fuse[16 * b:16 * b + 16])
+        assert not np.array_equal(swapped, want)
+
+
+@pytest.mark.parametrize("case", [c for c in G.OSVOS_CASES if c[2] == 16 or c[:2] not in G.OSVOS_GEOMS], ids=str)
+def test_osvos_cases_are_inside_their_budget_and_equal_an_int64_scatter(case):
+    """Every geometry of the GPU test: the reference runs (its budget checks pass) and equals a tap-by-tap int64 scatter of the transposed
+    convolutions, cropped with slices worked out here."""
+    h, w, _, nb = case
+    c = G.gen_osvos(h, w, nb)
+    ref = G.osvos_ref(c)
+    assert E.osvos_sizes(h, w, nb) == [tuple(s.shape[2:]) for s in c["sides"]]
+    cat = []
+    for b, s in enumerate(c["strides"]):
+        full = deconv_i64(_i(c["sides"][b]), _i(c["up_w"][b]), None, s, 0)
+        dh, dw = full.shape[2] - h, full.shape[3] - w
+        assert dh >= 0 and dw >= 0
+        cat.append(full[:, :, dh // 2:dh // 2 + h, dw // 2:dw // 2 + w])
+    want = np.einsum("nchw,c->nhw", np.concatenate(cat, 1), _i(c["fuse_w"])) + int(c["bias"])
+    assert np.array_equal(_i(ref)[:, 0], want)
+
+
+def test_osvos_crop_offsets_take_both_parities_where_they_can():
+    """The seven geometries between them: the crop excess (hs + 1) s - h odd and even in every branch, in rows and in columns (odd: the
+    spare pixel goes at the bottom / right); the offset excess // 2 odd and even in branches 1..3 -- in branch 0 (s = 2, hs = ceil(h / 2))
+    the excess is 2 or 3 and the offset 1 at every size; a side map of one row (2 x 3) and, in the added 33 x 1 case, of one column."""
+    off = {(b, ax): set() for b in range(4) for ax in (0, 1)}
+    exc = {(b, ax): set() for b in range(4) for ax in (0, 1)}
+    one = set()
+    for h, w in G.OSVOS_GEOMS + [(33, 1)]:
+        for b, (hs, ws) in enumerate(E.osvos_sizes(h, w)):
+            s = G.OSVOS_STRIDES[b]
+            if (h, w) == (33, 1):                                    # (the one-column side maps of more than one row)
+                one |= {"col"} if ws == 1 and hs > 1 else set()
+                continue
+            for ax, e in enumerate(((hs + 1) * s - h, (ws + 1) * s - w)):
+                exc[(b, ax)].add(e & 1)
+                off[(b, ax)].add((e // 2) & 1 if b else e // 2)
+            one |= {"row"} if hs == 1 and ws > 1 else set()
+    assert all(v == {0, 1} for v in exc.values()), exc
+    assert all(v == ({0, 1} if b else {1}) for (b, _), v in off.items()), off
+    assert one == {"row", "col"}
+
+
+def test_osvos_head_budget_checks_fire():
+    c = G.gen_osvos(17, 33)
+    fuse = c["fuse_w"].clone()
+    fuse[0] = 4097.0                                                 # folded weights 4097 u + a few units: not multiples of 4
+    big = dict(c, fuse_w=fuse)
+    with pytest.raises(E.BudgetError, match="folded weight of branch"):
+        G.osvos_ref(big)
+    half = [s.clone() for s in c["sides"]]
+    half[2][1, 4, 0, 0] = 0.3
+    with pytest.raises(E.BudgetError, match="side map 2"):
+        G.osvos_ref(dict(c, sides=half))
+    wide = dict(c, sides=[s * 4096.0 for s in c["sides"]])          # fp16 values still, the sum is not below 2^24
+    with pytest.raises(E.BudgetError, match="OSVOS head"):
+        G.osvos_ref(wide)
+    with pytest.raises(E.BudgetError, match="upsamples to less"):
+        E.osvos_head_ref(c["sides"], c["up_w"], c["fuse_w"], c["bias"], (40, 33), live=False)
+
+
+def test_osvos_planted_weight_defect_has_the_footprint_of_one_phase():
+    """One unit in one folded weight of branch 3 (tap (13, 20), channel 5) moves at most the pixels of one output phase: (y + oy) % 16 ==
+    13 rows, (x + ox) % 16 == 4 columns with the source column one to the left -- and only where the side value is not zero."""
+    h, w = 23, 47
+    c = G.gen_osvos(h, w)
+    d = torch.zeros((16, 1, 32, 32), dtype=torch.float64)
+    d[5, 0, 13, 20] = 1.0
+    moved = G.osvos_ref(c, dweff=[None, None, None, d]) != G.osvos_ref(c)
+    hs, ws = c["sides"][3].shape[2:]
+    oy, ox = ((hs + 1) * 16 - h) // 2, ((ws + 1) * 16 - w) // 2
+    ys, xs = torch.nonzero(moved)[:, 2], torch.nonzero(moved)[:, 3]
+    assert 0 < int(moved.sum()) < moved.numel()
+    assert bool((((ys + oy) % 16) == 13).all()) and bool((((xs + ox) % 16) == 4).all())
+
+
+@pytest.mark.parametrize("case", G.PAIRS_CASES[:-1], ids=lambda c: f"{c[1]}x{c[2]}-B{len(c[4])}")
+def test_pairs_reference_is_the_stock_composition(case):
+    """`pairs_ref` against models.py:74-79 in float64 stock operators (mean over both frames and all pixels; the division by 255): the
+    float32 restatement is within one float32 rounding of each of its two operations, and its layouts are the kernel's three outputs."""
+    c = G.gen_pairs(case)
+    r = G.pairs_ref(c)
+    y0, x0, H, W = c["crop"]
+    crop = torch.from_numpy(c["frames"]).double()[:, y0:y0 + H, x0:x0 + W]
+    inputs = torch.stack([torch.stack([crop[a], crop[b]]).permute(3, 0, 1, 2) for a, b in c["pairs"]])       # [B,3,2,H,W]
+    mean = inputs.contiguous().view(len(c["pairs"]), 3, -1).mean(-1).view(-1, 3, 1, 1, 1)
+    want = (inputs - mean) / 255.0
+    want = torch.cat((want[:, :, 0], want[:, :, 1]), 1).numpy()
+    assert np.abs(r["x"] - want).max() <= 2.0 ** -23                                                     # |x| <= 1: 3 half-ulps
+    assert np.array_equal(r["x6h"][..., :6], r["x"].astype(np.float16).transpose(0, 2, 3, 1)) and not r["x6h"][..., 6:].any()
+    assert not r["both4"][..., 3].any()
+
+
+def test_pairs_largest_case_is_inside_its_budget_and_beyond_the_grid_cap():
+    case = G.PAIRS_CASES[-1]
+    y0, x0, H, W = case[5]
+    assert H * W > 2048 * 256 and H % 4 == 0 and W % 4 == 0 and 2 * H * W * case[3] < 2 ** 24
+    assert (H, W) == min(((a, b) for a in range(4, 2048, 4) for b in (1020,) if a * b > 2048 * 256), key=lambda s: s[0] * s[1])
+    G.pairs_ref(G.gen_pairs(case))
+
+
+def test_pairs_budget_checks_fire():
+    c = G.gen_pairs(G.PAIRS_CASES[-1])
+    c["frames"] = c["frames"] * 3.0                                   # values up to 45: the sum passes 2^24
+    with pytest.raises(E.BudgetError, match="not below 2\\^24"):
+        G.pairs_ref(c)
+    c = G.gen_pairs(G.PAIRS_CASES[0])
+    c["frames"][0, 5, 5, 1] = 0.5
+    with pytest.raises(E.BudgetError, match="integers"):
+        G.pairs_ref(c)
+    c = G.gen_pairs(G.PAIRS_CASES[0])
+    c["crop"] = (10, 4, 12, 16)
+    with pytest.raises(E.BudgetError, match="leaves the frame"):
+        G.pairs_ref(c)
+
+
+@pytest.mark.parametrize("bilinear", [1, 0])
+@pytest.mark.parametrize("shape", G.WARP_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_warp_cases_are_dyadic_and_clamp_on_every_side(shape, bilinear):
+    """Every case of the GPU test: the float64 upsampling is a float32 value (checked inside), the twelve channels are finite fp16 values,
+    and from 8 x 8 up the targets leave the image on all four sides."""
+    B, H, W = shape
+    c, out16 = G.warp_ref(shape, bilinear)
+    assert out16.shape == (B, H, W, 16) and out16.dtype == np.float16 and np.isfinite(out16.astype(np.float32)).all()
+    assert not out16[..., 12:].any() and not out16.flags.writeable
+    flow = G.warp_flow_ref(c, bilinear)
+    assert np.array_equal(out16[..., :6], c["x6"].numpy().transpose(0, 2, 3, 1).astype(np.float16))
+    if H >= 8 and W >= 8:
+        assert all(G.warp_leaves_every_side(flow, H, W))
+    if bilinear and H >= 8:
+        assert len(np.unique(flow)) > 16           # the lerp is live: values between the grid's own
+
+
+def test_warp_budget_checks_fire():
+    c = G.gen_warp((1, 8, 8))
+    c["q"] = c["q"] + 2.0 ** -20                                      # no longer multiples of 1/8: float32 lerps would round
+    with pytest.raises(E.BudgetError):
+        G.warp_flow_ref(c, 1)
+    c = G.gen_warp((1, 8, 8))
+    c["q"] = c["q"] * 4.0                                            # beyond 2: x 20 leaves the stated range
+    with pytest.raises(E.BudgetError, match="beyond 40"):
+        G.warp_flow_ref(c, 0)
+
+
+@pytest.mark.parametrize("sizes", [(26, 22), (14, 46), (21, 69)])
+def test_nearest_resize_ref_differs_from_the_rational_index_where_the_cases_say(sizes):
+    n_in, n_out = sizes
+    assert E.nearest_differs_from_rational(n_in, n_out)
+    assert not E.nearest_differs_from_rational(13, 5) and not E.nearest_differs_from_rational(9, 4) and not E.nearest_differs_from_rational(7, 7)
+    x = torch.arange(n_in, dtype=torch.float16).view(1, 1, n_in, 1) + 0.5
+    got = E.nearest_resize_ref(x, (n_out, 1))
+    assert got.dtype == torch.float16 and torch.equal(got[0, 0, :, 0], E.nearest_sources(n_in, n_out).to(torch.float16) + 0.5)

@@ -547,6 +547,16 @@ class FlowNet2Exec:
 
 
 # ------------------------------------------------------------------------------------------------ OSVOS
+def osvos_fold(upscale_weights, fuse_weight):
+    """upscale (ConvTranspose2d 16->16, k = 2s, stride s) -> centre crop -> cat -> fuse 1x1 is linear: fold the fuse row into each
+    branch's transposed-conv kernel.  upscale_weights: [16 (in), 16 (out), k, k] per branch; fuse_weight: 16 entries per branch in
+    cat order (any shape).  -> [weff_b] fp16 [k][k][16 (in)], weff_b[ky][kx][ci] = sum_co fuse[16 b + co] * up_b[ci][co][ky][kx]
+    (csrc/conv_igemm.hip k_osvos_fuse)."""
+    fw = fuse_weight.detach().float().reshape(-1)
+    return [torch.einsum("iokl,o->kli", w.detach().float(), fw[16 * b:16 * b + 16]).contiguous().half()
+            for b, w in enumerate(upscale_weights)]
+
+
 class OSVOSExec:
     def __init__(self, net):
         self.stages = []
@@ -560,12 +570,8 @@ class OSVOSExec:
                                  HConv(m.weight, m.bias, pad=1, act=ACT_RELU))
             self.stages.append(items)
         self.side = [HConv(m.weight, m.bias, pad=1, act=ACT_NONE) for m in net.side_prep]
-        # upscale (ConvTranspose2d 16->16, k = 2s, stride s) -> centre crop -> cat -> fuse 1x1 is linear: fold the fuse
-        # row into each branch's transposed-conv kernel, weff[ky][kx][ci] (csrc/conv_igemm.hip k_osvos_fuse)
-        fw = net.fuse.weight.detach().float().view(-1)
         self.up_s = [m.stride[0] for m in net.upscale]
-        self.weff = [torch.einsum("iokl,o->kli", m.weight.detach().float(), fw[16 * b:16 * b + 16]).contiguous().half()
-                     for b, m in enumerate(net.upscale)]
+        self.weff = osvos_fold([m.weight for m in net.upscale], net.fuse.weight)
         self.fuse_b = float(net.fuse.bias.detach())
 
     @L.on_device
@@ -582,13 +588,23 @@ class OSVOSExec:
             if si > 0:   # side_prep: 16 channels, as a DENSE [N,h',w',16] map (full-line stores, see _Inception.dense_thin)
                 hs, ws = x.shape[1], x.shape[2]
                 sides.append(self.side[si - 1](x, out=torch.empty((N, hs, ws, 16), dtype=torch.float16, device=x.device)))
+        return self.fuse_sides(sides, hh, ww)
+
+    @L.on_device
+    @torch.no_grad()
+    def fuse_sides(self, sides, hh, ww):
+        """The side maps [N,hs_b,ws_b,ld] fp16 (channels 0..15 live, one `ld` for all) of the first len(sides) branches -> the fused
+        logit [N,1,hh,ww] float32 in one launch."""
         nb = len(sides)
-        out = torch.empty((N, 1, hh, ww), dtype=torch.float32, device=x.device)
+        N, ld = sides[0].shape[0], sides[0].shape[3]
+        if not 1 <= nb <= len(self.weff) or any(t.dim() != 4 or t.shape[0] != N or t.shape[3] != ld for t in sides):
+            raise L.VsrHipError("osvos_fuse: one [N,hs,ws,ld] side map per branch, the same N and ld for all")
+        out = torch.empty((N, 1, hh, ww), dtype=torch.float32, device=sides[0].device)
         vp = ctypes.c_void_p * nb
         ip = ctypes.c_int * nb
-        L.check(L.load().vsr_osvos_fuse_f16(vp(*[t.data_ptr() for t in sides]), ip(*[t.shape[1] for t in sides]),
-                                            ip(*[t.shape[2] for t in sides]), sides[0].shape[3], vp(*[t.data_ptr() for t in self.weff]),
-                                            ip(*self.up_s), nb, L.cf(self.fuse_b), L.dptr(out), N, hh, ww, L.stream()), "osvos_fuse")
+        L.check(L.load().vsr_osvos_fuse_f16(vp(*[L.dptr(t, torch.float16).value for t in sides]), ip(*[t.shape[1] for t in sides]),
+                                            ip(*[t.shape[2] for t in sides]), ld, vp(*[L.dptr(t, torch.float16).value for t in self.weff[:nb]]),
+                                            ip(*self.up_s[:nb]), nb, L.cf(self.fuse_b), L.dptr(out), N, hh, ww, L.stream()), "osvos_fuse")
         return out
 
 
