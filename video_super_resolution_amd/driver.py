@@ -11,12 +11,15 @@ feeds it, on the GPU path and without OpenCV:
                             estimated_image); estimated_image = output` (main.py:196-203) -> HR frames (+ losses)
     frames_to_u8            HR write-out, float32 -> uint8 NHWC on the device (the step after the path; the reference never
                             writes its frames)
+    frame_metrics / psnr_ssim   HR frames scored against ground truth on the device: the float64 sums behind PSNR and SSIM per frame
+                            (include/vsr_hip_metric.h), and the host step that forms the two numbers from them
     read_clip_yuv / ingest_item_yuv / frames_to_yuv     the same three steps for what decoders emit: packed Y'CbCr 4:2:0 frames
                             (yuv420p, nv12, yuv420p10le, p010le), converted on the device (include/vsr_hip_yuv.h); the matrix
                             coefficients come from `yuv_coefficients` alone
     ClipRunner              a clip streamed through the model: every source frame uploaded once from pinned memory on a copy stream,
                             converted once into a three-slot LR ring, the window formed on the device, the HR frame written out as
-                            4:2:0 and copied back on a second copy stream
+                            4:2:0 and copied back on a second copy stream; `score=`: every output frame scored against the source
+                            frame it restores, from the upload already on the device
     save_checkpoint / load_checkpoint   utils/tools.py:68-73 and main.py:108-122,233-237: {'arch','epoch','state_dict':
                             SRmodel.model.state_dict(),'optimizer'} -- files interchange with the reference's
 
@@ -123,6 +126,83 @@ def frames_to_u8(frames: torch.Tensor) -> torch.Tensor:
     import ctypes
     L.check(L.load().vsr_frame_to_u8(L.dptr(f), L.dptr(out, torch.uint8), ctypes.c_size_t(f.numel()), L.stream()), "frame_to_u8")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ PSNR / SSIM
+METRIC_CHANNELS = {"rgb": 0, "y": 1}     # the `channels` codes of include/vsr_hip_metric.h
+METRIC_WHAT = {"psnr": 1, "ssim": 2}     # the bits of `what`: PSNR needs the SSE
+
+
+def ssim_window() -> np.ndarray:
+    """The normalised 1-D window of SSIM (Wang et al. 2004): 11 taps of exp(-(i - 5)^2 / (2 * 1.5^2)) over their sum, float64; the 2-D
+    window is its outer product."""
+    g = np.exp(-((np.arange(11, dtype=np.float64) - 5.0) ** 2) / (2.0 * 1.5 ** 2))
+    return g / g.sum()
+
+
+@L.on_device
+def frame_metrics(a: torch.Tensor, b: torch.Tensor, channels: str = "rgb", quantise: bool = True, shave: int = 0, what=("psnr", "ssim"),
+                  matrix: str = "bt601", full_range: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """float32 RGB frames `a`, `b` ([H,W,3], [1,H,W,3] or [F,H,W,3], 0..255) -> the device tensor [F,4] float64 of
+    {sse, n_sse, ssim_sum, n_ssim} per frame (vsr_metric_frames); nothing is synchronised, `psnr_ssim` is the host step.
+    `quantise`: score what write-out stores (clamp to 0..255, round half to even); `shave`: pixels dropped on every side;
+    `channels="y"`: on the luma of `matrix` / `full_range` (row 0 of `yuv_coefficients`; the default is BT.601 limited range, the
+    literature's "Y"); `what`: "psnr" and / or "ssim" (the slots of the other are 0); `out`: write the sums there ([F,4] float64)."""
+    import ctypes
+    if channels not in METRIC_CHANNELS:
+        raise ValueError(f"unknown channels {channels!r} (known: {', '.join(METRIC_CHANNELS)})")
+    names = (what,) if isinstance(what, str) else tuple(what)
+    if not names or any(n not in METRIC_WHAT for n in names):
+        raise ValueError(f"what must name 'psnr' and / or 'ssim', got {what!r}")
+    bits = 0
+    for n in names:
+        bits |= METRIC_WHAT[n]
+    if tuple(a.shape) != tuple(b.shape) or a.dim() not in (3, 4) or a.shape[-1] != 3:
+        raise ValueError(f"expected two float32 tensors of one shape [H,W,3] or [F,H,W,3], got {tuple(a.shape)} and {tuple(b.shape)}")
+    shave = int(shave)
+    H, W = int(a.shape[-3]), int(a.shape[-2])
+    F = int(a.shape[0]) if a.dim() == 4 else 1
+    if shave < 0 or 2 * shave >= min(H, W):
+        raise ValueError(f"shave {shave} leaves nothing of {H} x {W}")
+    if bits & 2 and min(H, W) - 2 * shave < 11:
+        raise ValueError(f"SSIM needs 11 pixels each way after the shave, got {min(H, W) - 2 * shave}")
+    luma4 = None
+    if channels == "y":
+        c = yuv_coefficients("yuv420p", matrix, full_range)
+        luma4 = np.ascontiguousarray(np.array([c[0], c[1], c[2], c[9]], dtype=np.float32))
+    win = ssim_window()
+    fa, fb = a.detach().contiguous(), b.detach().contiguous()
+    M = L.load_metric()
+    pa, pb = L.dptr(fa), L.dptr(fb)   # (raises on CPU tensors and on anything but float32)
+    if fb.device != fa.device:
+        raise ValueError("the two tensors live on different devices")
+    if out is None:
+        out = torch.empty((F, 4), dtype=torch.float64, device=fa.device)
+    elif tuple(out.shape) != (F, 4) or out.device != fa.device:
+        raise ValueError(f"out must be float64 {(F, 4)} on {fa.device}, got {tuple(out.shape)} on {out.device}")
+    ws = torch.empty(int(M.vsr_metric_ws_bytes(F, H, W, shave, bits)), dtype=torch.uint8, device=fa.device)
+    L.check(M.vsr_metric_frames(pa, pb, F, H, W, bits, METRIC_CHANNELS[channels], 1 if quantise else 0, shave,
+                                None if luma4 is None else luma4.ctypes.data_as(ctypes.c_void_p), win.ctypes.data_as(ctypes.c_void_p),
+                                L.dptr(out, torch.float64), L.dptr(ws, torch.uint8), L.stream()), "metric_frames", lib=M)
+    return out
+
+
+def psnr_ssim(sums) -> Tuple[np.ndarray, np.ndarray]:
+    """The host step after `frame_metrics`: sums [F,4] (a tensor, copied to the host here, or an array) -> (PSNR [F] in dB,
+    SSIM [F]).  PSNR = 10 log10(255^2 n_sse / sse), `inf` where sse == 0; SSIM = ssim_sum / n_ssim.  A metric that was not asked for
+    (its count is 0) comes back as NaN."""
+    s = sums.detach().cpu().numpy() if isinstance(sums, torch.Tensor) else np.asarray(sums)
+    s = np.asarray(s, dtype=np.float64).reshape(-1, 4)
+    sse, n_sse, ssim_sum, n_ssim = s[:, 0], s[:, 1], s[:, 2], s[:, 3]
+    psnr = np.full(s.shape[0], np.nan)
+    ssim = np.full(s.shape[0], np.nan)
+    on = n_sse > 0
+    psnr[on & (sse == 0)] = np.inf
+    pos = on & (sse > 0)
+    psnr[pos] = 10.0 * np.log10(255.0 ** 2 * n_sse[pos] / sse[pos])
+    on = n_ssim > 0
+    ssim[on] = ssim_sum[on] / n_ssim[on]
+    return psnr, ssim
 
 
 # ------------------------------------------------------------------------------------------------ Y'CbCr 4:2:0 in and out
@@ -288,16 +368,35 @@ class ClipRunner:
     estimate fed back (as `run_item`), `frames_to_yuv`'s kernel into one of two device slots, the copy back into one of two pinned
     slots on the copy-out stream.  Events order every reuse of a slot; the host waits on events only, never on the device.
     `overlap=False`: both copy streams ARE the current stream -- the same work in one stream's order (the cross-check).
-    `h2d_bytes`, `d2h_bytes`, `frames_in`, `frames_out` count what the last `run()` moved (reset when a run starts)."""
+    `h2d_bytes`, `d2h_bytes`, `frames_in`, `frames_out` count what the last `run()` moved (reset when a run starts).
+
+    `score="rgb" | "y"` (only where the output frame has the source's shape, `scale_down == S`): output frame j is scored against source
+    frame j + 1, the middle frame of its window (`target = datas[:, 1:2]` in the reference's loop), which is still resident in its
+    upload slot when the window runs: one more conversion at full size into a reused HR buffer and `frame_metrics` of the float
+    estimate (quantised as write-out does, `shave` pixels dropped on every side, default S; "y" is `frame_metrics`' BT.601 luma whatever
+    `matrix` the frames are coded with) into row j of one [T-2,4] tensor; nothing
+    extra is uploaded, and one copy at the end gives `metrics = {"psnr": [T-2], "ssim": [T-2]}`."""
 
     def __init__(self, model, shape: Tuple[int, int], fmt_in: str, fmt_out: str, scale_down: int = 1, overlap: bool = True,
-                 matrix: str = "bt709", full_range: bool = False, siting: str = "left"):
+                 matrix: str = "bt709", full_range: bool = False, siting: str = "left", score: Optional[str] = None,
+                 shave: Optional[int] = None):
         self.model, self.fmt_in, self.fmt_out, self.overlap, self.siting = model, fmt_in, fmt_out, bool(overlap), siting
         H, W = int(shape[0]), int(shape[1])
         self.shape = (H, W)
         self.lr_shape = (int(H / scale_down), int(W / scale_down))
         S = int(model.model.upscale_factor)
         self.out_shape = (S * self.lr_shape[0], S * self.lr_shape[1])
+        if score is not None and score not in METRIC_CHANNELS:
+            raise ValueError(f"score must be None, 'rgb' or 'y', got {score!r}")
+        if score is None and shave is not None:
+            raise ValueError("shave is given but nothing is scored (score=None)")
+        if score is not None and self.out_shape != self.shape:
+            raise ValueError(f"score={score!r} needs output frames of the source's shape: {self.shape} in, {self.out_shape} out "
+                             f"(scale_down {scale_down}, x{S})")
+        self.score, self.shave = score, (S if shave is None else int(shave))
+        if score is not None and (self.shave < 0 or min(self.shape) - 2 * self.shave < 11):
+            raise ValueError(f"shave {self.shave} leaves less than SSIM's 11 pixels of {self.shape}")
+        self.metrics = None   # of the last run(): {"psnr": [T-2], "ssim": [T-2]} when scoring
         self.in_bytes = yuv_frame_bytes(fmt_in, H, W)
         self.out_bytes = yuv_frame_bytes(fmt_out, *self.out_shape)
         self.coef_in = yuv_coefficients(fmt_in, matrix, full_range, inverse=True)
@@ -309,6 +408,7 @@ class ClipRunner:
         self._dev_in = [torch.empty(self.in_bytes, dtype=torch.uint8, device=dev) for _ in range(2)]
         self._dev_out = [torch.empty(self.out_bytes, dtype=torch.uint8, device=dev) for _ in range(2)]
         self._ring = [torch.empty(self.lr_shape + (3,), dtype=torch.float32, device=dev) for _ in range(3)]
+        self._truth = torch.empty(self.shape + (3,), dtype=torch.float32, device=dev) if score is not None else None
         self._s_in = torch.cuda.Stream(dev) if self.overlap else None
         self._s_out = torch.cuda.Stream(dev) if self.overlap else None
         self.h2d_bytes = self.d2h_bytes = self.frames_in = self.frames_out = 0   # of the last run()
@@ -324,7 +424,9 @@ class ClipRunner:
         T = frames.shape[0]
         out = np.empty((T - 2, self.out_bytes), dtype=np.uint8)
         self.h2d_bytes = self.d2h_bytes = self.frames_in = self.frames_out = 0
+        self.metrics = None
         with torch.cuda.device(self.device), torch.no_grad():
+            sums = torch.empty((T - 2, 4), dtype=torch.float64, device=self.device) if self.score is not None else None
             main = torch.cuda.current_stream(self.device)
             s_in, s_out = (self._s_in, self._s_out) if self.overlap else (main, main)
             uploaded = [None, None]    # per input slot: the upload from its pinned buffer has finished (event on s_in)
@@ -355,6 +457,14 @@ class ClipRunner:
                 b = j % 2
                 x = torch.stack([self._ring[(i - 2) % 3], self._ring[(i - 1) % 3], self._ring[i % 3]])
                 est, _ = self.model(x, None, None, est, train=False)
+                if sums is not None:
+                    # source frame j + 1 = i - 1 is still in its upload slot (the other one of the pair): converted at full size into the
+                    # reused HR buffer, then scored; the slot's next upload waits for this read as it does for the LR conversion
+                    c = (i - 1) % 2
+                    yuv_ingest(self._dev_in[c], self.shape, self.fmt_in, self.coef_in, self.siting, lr_out=self._truth)
+                    frame_metrics(est[0], self._truth, self.score, True, self.shave, out=sums[j:j + 1])
+                    converted[c] = torch.cuda.Event()
+                    converted[c].record(main)
                 if copied[b] is not None:   # frame j-2 leaves the slot pair: wait for its copy, take it from the pinned buffer
                     jj, ev = copied[b]
                     ev.synchronize()
@@ -379,6 +489,9 @@ class ClipRunner:
             for ev in uploaded + converted:   # the slots are idle when run() returns
                 if ev is not None:
                     ev.synchronize()
+            if sums is not None:
+                psnr, ssim = psnr_ssim(sums)   # the one copy (it waits for the current stream)
+                self.metrics = {"psnr": psnr, "ssim": ssim}
         return out
 
 
@@ -454,9 +567,10 @@ def run_c1(lr: int = 128, frames: int = 3, scale: int = 4, precision: str = "fp3
     return line, model, datas, outs
 
 
-def run_c1_yuv(pix_fmt: str, lr: int = 128, frames: int = 3, scale: int = 4, precision: str = "fp32"):
+def run_c1_yuv(pix_fmt: str, lr: int = 128, frames: int = 3, scale: int = 4, precision: str = "fp32", score: Optional[str] = None):
     """Config C1 with a 4:2:0 boundary: the synthetic clip as `pix_fmt` frames on the host, streamed through `ClipRunner`
-    (decimated by `scale`, super-resolved by `scale`).  -> (result line, output frames uint8 [T-2, frame_bytes] on the host)."""
+    (decimated by `scale`, super-resolved by `scale`).  -> (result line, output frames uint8 [T-2, frame_bytes] on the host).
+    `score`: "rgb" | "y": the line also carries the per-frame PSNR / SSIM against the synthetic HR clip."""
     import time
     from . import VSR
     from .weights import fill_module_
@@ -467,7 +581,7 @@ def run_c1_yuv(pix_fmt: str, lr: int = 128, frames: int = 3, scale: int = 4, pre
     model.precision = model.model.precision = precision
     video = synthetic_video(frames, S * lr, S * lr)
     clip = frames_to_yuv(torch.from_numpy(video).to(dev).float(), pix_fmt).cpu().numpy()
-    runner = ClipRunner(model, (S * lr, S * lr), pix_fmt, pix_fmt, scale_down=S)
+    runner = ClipRunner(model, (S * lr, S * lr), pix_fmt, pix_fmt, scale_down=S, score=score)
     runner.run(clip)                                                      # warm-up (packing, allocator)
     t0 = time.perf_counter()
     out = runner.run(clip)
@@ -475,6 +589,9 @@ def run_c1_yuv(pix_fmt: str, lr: int = 128, frames: int = 3, scale: int = 4, pre
     line = dict(config=f"C1: {frames}-frame {lr}x{lr} LR synthetic clip, x{S}, {pix_fmt} in and out, streamed clip runner, GPU path",
                 precision=precision, windows=frames - 2, frames_per_s=round((frames - 2) / dt, 3), out_shape=list(out.shape),
                 h2d_bytes_per_frame=runner.in_bytes, d2h_bytes_per_frame=runner.out_bytes)
+    if score is not None:
+        line.update(score=score, shave=runner.shave, psnr_db=[round(float(v), 4) for v in runner.metrics["psnr"]],
+                    ssim=[round(float(v), 6) for v in runner.metrics["ssim"]])
     return line, out
 
 
@@ -488,9 +605,13 @@ def main(argv=None):
     ap.add_argument("--precision", default="fp32", choices=["fp16", "fp32"])
     ap.add_argument("--pix-fmt", default=None, choices=sorted(YUV_FORMATS),
                     help="the clip enters and leaves as 4:2:0 frames of this format through ClipRunner (default: the RGB path)")
+    ap.add_argument("--score", default=None, choices=sorted(METRIC_CHANNELS),
+                    help="with --pix-fmt: per-frame PSNR / SSIM of the output against the synthetic HR clip, on RGB or on luma (BT.601 Y)")
     args = ap.parse_args(argv)
+    if args.score is not None and args.pix_fmt is None:
+        ap.error("--score needs --pix-fmt (the streamed clip runner scores its frames)")
     if args.pix_fmt is not None:
-        line, _ = run_c1_yuv(args.pix_fmt, args.lr, args.frames, args.scale, args.precision)
+        line, _ = run_c1_yuv(args.pix_fmt, args.lr, args.frames, args.scale, args.precision, args.score)
     else:
         line, _, _, _ = run_c1(args.lr, args.frames, args.scale, args.precision)
     print(json.dumps(line))
