@@ -358,6 +358,21 @@ def run_item(model, data, target, high_frames, train: bool = False, estimated_im
     return torch.stack(outs), losses, estimated_image
 
 
+def train_step(model, optimizer, x, y, high_frame, estimated_image, loss_value=None):
+    """main.py:206-210 for one window, without the host round trip of :207: the differentiable call (the SR net through
+    sr_train.forward_train), the fake MSE against `y` on the device, `loss.data` overwritten by `loss_value` when given (:208, the mean
+    of the no-grad windows' losses), backward, `optimizer.step()`.  `optimizer`: optim.Adam (update and clip on the device path) or
+    any torch optimizer.  The caller zeroes the gradients (:197).  -> (output detached, loss)."""
+    import torch.nn.functional as F
+    output, _ = model(x, y, high_frame, estimated_image)
+    loss = F.mse_loss(output, y.detach().float())
+    if loss_value is not None:
+        loss.data = torch.as_tensor(loss_value, dtype=loss.dtype, device=loss.device).reshape(())
+    loss.backward()
+    optimizer.step()
+    return output.detach(), loss
+
+
 class ClipRunner:
     """A 4:2:0 clip streamed through `model` frame by frame.  `shape` = (H, W) of the source frames in `fmt_in`; the model sees them
     decimated by `scale_down` (1: as they are) and returns frames of (S * (H // scale_down), S * (W // scale_down)), written out as
@@ -595,6 +610,30 @@ def run_c1_yuv(pix_fmt: str, lr: int = 128, frames: int = 3, scale: int = 4, pre
     return line, out
 
 
+def run_c1_train(steps: int, lr: int = 128, frames: int = 3, scale: int = 4, precision: str = "fp32", max_grad_norm: Optional[float] = None,
+                 learning_rate: float = 1e-3):
+    """Config C1's clip, then `steps` train steps on its last window (main.py:196-210 with optim.Adam): the no-grad windows give the
+    loss value and the estimate, each step is `train_step`.  -> result line with the loss per step and, with `max_grad_norm`, the
+    gradient norm per step (read back once, after the last step)."""
+    from . import optim
+    line, model, datas, _ = run_c1(lr, frames, scale, precision)
+    data, target, high_frames = ingest_item(datas, scale)
+    model.train()
+    optimizer = optim.Adam(model.parameters(), lr=learning_rate, max_grad_norm=max_grad_norm)
+    losses, norms_sq = [], []
+    for _ in range(steps):
+        optimizer.zero_grad()
+        _, window_losses, est = run_item(model, data, target, high_frames, train=True)                 # main.py:199-203
+        _, loss = train_step(model, optimizer, data[-1], target[-1], high_frames[-1], est, sum(window_losses) / len(window_losses))
+        losses.append(loss.detach())
+        if optimizer.last_grad_norm_sq is not None:
+            norms_sq.append(optimizer.last_grad_norm_sq.clone())
+    line.update(train_steps=steps, learning_rate=learning_rate, max_grad_norm=max_grad_norm,
+                loss=[round(float(v), 6) for v in torch.stack(losses).cpu()] if losses else [],
+                grad_norm=[round(float(v) ** 0.5, 6) for v in torch.stack(norms_sq).cpu()] if norms_sq else None)
+    return line, model
+
+
 def main(argv=None):
     import argparse
     import json
@@ -607,10 +646,20 @@ def main(argv=None):
                     help="the clip enters and leaves as 4:2:0 frames of this format through ClipRunner (default: the RGB path)")
     ap.add_argument("--score", default=None, choices=sorted(METRIC_CHANNELS),
                     help="with --pix-fmt: per-frame PSNR / SSIM of the output against the synthetic HR clip, on RGB or on luma (BT.601 Y)")
+    ap.add_argument("--train-steps", type=int, default=None, metavar="K",
+                    help="after the no-grad windows: K train steps on the last window (optim.Adam); the line carries the loss per step")
+    ap.add_argument("--max-grad-norm", type=float, default=None, metavar="X",
+                    help="with --train-steps: clip the global gradient norm at X on the device; the line carries the norm per step")
     args = ap.parse_args(argv)
     if args.score is not None and args.pix_fmt is None:
         ap.error("--score needs --pix-fmt (the streamed clip runner scores its frames)")
-    if args.pix_fmt is not None:
+    if args.max_grad_norm is not None and args.train_steps is None:
+        ap.error("--max-grad-norm needs --train-steps")
+    if args.train_steps is not None:
+        if args.pix_fmt is not None or args.train_steps < 0:
+            ap.error("--train-steps takes a non-negative count and runs on the RGB path (no --pix-fmt)")
+        line, _ = run_c1_train(args.train_steps, args.lr, args.frames, args.scale, args.precision, args.max_grad_norm)
+    elif args.pix_fmt is not None:
         line, _ = run_c1_yuv(args.pix_fmt, args.lr, args.frames, args.scale, args.precision, args.score)
     else:
         line, _, _, _ = run_c1(args.lr, args.frames, args.scale, args.precision)
