@@ -611,12 +611,14 @@ def run_c1_yuv(pix_fmt: str, lr: int = 128, frames: int = 3, scale: int = 4, pre
 
 
 def run_c1_train(steps: int, lr: int = 128, frames: int = 3, scale: int = 4, precision: str = "fp32", max_grad_norm: Optional[float] = None,
-                 learning_rate: float = 1e-3):
+                 learning_rate: float = 1e-3, loss_path: str = "reference"):
     """Config C1's clip, then `steps` train steps on its last window (main.py:196-210 with optim.Adam): the no-grad windows give the
     loss value and the estimate, each step is `train_step`.  -> result line with the loss per step and, with `max_grad_norm`, the
-    gradient norm per step (read back once, after the last step)."""
+    gradient norm per step (read back once, after the last step).  `loss_path` is VSR.loss_path: with "fused" the windows' losses and their
+    mean stay on the device."""
     from . import optim
     line, model, datas, _ = run_c1(lr, frames, scale, precision)
+    model.loss_path = loss_path
     data, target, high_frames = ingest_item(datas, scale)
     model.train()
     optimizer = optim.Adam(model.parameters(), lr=learning_rate, max_grad_norm=max_grad_norm)
@@ -628,7 +630,7 @@ def run_c1_train(steps: int, lr: int = 128, frames: int = 3, scale: int = 4, pre
         losses.append(loss.detach())
         if optimizer.last_grad_norm_sq is not None:
             norms_sq.append(optimizer.last_grad_norm_sq.clone())
-    line.update(train_steps=steps, learning_rate=learning_rate, max_grad_norm=max_grad_norm,
+    line.update(train_steps=steps, learning_rate=learning_rate, max_grad_norm=max_grad_norm, loss_path=loss_path,
                 loss=[round(float(v), 6) for v in torch.stack(losses).cpu()] if losses else [],
                 grad_norm=[round(float(v) ** 0.5, 6) for v in torch.stack(norms_sq).cpu()] if norms_sq else None)
     return line, model
@@ -650,7 +652,11 @@ def main(argv=None):
                     help="after the no-grad windows: K train steps on the last window (optim.Adam); the line carries the loss per step")
     ap.add_argument("--max-grad-norm", type=float, default=None, metavar="X",
                     help="with --train-steps: clip the global gradient norm at X on the device; the line carries the norm per step")
+    ap.add_argument("--loss-path", default=None, choices=["reference", "fused"],
+                    help="with --train-steps: VSR.loss_path (default reference; fused: the loss stays on the device)")
     args = ap.parse_args(argv)
+    if args.loss_path is not None and args.train_steps is None:
+        ap.error("--loss-path needs --train-steps")
     if args.score is not None and args.pix_fmt is None:
         ap.error("--score needs --pix-fmt (the streamed clip runner scores its frames)")
     if args.max_grad_norm is not None and args.train_steps is None:
@@ -658,7 +664,8 @@ def main(argv=None):
     if args.train_steps is not None:
         if args.pix_fmt is not None or args.train_steps < 0:
             ap.error("--train-steps takes a non-negative count and runs on the RGB path (no --pix-fmt)")
-        line, _ = run_c1_train(args.train_steps, args.lr, args.frames, args.scale, args.precision, args.max_grad_norm)
+        line, _ = run_c1_train(args.train_steps, args.lr, args.frames, args.scale, args.precision, args.max_grad_norm,
+                               loss_path=args.loss_path or "reference")
     elif args.pix_fmt is not None:
         line, _ = run_c1_yuv(args.pix_fmt, args.lr, args.frames, args.scale, args.precision, args.score)
     else:

@@ -24,6 +24,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import _lib as L
 from .vos import VOSProjectionModule
 
 _VGG16_CFG = [64, 64, "M", 128, 128, "M", 256, 256, 256, "M", 512, 512, 512, "M", 512, 512, 512, "M"]
@@ -169,3 +170,71 @@ def loss_calculate(model, target, outputs, taps: dict | None = None) -> torch.Te
                         masked_sr_tgt=masked[1], masked_flow=masked_flow)
         loss = gen_sr.data + obj_sr.data + 0.006 * gen_flow.data + 0.006 * obj_flow.data
         return loss.cpu()
+
+
+@L.on_device
+def pixel_terms(outputs: torch.Tensor, target: torch.Tensor, mask: torch.Tensor, masked: bool = True, nhwc4: bool = False):
+    """Everything of `loss_calculate` that is per-pixel arithmetic, in one launch and a finish (libvsr_hip_loss.so;
+    include/vsr_hip_loss.h states the arithmetic): outputs [3,H,W,3] and target [H,W,3] | [1,H,W,3] float32 on the device, mask
+    3*H*W bool / uint8 of any shape (element e of a frame is masked by element e of the mask, as numpy reshapes it).
+    -> (sums float64 [14], terms float32 [6,2] = {image, tv} of the six SR_loss calls, masked float32 [4,H,W,3] = mO0, mO1, mO2, mT
+    or None, nhwc4 float16 [8,H,W,4] = O0, O1, O2, T, mO0, mO1, mO2, mT or None).  Enqueues on the current stream, waits for nothing."""
+    if outputs.dim() != 4 or outputs.shape[0] != 3 or outputs.shape[3] != 3:
+        raise L.VsrHipError(f"pixel_terms: outputs must be [3,H,W,3], got {tuple(outputs.shape)}")
+    H, W = int(outputs.shape[1]), int(outputs.shape[2])
+    if target.numel() != 3 * H * W or mask.numel() != 3 * H * W:
+        raise L.VsrHipError(f"pixel_terms: target and mask must hold {3 * H * W} elements, got {target.numel()} and {mask.numel()}")
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    lib, dev = L.load_loss(), outputs.device
+    ws = torch.empty(max(int(lib.vsr_loss_ws_bytes(H, W)) // 8, 1), dtype=torch.float64, device=dev)
+    sums = torch.empty(14, dtype=torch.float64, device=dev)
+    terms = torch.empty((6, 2), dtype=torch.float32, device=dev)
+    m = torch.empty((4, H, W, 3), dtype=torch.float32, device=dev) if masked else None
+    h = torch.empty((8, H, W, 4), dtype=torch.float16, device=dev) if nhwc4 else None
+    L.check(lib.vsr_loss_pixel_terms(L.dptr(outputs), L.dptr(target), L.dptr(mask, torch.uint8), H, W, L.optr(m), L.optr(h, torch.float16),
+                                     L.dptr(sums, torch.float64), L.dptr(terms), L.dptr(ws, torch.float64), L.stream()),
+            "loss_pixel_terms", lib=lib)
+    return sums, terms, m, h
+
+
+def loss_calculate_fused(model, target, outputs, taps: dict | None = None) -> torch.Tensor:
+    """`loss_calculate` with its pixel arithmetic in `pixel_terms` and every distinct (network, frame) pair through VGG once (ten
+    passes for the reference's twelve: Flow_loss evaluates O1 and mO1 twice).  -> a 0-d float32 tensor ON THE DEVICE; nothing is
+    read back unless `taps` is given (the same keys as `loss_calculate`'s).  The object mask is computed and cached by the first call
+    through `loss4object`, as there.  precision "fp16": the VGG executor takes the NHWC-4 half frames the launch wrote; "fp32": the
+    stock networks take the float frames (the masked ones from the launch).  One frame per VGG call, as in `loss_calculate`."""
+    with torch.no_grad():
+        precision = getattr(model, "precision", "fp32")
+        model.SR_loss.precision = model.Flow_loss.SR_loss.precision = model.loss4object.precision = precision
+        sr, fsr = model.SR_loss, model.Flow_loss.SR_loss
+        dev = next(sr.loss_network.parameters()).device
+        outputs = outputs.to(dev, torch.float32).contiguous()
+        target = target.to(dev, torch.float32).contiguous()
+        H, W = outputs.shape[1], outputs.shape[2]
+        if model.loss4object.mask is None:
+            model.loss4object(outputs[:2], target, SR=True)   # OSVOS on (frame 0, frame 1), once; the mask stays cached
+        fp16 = precision == "fp16" and outputs.is_cuda
+        _, terms, mk, nh = pixel_terms(outputs, target, model.loss4object.mask, masked=not fp16 or taps is not None, nhwc4=fp16)
+
+        def feats(net, k):   # frame k of O0, O1, O2, T, mO0, mO1, mO2, mT through `net`'s VGG16
+            if fp16:
+                from .trunk_exec import TrunkExecCache, VGGFeatExec
+                if net._exec is None:
+                    net._exec = TrunkExecCache(net.loss_network, VGGFeatExec)
+                return net._exec.get().from_nhwc4(nh[k:k + 1])
+            frame = outputs[k:k + 1] if k < 3 else target.reshape(1, H, W, 3) if k == 3 else mk[k - 4:k - 3]
+            return net.loss_network(frame.permute(0, 3, 1, 2))   # transpose1323
+
+        def sr_loss(net, i, fa, fb):   # SR_loss.forward with the image and TV terms of call i
+            return terms[i, 0] + 0.006 * net.mse_loss(fa, fb) + 2e-8 * terms[i, 1]
+
+        gen_sr = sr_loss(sr, 0, feats(sr, 0), feats(sr, 3))
+        obj_sr = sr_loss(sr, 1, feats(sr, 5), feats(sr, 7))
+        f = {k: feats(fsr, k) for k in (0, 1, 2, 4, 5, 6)}
+        gen_flow = 0.005 * torch.mean(torch.stack((sr_loss(fsr, 2, f[0], f[1]), sr_loss(fsr, 3, f[1], f[2]))))
+        obj_flow = 0.005 * torch.mean(torch.stack((sr_loss(fsr, 4, f[4], f[5]), sr_loss(fsr, 5, f[5], f[6]))))
+        if taps is not None:
+            taps.update(terms=[float(gen_sr), float(obj_sr), float(gen_flow), float(obj_flow)], masked_sr_out=mk[1:2],
+                        masked_sr_tgt=mk[3:4], masked_flow=mk[:3])
+        return gen_sr + obj_sr + 0.006 * gen_flow + 0.006 * obj_flow

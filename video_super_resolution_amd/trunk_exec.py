@@ -624,11 +624,19 @@ class VGGFeatExec:
 
     @L.on_device
     @torch.no_grad()
-    def __call__(self, x_nchw):
-        x = to_nhwc_half(x_nchw.float().contiguous(), 4)
+    def from_nhwc4(self, x):
+        """[N,H,W,4] float16 (RGB in channels 0..2, channel 3 zero: what `to_nhwc_half(frames, 4)` makes, or a frame of
+        loss.pixel_terms' `nhwc4`) -> [N,512,H/32,W/32] float32."""
+        if x.dim() != 4 or x.shape[3] != 4 or x.dtype != torch.float16 or not x.is_contiguous():
+            raise L.VsrHipError("VGGFeatExec.from_nhwc4: a dense [N,H,W,4] float16 tensor")
         for it in self.items:
             x = pool2x2(x, 0, x.shape[3], 0) if it == "M" else it(x)   # MaxPool2d(2, 2): floor mode
         return x.permute(0, 3, 1, 2).float()
+
+    @L.on_device
+    @torch.no_grad()
+    def __call__(self, x_nchw):
+        return self.from_nhwc4(to_nhwc_half(x_nchw.float().contiguous(), 4))
 
 
 class TrunkExecCache:

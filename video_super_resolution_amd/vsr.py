@@ -36,7 +36,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .depth import DepthProjectionModule
-from .loss import Flow_loss, GetObjectsForOBJLoss, SR_loss, loss_calculate
+from .loss import Flow_loss, GetObjectsForOBJLoss, SR_loss, loss_calculate, loss_calculate_fused
 from .flownet import FlowProjectionModule
 from .sr import SRProjectionModule
 from .trunk_exec import FlowNet2Exec, HourglassExec, OSVOSExec, TrunkExecCache
@@ -66,6 +66,9 @@ class VSR(nn.Module):
         self.Flow_loss = Flow_loss().eval()
         self.loss4object = GetObjectsForOBJLoss().eval()
         self.loss_fn: Optional[Callable] = None   # optional override: loss_fn(target, high_frames) instead of loss_calculate
+        # "reference": loss.loss_calculate, a 0-d CPU tensor like the reference's; "fused": loss.loss_calculate_fused (the pixel terms in
+        # one launch, ten VGG passes for twelve), a 0-d tensor on the device, no host wait
+        self.loss_path = "reference"
         # "fp16": the headline configuration -- SR stack on the MFMA path, guidance trunks on the hand-written NHWC fp16
         #         MFMA convolution (trunk_exec.py: BatchNorm folded, concatenations written in place, frames batched);
         # "fp32": SR stack in exact float32 kernels, trunks on stock float32 convolutions (the parity configuration).
@@ -114,9 +117,13 @@ class VSR(nn.Module):
         return self
 
     def loss_calculate(self, target, outputs):
-        """video_super_resolution.py:71-80 (a 0-d CPU tensor, computed under no_grad like the reference)."""
+        """video_super_resolution.py:71-80, computed under no_grad like the reference: a 0-d CPU tensor, or with
+        `loss_path = "fused"` a 0-d tensor on the device."""
+        path = getattr(self, "loss_path", "reference")
+        if path not in ("reference", "fused"):
+            raise ValueError(f"VSR.loss_path must be 'reference' or 'fused', got {path!r}")
         taps = {} if self.keep_loss_terms else None
-        loss = loss_calculate(self, target, outputs, taps)
+        loss = (loss_calculate_fused if path == "fused" else loss_calculate)(self, target, outputs, taps)
         if taps is not None:
             self.last_loss_terms = taps
         return loss
