@@ -16,10 +16,15 @@ feeds it, on the GPU path and without OpenCV:
     read_clip_yuv / ingest_item_yuv / frames_to_yuv     the same three steps for what decoders emit: packed Y'CbCr 4:2:0 frames
                             (yuv420p, nv12, yuv420p10le, p010le), converted on the device (include/vsr_hip_yuv.h); the matrix
                             coefficients come from `yuv_coefficients` alone
+    resize_tables / FrameResizer   float32 RGB frames resampled on the device by a separable filter given as tables
+                            (include/vsr_hip_resize.h): antialiased bicubic (Keys, a = -0.5, Pillow's convention) or bilinear; the tables
+                            come from `resize_tables` alone
     ClipRunner              a clip streamed through the model: every source frame uploaded once from pinned memory on a copy stream,
                             converted once into a three-slot LR ring, the window formed on the device, the HR frame written out as
                             4:2:0 and copied back on a second copy stream; `score=`: every output frame scored against the source
-                            frame it restores, from the upload already on the device
+                            frame it restores, from the upload already on the device; `decimate="bicubic"`: LR frames that are the
+                            antialiased bicubic reduction of the source stored as 8-bit; `baseline="bicubic"`: the bicubic enlargement
+                            of the middle LR frame scored beside the estimate
     save_checkpoint / load_checkpoint   utils/tools.py:68-73 and main.py:108-122,233-237: {'arch','epoch','state_dict':
                             SRmodel.model.state_dict(),'optimizer'} -- files interchange with the reference's
 
@@ -203,6 +208,100 @@ def psnr_ssim(sums) -> Tuple[np.ndarray, np.ndarray]:
     on = n_ssim > 0
     ssim[on] = ssim_sum[on] / n_ssim[on]
     return psnr, ssim
+
+
+# ------------------------------------------------------------------------------------------------ resampling
+RESIZE_KERNELS = {"bicubic": 2.0, "bilinear": 1.0}   # the support of the filter at scale 1
+RESIZE_MAX_TAPS = 33                                 # VSR_RESIZE_MAX_TAPS of include/vsr_hip_resize.h
+
+
+def _resize_filter(kernel: str, x: np.ndarray) -> np.ndarray:
+    x = np.abs(x)
+    if kernel == "bilinear":
+        return np.where(x < 1.0, 1.0 - x, 0.0)
+    a = -0.5   # Keys' cubic
+    return np.where(x < 1.0, ((a + 2.0) * x - (a + 3.0)) * x * x + 1.0, np.where(x < 2.0, a * (((x - 5.0) * x + 8.0) * x - 4.0), 0.0))
+
+
+def resize_tables(n_in: int, n_out: int, kernel: str = "bicubic") -> Tuple[np.ndarray, np.ndarray]:
+    """One axis of an antialiased resize from `n_in` to `n_out` samples as the two tables vsr_resize_frames takes:
+    (first int32 [n_out], weight float32 [n_out, K]); output i is sum_k weight[i, k] * in[clamp(first[i] + k)].  Pillow's convention,
+    which is also that of torch's `interpolate(antialias=True, align_corners=False)`: scale = n_in / n_out, fs = max(scale, 1), support =
+    2 fs ("bicubic": Keys' cubic with a = -0.5) or fs ("bilinear": the triangle), K = 2 ceil(support) + 1; for output i, c = scale (i + 0.5),
+    lo = max(int(c - support + 0.5), 0), hi = min(int(c + support + 0.5), n_in), w_j = filter((j + lo - c + 0.5) / fs) for j < hi - lo over
+    their sum, first = lo; the taps from hi - lo to K - 1 carry weight 0.  Computed in float64, the weights rounded once to float32;
+    this is the single source of the coefficients (the C side computes none)."""
+    if kernel not in RESIZE_KERNELS:
+        raise ValueError(f"unknown kernel {kernel!r} (known: {', '.join(RESIZE_KERNELS)})")
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in <= 0 or n_out <= 0:
+        raise ValueError(f"sizes must be positive, got {n_in} -> {n_out}")
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    support = RESIZE_KERNELS[kernel] * fs
+    K = 2 * int(np.ceil(support)) + 1
+    if K > RESIZE_MAX_TAPS:
+        raise ValueError(f"{kernel} from {n_in} to {n_out} needs {K} taps, beyond the {RESIZE_MAX_TAPS} of the library")
+    c = scale * (np.arange(n_out, dtype=np.float64) + 0.5)
+    lo = np.maximum((c - support + 0.5).astype(np.int64), 0)       # (int(): truncation; the arguments of the ones that matter are >= 0)
+    hi = np.minimum((c + support + 0.5).astype(np.int64), n_in)
+    j = np.arange(K, dtype=np.float64)[None, :]
+    wt = _resize_filter(kernel, (j + lo[:, None] - c[:, None] + 0.5) / fs)
+    wt = np.where(j < (hi - lo)[:, None], wt, 0.0)
+    wt = wt / wt.sum(axis=1, keepdims=True)
+    return lo.astype(np.int32), np.ascontiguousarray(wt.astype(np.float32))
+
+
+@L.on_device
+def resize_frames(src: torch.Tensor, out_shape: Tuple[int, int], x_first: torch.Tensor, x_weight: torch.Tensor, y_first: torch.Tensor,
+                  y_weight: torch.Tensor, quantise: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The low-level call (vsr_resize_frames) with any tables on the device: src float32 [F,H,W,3] (or [H,W,3]) -> [F,h,w,3] ([h,w,3]);
+    x_first int32 [w], x_weight float32 [w,KX], y_first int32 [h], y_weight float32 [h,KY]."""
+    if src.dim() not in (3, 4) or src.shape[-1] != 3:
+        raise ValueError(f"expected float32 [F,H,W,3] or [H,W,3], got {tuple(src.shape)}")
+    h, w = int(out_shape[0]), int(out_shape[1])
+    H, W = int(src.shape[-3]), int(src.shape[-2])
+    lead = tuple(src.shape[:-3])
+    F = int(src.shape[0]) if src.dim() == 4 else 1
+    if tuple(x_first.shape) != (w,) or x_weight.dim() != 2 or x_weight.shape[0] != w or tuple(y_first.shape) != (h,) or y_weight.dim() != 2 \
+            or y_weight.shape[0] != h:
+        raise ValueError(f"tables do not fit {h} x {w}: x {tuple(x_first.shape)} / {tuple(x_weight.shape)}, y {tuple(y_first.shape)} / "
+                         f"{tuple(y_weight.shape)}")
+    R = L.load_resize()
+    ps = L.dptr(src)   # (raises on CPU tensors, on anything but float32 and on strided views)
+    if out is None:
+        out = torch.empty(lead + (h, w, 3), dtype=torch.float32, device=src.device)
+    elif tuple(out.shape) != lead + (h, w, 3) or out.device != src.device:
+        raise ValueError(f"out must be float32 {lead + (h, w, 3)} on {src.device}, got {tuple(out.shape)} on {out.device}")
+    L.check(R.vsr_resize_frames(ps, L.dptr(out), F, H, W, h, w, L.dptr(x_first, torch.int32), L.dptr(x_weight), int(x_weight.shape[1]),
+                                L.dptr(y_first, torch.int32), L.dptr(y_weight), int(y_weight.shape[1]), 1 if quantise else 0, L.stream()),
+            "resize_frames", lib=R)
+    return out
+
+
+class FrameResizer:
+    """Frames of `in_shape` = (H, W) resampled to `out_shape` = (h, w) by `kernel` ("bicubic" | "bilinear", antialiased: `resize_tables`):
+    the four tables are built and uploaded once; `resizer(src [F,H,W,3] or [H,W,3] float32 on the device, quantise=False, out=None)`
+    enqueues one launch on the current stream.  `quantise`: the result as an 8-bit file would hold it (clamped to 0..255, rounded half to
+    even); without it a bicubic result may leave 0..255."""
+
+    def __init__(self, in_shape: Tuple[int, int], out_shape: Tuple[int, int], kernel: str = "bicubic", device="cuda"):
+        self.in_shape = (int(in_shape[0]), int(in_shape[1]))
+        self.out_shape = (int(out_shape[0]), int(out_shape[1]))
+        self.kernel = kernel
+        yf, yw = resize_tables(self.in_shape[0], self.out_shape[0], kernel)
+        xf, xw = resize_tables(self.in_shape[1], self.out_shape[1], kernel)
+        self.device = torch.device(device)
+        self.y_first, self.y_weight, self.x_first, self.x_weight = (torch.from_numpy(a).to(self.device) for a in (yf, yw, xf, xw))
+
+    def __call__(self, src: torch.Tensor, quantise: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if not src.is_cuda:
+            raise L.VsrHipError("device path called with a CPU tensor (no CPU fallback exists)")
+        if src.dim() not in (3, 4) or tuple(src.shape[-3:]) != self.in_shape + (3,):
+            raise ValueError(f"expected float32 [F,{self.in_shape[0]},{self.in_shape[1]},3], got {tuple(src.shape)}")
+        if src.device != self.x_first.device:
+            raise ValueError(f"the tables live on {self.x_first.device}, the frames on {src.device}")
+        return resize_frames(src, self.out_shape, self.x_first, self.x_weight, self.y_first, self.y_weight, quantise, out)
 
 
 # ------------------------------------------------------------------------------------------------ Y'CbCr 4:2:0 in and out
@@ -390,11 +489,29 @@ class ClipRunner:
     upload slot when the window runs: one more conversion at full size into a reused HR buffer and `frame_metrics` of the float
     estimate (quantised as write-out does, `shave` pixels dropped on every side, default S; "y" is `frame_metrics`' BT.601 luma whatever
     `matrix` the frames are coded with) into row j of one [T-2,4] tensor; nothing
-    extra is uploaded, and one copy at the end gives `metrics = {"psnr": [T-2], "ssim": [T-2]}`."""
+    extra is uploaded, and one copy at the end gives `metrics = {"psnr": [T-2], "ssim": [T-2]}`.
+
+    `decimate="nearest"` (default): the LR frame is the conversion's own nearest-neighbour decimation (the reference's `interpolate` at
+    main.py:157).  `decimate="bicubic"`: every uploaded frame is converted at full size into a reused HR buffer of its own (not the one the
+    scored window's truth lives in) and reduced into its ring slot by `FrameResizer(quantise=True)`: the antialiased bicubic LR frame as an
+    8-bit file would hold it, the evaluation protocol of the literature.  `baseline="bicubic"` (needs `score`): per window the middle LR
+    frame of the ring is enlarged to the output shape into a reused buffer and scored against the same truth with the same quantise,
+    shave and channels as the estimate, into a second [T-2,4] tensor copied with the first: `metrics` gains `psnr_baseline` and
+    `ssim_baseline`.  Neither uploads or downloads a byte more; with both at their defaults the launches are the ones described above."""
+
+    DECIMATE = ("nearest", "bicubic")
+    BASELINE = (None, "bicubic")
 
     def __init__(self, model, shape: Tuple[int, int], fmt_in: str, fmt_out: str, scale_down: int = 1, overlap: bool = True,
                  matrix: str = "bt709", full_range: bool = False, siting: str = "left", score: Optional[str] = None,
-                 shave: Optional[int] = None):
+                 shave: Optional[int] = None, decimate: str = "nearest", baseline: Optional[str] = None):
+        if decimate not in self.DECIMATE:
+            raise ValueError(f"decimate must be 'nearest' or 'bicubic', got {decimate!r}")
+        if baseline not in self.BASELINE:
+            raise ValueError(f"baseline must be None or 'bicubic', got {baseline!r}")
+        if baseline is not None and score is None:
+            raise ValueError(f"baseline={baseline!r} is scored beside the estimate: it needs score='rgb' or 'y'")
+        self.decimate, self.baseline = decimate, baseline
         self.model, self.fmt_in, self.fmt_out, self.overlap, self.siting = model, fmt_in, fmt_out, bool(overlap), siting
         H, W = int(shape[0]), int(shape[1])
         self.shape = (H, W)
@@ -424,6 +541,13 @@ class ClipRunner:
         self._dev_out = [torch.empty(self.out_bytes, dtype=torch.uint8, device=dev) for _ in range(2)]
         self._ring = [torch.empty(self.lr_shape + (3,), dtype=torch.float32, device=dev) for _ in range(3)]
         self._truth = torch.empty(self.shape + (3,), dtype=torch.float32, device=dev) if score is not None else None
+        self._full = self._down = self._up = self._base = None
+        if decimate == "bicubic":
+            self._full = torch.empty(self.shape + (3,), dtype=torch.float32, device=dev)   # the frame being reduced; `_truth` is the window's
+            self._down = FrameResizer(self.shape, self.lr_shape, "bicubic", dev)
+        if baseline is not None:
+            self._base = torch.empty(self.out_shape + (3,), dtype=torch.float32, device=dev)
+            self._up = FrameResizer(self.lr_shape, self.out_shape, baseline, dev)
         self._s_in = torch.cuda.Stream(dev) if self.overlap else None
         self._s_out = torch.cuda.Stream(dev) if self.overlap else None
         self.h2d_bytes = self.d2h_bytes = self.frames_in = self.frames_out = 0   # of the last run()
@@ -442,6 +566,7 @@ class ClipRunner:
         self.metrics = None
         with torch.cuda.device(self.device), torch.no_grad():
             sums = torch.empty((T - 2, 4), dtype=torch.float64, device=self.device) if self.score is not None else None
+            sums_base = torch.empty((T - 2, 4), dtype=torch.float64, device=self.device) if self.baseline is not None else None
             main = torch.cuda.current_stream(self.device)
             s_in, s_out = (self._s_in, self._s_out) if self.overlap else (main, main)
             uploaded = [None, None]    # per input slot: the upload from its pinned buffer has finished (event on s_in)
@@ -463,7 +588,11 @@ class ClipRunner:
                 self.frames_in += 1
                 main.wait_event(uploaded[a])
                 # (ring slot i % 3 was last read by the window of frames i-3 .. i-1, stacked on this stream)
-                yuv_ingest(self._dev_in[a], self.shape, self.fmt_in, self.coef_in, self.siting, self.lr_shape, lr_out=self._ring[i % 3])
+                if self._down is None:
+                    yuv_ingest(self._dev_in[a], self.shape, self.fmt_in, self.coef_in, self.siting, self.lr_shape, lr_out=self._ring[i % 3])
+                else:   # (the HR buffer was last read by the previous frame's reduction, on this stream)
+                    yuv_ingest(self._dev_in[a], self.shape, self.fmt_in, self.coef_in, self.siting, lr_out=self._full)
+                    self._down(self._full, quantise=True, out=self._ring[i % 3])
                 converted[a] = torch.cuda.Event()
                 converted[a].record(main)
                 if i < 2:
@@ -478,6 +607,9 @@ class ClipRunner:
                     c = (i - 1) % 2
                     yuv_ingest(self._dev_in[c], self.shape, self.fmt_in, self.coef_in, self.siting, lr_out=self._truth)
                     frame_metrics(est[0], self._truth, self.score, True, self.shave, out=sums[j:j + 1])
+                    if sums_base is not None:
+                        self._up(self._ring[(i - 1) % 3], quantise=False, out=self._base)
+                        frame_metrics(self._base, self._truth, self.score, True, self.shave, out=sums_base[j:j + 1])
                     converted[c] = torch.cuda.Event()
                     converted[c].record(main)
                 if copied[b] is not None:   # frame j-2 leaves the slot pair: wait for its copy, take it from the pinned buffer
@@ -505,8 +637,14 @@ class ClipRunner:
                 if ev is not None:
                     ev.synchronize()
             if sums is not None:
-                psnr, ssim = psnr_ssim(sums)   # the one copy (it waits for the current stream)
-                self.metrics = {"psnr": psnr, "ssim": ssim}
+                if sums_base is None:
+                    psnr, ssim = psnr_ssim(sums)   # the one copy (it waits for the current stream)
+                    self.metrics = {"psnr": psnr, "ssim": ssim}
+                else:
+                    both = torch.stack([sums, sums_base]).cpu().numpy()   # still one copy
+                    psnr, ssim = psnr_ssim(both[0])
+                    psnr_b, ssim_b = psnr_ssim(both[1])
+                    self.metrics = {"psnr": psnr, "ssim": ssim, "psnr_baseline": psnr_b, "ssim_baseline": ssim_b}
         return out
 
 
@@ -582,10 +720,12 @@ def run_c1(lr: int = 128, frames: int = 3, scale: int = 4, precision: str = "fp3
     return line, model, datas, outs
 
 
-def run_c1_yuv(pix_fmt: str, lr: int = 128, frames: int = 3, scale: int = 4, precision: str = "fp32", score: Optional[str] = None):
+def run_c1_yuv(pix_fmt: str, lr: int = 128, frames: int = 3, scale: int = 4, precision: str = "fp32", score: Optional[str] = None,
+               decimate: str = "nearest", baseline: Optional[str] = None):
     """Config C1 with a 4:2:0 boundary: the synthetic clip as `pix_fmt` frames on the host, streamed through `ClipRunner`
     (decimated by `scale`, super-resolved by `scale`).  -> (result line, output frames uint8 [T-2, frame_bytes] on the host).
-    `score`: "rgb" | "y": the line also carries the per-frame PSNR / SSIM against the synthetic HR clip."""
+    `score`: "rgb" | "y": the line also carries the per-frame PSNR / SSIM against the synthetic HR clip.  `decimate` / `baseline`: as
+    `ClipRunner`'s; with a baseline the line carries its mean PSNR / SSIM beside the estimate's and `psnr_gain`, their difference in dB."""
     import time
     from . import VSR
     from .weights import fill_module_
@@ -596,7 +736,7 @@ def run_c1_yuv(pix_fmt: str, lr: int = 128, frames: int = 3, scale: int = 4, pre
     model.precision = model.model.precision = precision
     video = synthetic_video(frames, S * lr, S * lr)
     clip = frames_to_yuv(torch.from_numpy(video).to(dev).float(), pix_fmt).cpu().numpy()
-    runner = ClipRunner(model, (S * lr, S * lr), pix_fmt, pix_fmt, scale_down=S, score=score)
+    runner = ClipRunner(model, (S * lr, S * lr), pix_fmt, pix_fmt, scale_down=S, score=score, decimate=decimate, baseline=baseline)
     runner.run(clip)                                                      # warm-up (packing, allocator)
     t0 = time.perf_counter()
     out = runner.run(clip)
@@ -607,6 +747,14 @@ def run_c1_yuv(pix_fmt: str, lr: int = 128, frames: int = 3, scale: int = 4, pre
     if score is not None:
         line.update(score=score, shave=runner.shave, psnr_db=[round(float(v), 4) for v in runner.metrics["psnr"]],
                     ssim=[round(float(v), 6) for v in runner.metrics["ssim"]])
+    if decimate != "nearest":
+        line.update(decimate=decimate)
+    if baseline is not None:
+        m = runner.metrics
+        line.update(baseline=baseline, psnr_mean_db=round(float(np.mean(m["psnr"])), 4), ssim_mean=round(float(np.mean(m["ssim"])), 6),
+                    psnr_baseline_mean_db=round(float(np.mean(m["psnr_baseline"])), 4),
+                    ssim_baseline_mean=round(float(np.mean(m["ssim_baseline"])), 6),
+                    psnr_gain=round(float(np.mean(m["psnr"]) - np.mean(m["psnr_baseline"])), 4))
     return line, out
 
 
@@ -648,6 +796,10 @@ def main(argv=None):
                     help="the clip enters and leaves as 4:2:0 frames of this format through ClipRunner (default: the RGB path)")
     ap.add_argument("--score", default=None, choices=sorted(METRIC_CHANNELS),
                     help="with --pix-fmt: per-frame PSNR / SSIM of the output against the synthetic HR clip, on RGB or on luma (BT.601 Y)")
+    ap.add_argument("--decimate", default="nearest", choices=list(ClipRunner.DECIMATE),
+                    help="with --pix-fmt: how the LR frames are made (nearest: the reference's decimation; bicubic: antialiased, stored as 8-bit)")
+    ap.add_argument("--baseline", default=None, choices=["bicubic"],
+                    help="with --score: also score the bicubic enlargement of the LR frame; the line carries both means and psnr_gain")
     ap.add_argument("--train-steps", type=int, default=None, metavar="K",
                     help="after the no-grad windows: K train steps on the last window (optim.Adam); the line carries the loss per step")
     ap.add_argument("--max-grad-norm", type=float, default=None, metavar="X",
@@ -659,6 +811,10 @@ def main(argv=None):
         ap.error("--loss-path needs --train-steps")
     if args.score is not None and args.pix_fmt is None:
         ap.error("--score needs --pix-fmt (the streamed clip runner scores its frames)")
+    if args.decimate != "nearest" and args.pix_fmt is None:
+        ap.error("--decimate needs --pix-fmt (the streamed clip runner makes the LR frames)")
+    if args.baseline is not None and args.score is None:
+        ap.error("--baseline needs --score (it is scored beside the estimate)")
     if args.max_grad_norm is not None and args.train_steps is None:
         ap.error("--max-grad-norm needs --train-steps")
     if args.train_steps is not None:
@@ -667,7 +823,7 @@ def main(argv=None):
         line, _ = run_c1_train(args.train_steps, args.lr, args.frames, args.scale, args.precision, args.max_grad_norm,
                                loss_path=args.loss_path or "reference")
     elif args.pix_fmt is not None:
-        line, _ = run_c1_yuv(args.pix_fmt, args.lr, args.frames, args.scale, args.precision, args.score)
+        line, _ = run_c1_yuv(args.pix_fmt, args.lr, args.frames, args.scale, args.precision, args.score, args.decimate, args.baseline)
     else:
         line, _, _, _ = run_c1(args.lr, args.frames, args.scale, args.precision)
     print(json.dumps(line))
