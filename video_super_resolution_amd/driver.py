@@ -24,7 +24,11 @@ feeds it, on the GPU path and without OpenCV:
                             4:2:0 and copied back on a second copy stream; `score=`: every output frame scored against the source
                             frame it restores, from the upload already on the device; `decimate="bicubic"`: LR frames that are the
                             antialiased bicubic reduction of the source stored as 8-bit; `baseline="bicubic"`: the bicubic enlargement
-                            of the middle LR frame scored beside the estimate
+                            of the middle LR frame scored beside the estimate; `temporal="warp"`: the flow-warped error between
+                            consecutive output frames beside the per-frame scores
+    truth_flows / warp_error / ewarp   the temporal warping error on the device (include/vsr_hip_warp.h): forward and backward FlowNet2
+                            flows between ground-truth frames, frame t + 1 warped back onto frame t and the squared difference summed
+                            over the pixels that are not occluded, in float64, and the host step that forms E_warp from the sums
     save_checkpoint / load_checkpoint   utils/tools.py:68-73 and main.py:108-122,233-237: {'arch','epoch','state_dict':
                             SRmodel.model.state_dict(),'optimizer'} -- files interchange with the reference's
 
@@ -208,6 +212,106 @@ def psnr_ssim(sums) -> Tuple[np.ndarray, np.ndarray]:
     on = n_ssim > 0
     ssim[on] = ssim_sum[on] / n_ssim[on]
     return psnr, ssim
+
+
+# ------------------------------------------------------------------------------------------------ temporal warping error
+WARP_OCC = (0.01, 0.5, 0.01, 0.002)   # {c1, c2, g1, g2} of the occlusion rule (Ruder, Dosovitskiy, Brox 2016)
+_truth_flow_exec = None               # model -> its FlowNet2 executor for `truth_flows` (made on first use)
+
+
+def truth_flows(model, frames_t: torch.Tensor, frames_t1: torch.Tensor):
+    """The optical flow between ground-truth frames, the guide of `warp_error`: float32 RGB frames [P,H,W,3] (or [H,W,3]) at time t and
+    at time t + 1 -> (forward flows t -> t + 1, backward flows t + 1 -> t, crop (y0, x0, h, w)), all 2 P flows as one FlowNet2 batch over
+    the centre crop to multiples of 64, in the precision `model.precision` selects: "fp32" planar float32 [P,2,h,w]; "fp16" the executor's
+    NHWC half map [P,h,w,ld] with the flow in channels 0 and 1.  The executor is one of this function's own per model: its buffers hold
+    the geometry of the truth frames, and `model._flow_exec`, whose buffers hold the LR geometry of the windows, is left alone."""
+    global _truth_flow_exec
+    if frames_t.dim() == 3:
+        frames_t, frames_t1 = frames_t[None], frames_t1[None]
+    if tuple(frames_t.shape) != tuple(frames_t1.shape) or frames_t.dim() != 4 or frames_t.shape[-1] != 3:
+        raise ValueError(f"expected two float32 tensors of one shape [H,W,3] or [P,H,W,3], got {tuple(frames_t.shape)} and {tuple(frames_t1.shape)}")
+    P = int(frames_t.shape[0])
+    net = None
+    if model._fast():
+        import weakref
+        from .trunk_exec import FlowNet2Exec, TrunkExecCache
+        if _truth_flow_exec is None:
+            _truth_flow_exec = weakref.WeakKeyDictionary()
+        if model not in _truth_flow_exec:
+            _truth_flow_exec[model] = TrunkExecCache(model.FlowModule.net, FlowNet2Exec)
+        net = _truth_flow_exec[model].get()
+    pairs = [(frames_t[p], frames_t1[p]) for p in range(P)] + [(frames_t1[p], frames_t[p]) for p in range(P)]
+    flows, crop = model.FlowModule.flow_pairs(pairs, net)
+    return flows[:P], flows[P:], crop
+
+
+@L.on_device
+def warp_error(a: torch.Tensor, b: torch.Tensor, flows, channels: str = "rgb", quantise: bool = True, shave: int = 0, occ=None,
+               out: Optional[torch.Tensor] = None, matrix: str = "bt601", full_range: bool = False, luma4=None) -> torch.Tensor:
+    """float32 RGB frames `a` (time t) and `b` (time t + 1) ([H,W,3] or [P,H,W,3], 0..255) and `flows` = (forward, backward, crop) as
+    `truth_flows` returns them -> the device tensor [P,4] float64 of {sse, n_terms, n_valid, n_pixels} per pair (vsr_warp_error,
+    include/vsr_hip_warp.h): frame b warped back onto frame a along the forward flow, the squared difference summed over the pixels of
+    the crop that are in frame, forward-backward consistent and off a motion boundary.  Nothing is synchronised, `ewarp` is the host
+    step.  `quantise`, `shave` (counted inside the crop), `channels`, `matrix`, `full_range`: as `frame_metrics`; `luma4`: four float32
+    {a0, a1, a2, o} in place of the matrix's luma row; `occ`: {c1, c2, g1, g2}, default `WARP_OCC`; `out`: write the sums there ([P,4]
+    float64, rows of a larger tensor will do)."""
+    import ctypes
+    if channels not in METRIC_CHANNELS:
+        raise ValueError(f"unknown channels {channels!r} (known: {', '.join(METRIC_CHANNELS)})")
+    fwd, bwd, crop = flows
+    if a.dim() == 3:
+        a, b = a[None], b[None]
+    if tuple(a.shape) != tuple(b.shape) or a.dim() != 4 or a.shape[-1] != 3:
+        raise ValueError(f"expected two float32 tensors of one shape [H,W,3] or [P,H,W,3], got {tuple(a.shape)} and {tuple(b.shape)}")
+    P, H, W = int(a.shape[0]), int(a.shape[1]), int(a.shape[2])
+    y0, x0, h, w = (int(v) for v in crop)
+    shave = int(shave)
+    if h <= 0 or w <= 0 or y0 < 0 or x0 < 0 or y0 + h > H or x0 + w > W:
+        raise ValueError(f"the crop {(y0, x0, h, w)} leaves the frame of {H} x {W}")
+    if shave < 0 or 2 * shave >= min(h, w):
+        raise ValueError(f"shave {shave} leaves nothing of the crop of {h} x {w}")
+    if fwd.dtype != bwd.dtype or tuple(fwd.shape) != tuple(bwd.shape) or fwd.stride() != bwd.stride():
+        raise ValueError("the forward and the backward flows must have one dtype, shape and layout")
+    if fwd.dtype == torch.float32 and tuple(fwd.shape) == (P, 2, h, w):
+        ftype, strides = 0, (2 * h * w, h * w, 1)                                # VSR_WARP_FLOW_F32, planar
+    elif fwd.dtype == torch.float16 and fwd.dim() == 4 and tuple(fwd.shape[:3]) == (P, h, w) and fwd.shape[3] >= 2:
+        ftype, strides = 1, (h * w * int(fwd.shape[3]), 1, int(fwd.shape[3]))    # VSR_WARP_FLOW_F16, NHWC with the flow in channels 0, 1
+    else:
+        raise ValueError(f"flows must be float32 {(P, 2, h, w)} or float16 {(P, h, w)} + (ld,), got {fwd.dtype} {tuple(fwd.shape)}")
+    if luma4 is not None:
+        luma4 = np.ascontiguousarray(np.asarray(luma4, dtype=np.float32).reshape(4))
+    elif channels == "y":
+        c = yuv_coefficients("yuv420p", matrix, full_range)
+        luma4 = np.ascontiguousarray(np.array([c[0], c[1], c[2], c[9]], dtype=np.float32))
+    occ4 = np.ascontiguousarray(np.asarray(WARP_OCC if occ is None else occ, dtype=np.float64).reshape(4))
+    fa, fb = a.detach().contiguous(), b.detach().contiguous()
+    M = L.load_warp()
+    pa, pb = L.dptr(fa), L.dptr(fb)   # (raises on CPU tensors and on anything but float32)
+    pf, pg = L.dptr(fwd, fwd.dtype), L.dptr(bwd, bwd.dtype)
+    if any(t.device != fa.device for t in (fb, fwd, bwd)):
+        raise ValueError("the frames and the flows live on different devices")
+    if out is None:
+        out = torch.empty((P, 4), dtype=torch.float64, device=fa.device)
+    elif tuple(out.shape) != (P, 4) or out.device != fa.device:
+        raise ValueError(f"out must be float64 {(P, 4)} on {fa.device}, got {tuple(out.shape)} on {out.device}")
+    ws = torch.empty(int(M.vsr_warp_ws_bytes(P, h, w, shave)), dtype=torch.uint8, device=fa.device)
+    L.check(M.vsr_warp_error(pa, pb, P, H, W, y0, x0, h, w, pf, pg, ftype, strides[0], strides[1], strides[2], METRIC_CHANNELS[channels],
+                             1 if quantise else 0, shave, None if luma4 is None else luma4.ctypes.data_as(ctypes.c_void_p),
+                             occ4.ctypes.data_as(ctypes.c_void_p), L.dptr(out, torch.float64), L.dptr(ws, torch.uint8), L.stream()),
+            "warp_error", lib=M)
+    return out
+
+
+def ewarp(sums) -> Tuple[np.ndarray, np.ndarray]:
+    """The host step after `warp_error`: sums [P,4] (a tensor, copied to the host here, or an array) -> (E_warp [P] = sse / n_terms /
+    255^2, the mean squared warping error over the valid pixels in the 0..1 range of Lai et al. 2018; valid share [P] = n_valid /
+    n_pixels).  E_warp is NaN where no pixel is valid."""
+    s = sums.detach().cpu().numpy() if isinstance(sums, torch.Tensor) else np.asarray(sums)
+    s = np.asarray(s, dtype=np.float64).reshape(-1, 4)
+    e = np.full(s.shape[0], np.nan)
+    on = s[:, 2] > 0
+    e[on] = s[on, 0] / s[on, 1] / 255.0 ** 2
+    return e, s[:, 2] / s[:, 3]
 
 
 # ------------------------------------------------------------------------------------------------ resampling
@@ -497,21 +601,39 @@ class ClipRunner:
     8-bit file would hold it, the evaluation protocol of the literature.  `baseline="bicubic"` (needs `score`): per window the middle LR
     frame of the ring is enlarged to the output shape into a reused buffer and scored against the same truth with the same quantise,
     shave and channels as the estimate, into a second [T-2,4] tensor copied with the first: `metrics` gains `psnr_baseline` and
-    `ssim_baseline`.  Neither uploads or downloads a byte more; with both at their defaults the launches are the ones described above."""
+    `ssim_baseline`.  Neither uploads or downloads a byte more; with both at their defaults the launches are the ones described above.
+
+    `temporal="warp"` (needs `score`): the temporal warping error of the output (`warp_error`, Lai et al. 2018).  For every output frame
+    j >= 1 the pair (j - 1, j) is scored along the flows between the source frames j and j + 1 (`truth_flows`, both directions in one
+    FlowNet2 batch, in the model's precision): the previous estimate and the previous truth frame are kept (`_truth` is then two
+    alternating buffers), and the pair of truth frames is scored along the same flows: the floor any method sits above.  With
+    `baseline="bicubic"` the baseline pair is scored too (`_base` is then two alternating buffers).  Same channels, quantise and shave
+    (counted inside the flow's centre crop) as the per-frame scores, `occ` as `warp_error`'s (default: the published constants), into [T-3,4] tensors that travel in the one copy at the end:
+    `metrics` gains `ewarp`, `ewarp_truth`, `valid_share` (the occlusion mask depends on the flows alone: one share for all) and, with a
+    baseline, `ewarp_baseline`, each [T-3] (empty for T = 3).  No upload, download or host wait is added; with `temporal=None` the
+    launches are the ones described above."""
 
     DECIMATE = ("nearest", "bicubic")
     BASELINE = (None, "bicubic")
+    TEMPORAL = (None, "warp")
 
     def __init__(self, model, shape: Tuple[int, int], fmt_in: str, fmt_out: str, scale_down: int = 1, overlap: bool = True,
                  matrix: str = "bt709", full_range: bool = False, siting: str = "left", score: Optional[str] = None,
-                 shave: Optional[int] = None, decimate: str = "nearest", baseline: Optional[str] = None):
+                 shave: Optional[int] = None, decimate: str = "nearest", baseline: Optional[str] = None, temporal: Optional[str] = None,
+                 occ=None):
         if decimate not in self.DECIMATE:
             raise ValueError(f"decimate must be 'nearest' or 'bicubic', got {decimate!r}")
         if baseline not in self.BASELINE:
             raise ValueError(f"baseline must be None or 'bicubic', got {baseline!r}")
         if baseline is not None and score is None:
             raise ValueError(f"baseline={baseline!r} is scored beside the estimate: it needs score='rgb' or 'y'")
-        self.decimate, self.baseline = decimate, baseline
+        if temporal not in self.TEMPORAL:
+            raise ValueError(f"temporal must be None or 'warp', got {temporal!r}")
+        if temporal is not None and score is None:
+            raise ValueError(f"temporal={temporal!r} is scored beside the estimate: it needs score='rgb' or 'y'")
+        if occ is not None and temporal is None:
+            raise ValueError("occ is given but no temporal score is asked for (temporal=None)")
+        self.decimate, self.baseline, self.temporal, self.occ = decimate, baseline, temporal, occ
         self.model, self.fmt_in, self.fmt_out, self.overlap, self.siting = model, fmt_in, fmt_out, bool(overlap), siting
         H, W = int(shape[0]), int(shape[1])
         self.shape = (H, W)
@@ -541,6 +663,8 @@ class ClipRunner:
         self._dev_out = [torch.empty(self.out_bytes, dtype=torch.uint8, device=dev) for _ in range(2)]
         self._ring = [torch.empty(self.lr_shape + (3,), dtype=torch.float32, device=dev) for _ in range(3)]
         self._truth = torch.empty(self.shape + (3,), dtype=torch.float32, device=dev) if score is not None else None
+        if temporal is not None:   # the truth frame of the previous window stays: two alternating buffers
+            self._truth = [self._truth, torch.empty(self.shape + (3,), dtype=torch.float32, device=dev)]
         self._full = self._down = self._up = self._base = None
         if decimate == "bicubic":
             self._full = torch.empty(self.shape + (3,), dtype=torch.float32, device=dev)   # the frame being reduced; `_truth` is the window's
@@ -548,6 +672,8 @@ class ClipRunner:
         if baseline is not None:
             self._base = torch.empty(self.out_shape + (3,), dtype=torch.float32, device=dev)
             self._up = FrameResizer(self.lr_shape, self.out_shape, baseline, dev)
+            if temporal is not None:
+                self._base = [self._base, torch.empty(self.out_shape + (3,), dtype=torch.float32, device=dev)]
         self._s_in = torch.cuda.Stream(dev) if self.overlap else None
         self._s_out = torch.cuda.Stream(dev) if self.overlap else None
         self.h2d_bytes = self.d2h_bytes = self.frames_in = self.frames_out = 0   # of the last run()
@@ -567,6 +693,10 @@ class ClipRunner:
         with torch.cuda.device(self.device), torch.no_grad():
             sums = torch.empty((T - 2, 4), dtype=torch.float64, device=self.device) if self.score is not None else None
             sums_base = torch.empty((T - 2, 4), dtype=torch.float64, device=self.device) if self.baseline is not None else None
+            warp = self.temporal is not None
+            sums_warp = [torch.empty((T - 3, 4), dtype=torch.float64, device=self.device)
+                         for _ in range((2 + (self.baseline is not None)) if warp else 0)]   # the estimate's pairs, the truth's, the baseline's
+            prev_est = None
             main = torch.cuda.current_stream(self.device)
             s_in, s_out = (self._s_in, self._s_out) if self.overlap else (main, main)
             uploaded = [None, None]    # per input slot: the upload from its pinned buffer has finished (event on s_in)
@@ -605,11 +735,23 @@ class ClipRunner:
                     # source frame j + 1 = i - 1 is still in its upload slot (the other one of the pair): converted at full size into the
                     # reused HR buffer, then scored; the slot's next upload waits for this read as it does for the LR conversion
                     c = (i - 1) % 2
-                    yuv_ingest(self._dev_in[c], self.shape, self.fmt_in, self.coef_in, self.siting, lr_out=self._truth)
-                    frame_metrics(est[0], self._truth, self.score, True, self.shave, out=sums[j:j + 1])
+                    truth = self._truth[j % 2] if warp else self._truth
+                    base = self._base[j % 2] if warp and sums_base is not None else self._base
+                    yuv_ingest(self._dev_in[c], self.shape, self.fmt_in, self.coef_in, self.siting, lr_out=truth)
+                    frame_metrics(est[0], truth, self.score, True, self.shave, out=sums[j:j + 1])
                     if sums_base is not None:
-                        self._up(self._ring[(i - 1) % 3], quantise=False, out=self._base)
-                        frame_metrics(self._base, self._truth, self.score, True, self.shave, out=sums_base[j:j + 1])
+                        self._up(self._ring[(i - 1) % 3], quantise=False, out=base)
+                        frame_metrics(base, truth, self.score, True, self.shave, out=sums_base[j:j + 1])
+                    if warp and j >= 1:
+                        # the pair (j - 1, j) along the flows between source frames j and j + 1: the other truth buffer still holds
+                        # source frame j, `prev_est` the estimate of the window before
+                        truth_prev = self._truth[(j - 1) % 2]
+                        flows = truth_flows(self.model, truth_prev, truth)
+                        warp_error(prev_est, est[0], flows, self.score, True, self.shave, self.occ, out=sums_warp[0][j - 1:j])
+                        warp_error(truth_prev, truth, flows, self.score, True, self.shave, self.occ, out=sums_warp[1][j - 1:j])
+                        if sums_base is not None:
+                            warp_error(self._base[(j - 1) % 2], base, flows, self.score, True, self.shave, self.occ, out=sums_warp[2][j - 1:j])
+                    prev_est = est[0]
                     converted[c] = torch.cuda.Event()
                     converted[c].record(main)
                 if copied[b] is not None:   # frame j-2 leaves the slot pair: wait for its copy, take it from the pinned buffer
@@ -636,7 +778,19 @@ class ClipRunner:
             for ev in uploaded + converted:   # the slots are idle when run() returns
                 if ev is not None:
                     ev.synchronize()
-            if sums is not None:
+            if warp:
+                rows = torch.cat([sums] + ([sums_base] if sums_base is not None else []) + sums_warp).cpu().numpy()   # the one copy
+                psnr, ssim = psnr_ssim(rows[:T - 2])
+                self.metrics = {"psnr": psnr, "ssim": ssim}
+                at = T - 2
+                if sums_base is not None:
+                    self.metrics["psnr_baseline"], self.metrics["ssim_baseline"] = psnr_ssim(rows[at:at + T - 2])
+                    at += T - 2
+                self.metrics["ewarp"], self.metrics["valid_share"] = ewarp(rows[at:at + T - 3])
+                self.metrics["ewarp_truth"], _ = ewarp(rows[at + T - 3:at + 2 * (T - 3)])
+                if sums_base is not None:
+                    self.metrics["ewarp_baseline"], _ = ewarp(rows[at + 2 * (T - 3):at + 3 * (T - 3)])
+            elif sums is not None:
                 if sums_base is None:
                     psnr, ssim = psnr_ssim(sums)   # the one copy (it waits for the current stream)
                     self.metrics = {"psnr": psnr, "ssim": ssim}
@@ -721,11 +875,13 @@ def run_c1(lr: int = 128, frames: int = 3, scale: int = 4, precision: str = "fp3
 
 
 def run_c1_yuv(pix_fmt: str, lr: int = 128, frames: int = 3, scale: int = 4, precision: str = "fp32", score: Optional[str] = None,
-               decimate: str = "nearest", baseline: Optional[str] = None):
+               decimate: str = "nearest", baseline: Optional[str] = None, temporal: Optional[str] = None):
     """Config C1 with a 4:2:0 boundary: the synthetic clip as `pix_fmt` frames on the host, streamed through `ClipRunner`
     (decimated by `scale`, super-resolved by `scale`).  -> (result line, output frames uint8 [T-2, frame_bytes] on the host).
     `score`: "rgb" | "y": the line also carries the per-frame PSNR / SSIM against the synthetic HR clip.  `decimate` / `baseline`: as
-    `ClipRunner`'s; with a baseline the line carries its mean PSNR / SSIM beside the estimate's and `psnr_gain`, their difference in dB."""
+    `ClipRunner`'s; with a baseline the line carries its mean PSNR / SSIM beside the estimate's and `psnr_gain`, their difference in dB; with
+    `temporal` the clip means of E_warp of the estimate, of the truth frames (and of the baseline) and of the valid share (E_warp over the
+    pairs that have valid pixels; null where there is none, or no pair: a clip of three frames)."""
     import time
     from . import VSR
     from .weights import fill_module_
@@ -736,7 +892,8 @@ def run_c1_yuv(pix_fmt: str, lr: int = 128, frames: int = 3, scale: int = 4, pre
     model.precision = model.model.precision = precision
     video = synthetic_video(frames, S * lr, S * lr)
     clip = frames_to_yuv(torch.from_numpy(video).to(dev).float(), pix_fmt).cpu().numpy()
-    runner = ClipRunner(model, (S * lr, S * lr), pix_fmt, pix_fmt, scale_down=S, score=score, decimate=decimate, baseline=baseline)
+    runner = ClipRunner(model, (S * lr, S * lr), pix_fmt, pix_fmt, scale_down=S, score=score, decimate=decimate, baseline=baseline,
+                        temporal=temporal)
     runner.run(clip)                                                      # warm-up (packing, allocator)
     t0 = time.perf_counter()
     out = runner.run(clip)
@@ -755,6 +912,12 @@ def run_c1_yuv(pix_fmt: str, lr: int = 128, frames: int = 3, scale: int = 4, pre
                     psnr_baseline_mean_db=round(float(np.mean(m["psnr_baseline"])), 4),
                     ssim_baseline_mean=round(float(np.mean(m["ssim_baseline"])), 6),
                     psnr_gain=round(float(np.mean(m["psnr"]) - np.mean(m["psnr_baseline"])), 4))
+    if temporal is not None:
+        m = runner.metrics
+        mean = lambda v: float(np.mean(v[np.isfinite(v)])) if np.isfinite(v).any() else None   # (no pair, or no valid pixel in any: null)
+        line.update(temporal=temporal, ewarp=mean(m["ewarp"]), ewarp_truth=mean(m["ewarp_truth"]), valid_share=mean(m["valid_share"]))
+        if baseline is not None:
+            line.update(ewarp_baseline=mean(m["ewarp_baseline"]))
     return line, out
 
 
@@ -800,6 +963,8 @@ def main(argv=None):
                     help="with --pix-fmt: how the LR frames are made (nearest: the reference's decimation; bicubic: antialiased, stored as 8-bit)")
     ap.add_argument("--baseline", default=None, choices=["bicubic"],
                     help="with --score: also score the bicubic enlargement of the LR frame; the line carries both means and psnr_gain")
+    ap.add_argument("--temporal", default=None, choices=["warp"],
+                    help="with --score: also the flow-warped error between consecutive output frames (E_warp); the line carries the clip means")
     ap.add_argument("--train-steps", type=int, default=None, metavar="K",
                     help="after the no-grad windows: K train steps on the last window (optim.Adam); the line carries the loss per step")
     ap.add_argument("--max-grad-norm", type=float, default=None, metavar="X",
@@ -815,6 +980,8 @@ def main(argv=None):
         ap.error("--decimate needs --pix-fmt (the streamed clip runner makes the LR frames)")
     if args.baseline is not None and args.score is None:
         ap.error("--baseline needs --score (it is scored beside the estimate)")
+    if args.temporal is not None and args.score is None:
+        ap.error("--temporal needs --score (it is scored beside the estimate)")
     if args.max_grad_norm is not None and args.train_steps is None:
         ap.error("--max-grad-norm needs --train-steps")
     if args.train_steps is not None:
@@ -823,7 +990,8 @@ def main(argv=None):
         line, _ = run_c1_train(args.train_steps, args.lr, args.frames, args.scale, args.precision, args.max_grad_norm,
                                loss_path=args.loss_path or "reference")
     elif args.pix_fmt is not None:
-        line, _ = run_c1_yuv(args.pix_fmt, args.lr, args.frames, args.scale, args.precision, args.score, args.decimate, args.baseline)
+        line, _ = run_c1_yuv(args.pix_fmt, args.lr, args.frames, args.scale, args.precision, args.score, args.decimate, args.baseline,
+                             args.temporal)
     else:
         line, _, _, _ = run_c1(args.lr, args.frames, args.scale, args.precision)
     print(json.dumps(line))

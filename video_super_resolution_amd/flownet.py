@@ -269,29 +269,42 @@ class FlowProjectionModule(nn.Module):
     def forward_pairs(self, pairs, net=None):
         """Several frame pairs as ONE FlowNet2 batch (independent samples: same arithmetic per pair, fewer and
         better filled launches) -> colour pictures [B,h',w',3].  `net`: an execution copy of self.net (e.g. fp16)."""
+        flows, (_, _, th, tw) = self.flow_pairs(pairs, net)
         if net is not None and hasattr(net, "run_pairs"):
             # fp16 executor: the frames go in as they are (crop, normalisation and layout inside prepare_pairs), the flow
             # comes back as the fusion network's NHWC half map and is colour-coded from there
-            distinct, keys = [], []
-            for t in (t for pr in pairs for t in pr):
-                k = (t.data_ptr(), tuple(t.shape))
-                if k not in keys:
-                    keys.append(k)
-                    distinct.append(t)
-            h, w = distinct[0].shape[:2]
-            th, tw = (h // 64) * 64, (w // 64) * 64
-            if th == 0 or tw == 0:
-                raise ValueError("FlowNet2 needs frames of at least 64x64 (centre crop to multiples of 64)")
-            self.image_size, self.render_size = (h, w), [th, tw]
-            idx = [(keys.index((a.data_ptr(), tuple(a.shape))), keys.index((b.data_ptr(), tuple(b.shape)))) for a, b in pairs]
-            out = net.run_pairs(torch.stack(distinct), idx, ((h - th) // 2, (w - tw) // 2, th, tw))   # StaticCenterCrop, tools.py:8-14
-            pics = torch.empty((len(pairs), th, tw, 3), dtype=torch.float32, device=out.device)
+            pics = torch.empty((len(pairs), th, tw, 3), dtype=torch.float32, device=flows.device)
             for b in range(len(pairs)):
-                ops.flow2img_nhwc(out[b], out=pics[b])   # the colour coding normalises by a per-picture maximum
+                ops.flow2img_nhwc(flows[b], out=pics[b])   # the colour coding normalises by a per-picture maximum
             return pics
-        batch = torch.stack([self._crop_pair(a, b) for a, b in pairs])  # [B,3,2,h',w']
-        flows = (net or self.net)(batch)
         return torch.stack([ops.flow2img(f) for f in flows])  # the colour coding normalises by a per-picture maximum
+
+    @torch.no_grad()
+    def flow_pairs(self, pairs, net=None):
+        """What `forward_pairs` colour-codes: the raw flows of several [h,w,3] frame pairs as one FlowNet2 batch over the centre
+        crop -> (flows, (y0, x0, h', w')).  Without an executor: float32 [B,2,h',w'] (channel 0 along x, 1 along y, in pixels).  `net`
+        an fp16 executor: `run_pairs`' NHWC half map [B,h',w',ld] as it is, the flow in channels 0 and 1 (its glue launches take four
+        pairs at a time: more than four run as consecutive batches of four and come back concatenated)."""
+        h, w = pairs[0][0].shape[:2]
+        th, tw = (h // 64) * 64, (w // 64) * 64
+        if th == 0 or tw == 0:
+            raise ValueError("FlowNet2 needs frames of at least 64x64 (centre crop to multiples of 64)")
+        self.image_size, self.render_size = (h, w), [th, tw]
+        crop = ((h - th) // 2, (w - tw) // 2, th, tw)   # StaticCenterCrop, tools.py:8-14
+        if net is not None and hasattr(net, "run_pairs"):
+            outs = []
+            for c0 in range(0, len(pairs), 4):
+                distinct, keys = [], []
+                for t in (t for pr in pairs[c0:c0 + 4] for t in pr):
+                    k = (t.data_ptr(), tuple(t.shape))
+                    if k not in keys:
+                        keys.append(k)
+                        distinct.append(t)
+                idx = [(keys.index((a.data_ptr(), tuple(a.shape))), keys.index((b.data_ptr(), tuple(b.shape)))) for a, b in pairs[c0:c0 + 4]]
+                outs.append(net.run_pairs(torch.stack(distinct), idx, crop))
+            return (outs[0] if len(outs) == 1 else torch.cat(outs, 0)), crop
+        batch = torch.stack([self._crop_pair(a, b) for a, b in pairs])  # [B,3,2,h',w']
+        return (net or self.net)(batch).contiguous(), crop
 
     @torch.no_grad()
     def forward(self, input1, input2):
