@@ -146,7 +146,7 @@ int vsr_sr_conv1x1_f32(const float* in0, const float* w0, int ldw0, const float*
  * in [N,32,h,w] <-> [N,32,scale*h,scale*w]; weight_packed [ky][kx][in][out] as above with K x K taps.
  * dt_frags (optional, null: none): the FeedbackBlock's downtran 1x1 + PReLU (SRProjectionModule.py:77-79; the x S map's only consumer
  * under the zero-fill semantic) applied to the tile before it is stored: out = PReLU(W_dt . PReLU(deconv) + dt_bias, dt_slope).
- * dt_frags [16][64] float32: fragment r, lane l = W_dt[out = l % 32][in = 8 (r / 4) + 4 (l / 32) + r % 4] (sr.py:pack_dt_frags). */
+ * dt_frags [16][64] float32: fragment r, lane l = W_dt[out = l % 32][in = 8 (r / 4) + 4 (l / 32) + r % 4] (sr_pack.py:pack_dt_frags). */
 int vsr_sr_deconv_f32(const float* in, const float* weight_packed, const float* bias, float slope, float* out, int N,
                       int h, int w, int scale, const float* dt_frags, const float* dt_bias, float dt_slope, vsr_stream_t stream);
 int vsr_sr_conv_f32(const float* in, const float* weight_packed, const float* bias, float slope, float* out, int N,
@@ -201,13 +201,13 @@ int vsr_sr_utd_f16(const void* in, const void* blob, void* out, int N, int h, in
 /* vsr_sr_utd_f16 + the NEXT group's uptran slice (1x1 32 -> 32 + PReLU, SRProjectionModule.py:55-61 under zero fill) applied to every
  * finished output row inside the same launch: out [N,h,w,32] as above, out_post [N,h,w,32] fp16 = PReLU(W out + b) -- bit for bit
  * what vsr_sr_chain1x1_f16 (one stage, one input) makes of `out`.  W [mt 2][lane 64][8] fp16 fragments (natural channel order), b[32]
- * and the slope (fp32) travel in the blob's compress_out region (sr.py:pack_utd_blob(post=...)); slopes_le_one covers that slope too. */
+ * and the slope (fp32) travel in the blob's compress_out region (sr_pack.py:pack_utd_blob(post=...)); slopes_le_one covers that slope too. */
 int vsr_sr_utd_post_f16(const void* in, const void* blob, void* out, void* out_post, int N, int h, int w, int rows_per_seg, int slopes_le_one,
                         vsr_stream_t stream);
 /* The same fused stage on v_mfma_f32_32x32x16_f16 (k_utd4, csrc/sr_utd4.hip: 72 matrix instructions per LR row instead of 144 -- one
  * wave per SIMD pays ~8 cycles of issue per MFMA whatever its shape, and k_utd3's row was issue-bound; the default build of the
  * stage).  Arguments as vsr_sr_utd_f16 / vsr_sr_utd_post_f16 (out_post_or_null = NULL: no uptran slice); blob packed by
- * sr.py:pack_utd_blob(layout=4) -- same regions and sizes, fragments in the 32 x 32 operand layout, K index in the accumulator's
+ * sr_pack.py:pack_utd_blob(layout=4) -- same regions and sizes, fragments in the 32 x 32 operand layout, K index in the accumulator's
  * channel order.  Same values as vsr_sr_utd_f16 up to the fp32 summation order of the K dimension (not bit-identical). */
 int vsr_sr_utd4_f16(const void* in, const void* blob, void* out, void* out_post_or_null, int N, int h, int w, int rows_per_seg,
                     int slopes_le_one, vsr_stream_t stream);
@@ -246,7 +246,7 @@ int vsr_sr_head_f16(const float* x, const float* sub_scale3, const float* sub_bi
  * the 3x3 turned around so that the wave holding an HR row forms that row's contribution to its three output rows (M row
  * 4 dy + co) and only fp32 partial sums cross waves.  Writes the RAW planes raw [N,3,4h,4w] fp32 = conv_out(PReLU(out
  * deconv)) + bias; the bilinear skip and add_mean are applied by vsr_sr_fc_planes_skip_f32, which reads the planes next.
- * conv3_frags: [dx 3][lane 64][8] fp16 (sr.py:pack_conv_out_frags3); tail_params: fp32 b_out[3] sub_scale[3] sub_bias[3] add_scale[3] add_bias[3].  decimate != 0:
+ * conv3_frags: [dx 3][lane 64][8] fp16 (sr_pack.py:pack_conv_out_frags3); tail_params: fp32 b_out[3] sub_scale[3] sub_bias[3] add_scale[3] add_bias[3].  decimate != 0:
  * raw is [N,3,h,w], the pixels (4i,4j).  The pair the forward runs (the LDS-ring tail of the cross-check library, vsr_hip_xcheck.h, is the
  * LDS-ring build with the skip inside the tail (agree up to fp32 summation order). */
 int vsr_sr_tail3_f16(const void* hid_nhwc, const void* blob, const void* conv3_frags, const float* tail_params, float* raw,
@@ -267,7 +267,7 @@ int vsr_sr_fc_planes_skip_f32(const float* raw, const float* x, const float* tai
                               vsr_stream_t stream);
 
 /* The fused up -> tran -> down stage for the scale-2 extension (k6 s2 p2; csrc/sr_utd_s2.hip): vsr_sr_utd_f16's x2 sibling.
- * in / out [N,h,w,32] fp16 NHWC; blob = vsr_sr_query(VSR_Q_UTD_S2_BLOB_BYTES) bytes packed by sr.py:pack_utd_s2_blob
+ * in / out [N,h,w,32] fp16 NHWC; blob = vsr_sr_query(VSR_Q_UTD_S2_BLOB_BYTES) bytes packed by sr_pack.py:pack_utd_s2_blob
  * ([wave 4][tap 9][mt 2] deconv fragments, [wave 4][kernel-row slot 3][shift 3][mt 2] conv fragments, 2 fragments of the 1x1,
  * then b_up[32] b_dt[32] b_dn[32] slope_up slope_dt slope_dn as fp32); strips of vsr_sr_query(VSR_Q_UTD_S2_STRIP_WIDTH) = 30 LR columns. */
 int vsr_sr_utd_s2_f16(const void* in, const void* blob, void* out, int N, int h, int w, int rows_per_seg, int slopes_le_one,
@@ -275,26 +275,26 @@ int vsr_sr_utd_s2_f16(const void* in, const void* blob, void* out, int N, int h,
 /* The same launch + the NEXT group's uptran slice (1x1 + PReLU, SRProjectionModule.py:55-61 under the zero-fill semantic) applied to
  * every finished output row: out_post [N,h,w,32] fp16 = what vsr_sr_chain1x1_f16 would make of `out` (bit-identical), without the
  * HBM round trip (at x2 that launch costs a sixth of the stage).  The blob carries the 1x1 behind the stage's parameters
- * (sr.py:pack_utd_s2_blob(post=...): 2 fragments in natural channel order, b_post[32], slope_post). */
+ * (sr_pack.py:pack_utd_s2_blob(post=...): 2 fragments in natural channel order, b_post[32], slope_post). */
 int vsr_sr_utd_s2_post_f16(const void* in, const void* blob, void* out, void* out_post, int N, int h, int w, int rows_per_seg,
                            int slopes_le_one, vsr_stream_t stream);
 /* The same x2 stage on v_mfma_f32_32x32x16_f16 with one wave per SIMD (k_utd_s2w, csrc/sr_utd_s2w.hip: 38 matrix instructions per step
  * instead of 76 in each of two waves that share a SIMD's issue port; opt-in, measured 5 % slower).  Arguments as vsr_sr_utd_s2_f16; blob packed by
- * sr.py:pack_utd_s2_blob(layout=4) -- same regions and size, fragments in the 32 x 32 operand layout.  Same values up to the fp32
+ * sr_pack.py:pack_utd_s2_blob(layout=4) -- same regions and size, fragments in the 32 x 32 operand layout.  Same values up to the fp32
  * summation order of the K dimension (not bit-identical). */
 int vsr_sr_utd_s2w_f16(const void* in, const void* blob, void* out, int N, int h, int w, int rows_per_seg, int slopes_le_one,
                        vsr_stream_t stream);
 
 /* The tail for the scale-2 extension in one launch (csrc/sr_tail_s2.hip): `out` DeconvBlock (k6 s2 p2 + PReLU) -> conv_out 3x3
  * (32 -> 3, bias) -> raw planes [N,3,2h,2w] fp32 (decimate != 0: the pixels (2i, 2j) only -> [N,3,h,w]); the x2 map stays in
- * LDS.  hid_nhwc [N,h,w,32] fp16; blob = vsr_sr_query(VSR_Q_TAIL_S2_BLOB_BYTES) bytes packed by sr.py:pack_tail_s2_blob.  Followed by
+ * LDS.  hid_nhwc [N,h,w,32] fp16; blob = vsr_sr_query(VSR_Q_TAIL_S2_BLOB_BYTES) bytes packed by sr_pack.py:pack_tail_s2_blob.  Followed by
  * vsr_sr_fc_planes_skip_scale_f32 (skip + add_mean + fusion MLP). */
 int vsr_sr_tail_s2_f16(const void* hid_nhwc, const void* blob, float* raw, int N, int h, int w, int rows_per_seg, int slopes_le_one,
                        int decimate, vsr_stream_t stream);
 /* The same with the FeedbackBlock's last compress_out (1x1 over the two live LR maps lr_a, lr_b [N,h,w,32] fp16 + the constant map
  * cmap_nhwc [h*w,32] fp32 + PReLU, SRProjectionModule.py:99) applied in the kernel's LR load path instead of by a vsr_sr_chain1x1_f16
  * launch: bit-identical planes (the 1x1 in that kernel's operation order, its output in natural channel order in LDS).  The blob
- * carries the 1x1 behind the tail's parameters (sr.py:pack_tail_s2_blob(fold_co=...)). */
+ * carries the 1x1 behind the tail's parameters (sr_pack.py:pack_tail_s2_blob(fold_co=...)). */
 int vsr_sr_tail_s2_fold_f16(const void* lr_a, const void* lr_b, const float* cmap_nhwc, const void* blob, float* raw, int N, int h, int w,
                             int rows_per_seg, int slopes_le_one, int decimate, vsr_stream_t stream);
 

@@ -73,14 +73,14 @@ int vsr_sr_utd_stamp_buffer(void* device_buf);
 int vsr_sr_tail_stamp_buffer(void* device_buf, int totals_only);
 
 /* The fused stage with specialised wave roles (4 producer waves: deconv + 1x1 into the LDS ring; 4 consumer waves: stride-4 conv
- * out of it): 7 % slower than k_utd3.  blob_v2: sr.py:pack_utd_blob(..., layout=2). */
+ * out of it): 7 % slower than k_utd3.  blob_v2: sr_pack.py:pack_utd_blob(..., layout=2). */
 int vsr_sr_utd2_f16(const void* in, const void* blob_v2, void* out, int N, int h, int w, int rows_per_seg, int slopes_le_one,
                     vsr_stream_t stream);
 
 /* The LDS-ring tail k_tail (superseded by k_tail3): hid [N,h,w,32] fp16 -> `out` DeconvBlock -> conv_out 3x3 + bilinear x4 skip
  * of sub_mean(x) + add_mean -> pre-fusion planes prefc [N,3,4h,4w] fp32 (SRProjectionModule.py:118-123,136,142-143); _dec: only
  * the pixels (4i, 4j), prefc_dec [N,3,h,w].  blob: a deconv-only stage blob of the `out` block; conv_out_frags: 9 MFMA
- * A-fragments [tap][lane 64][8] fp16 (sr.py:pack_conv_out_frags).  Serves the `prefc` tap of the tests. */
+ * A-fragments [tap][lane 64][8] fp16 (sr_pack.py:pack_conv_out_frags).  Serves the `prefc` tap of the tests. */
 int vsr_sr_tail_f16(const void* hid_nhwc, const void* blob, const void* conv_out_frags, const float* tail_params,
                     const float* x, float* prefc, int N, int h, int w, int rows_per_seg, int slopes_le_one,
                     vsr_stream_t stream);

@@ -157,7 +157,7 @@ def test_import_path_shim_and_train_mode_keeps_guidance_frozen(cpu_vsr):
 
 
 def test_chunk_channel_order_is_a_permutation():
-    from video_super_resolution_amd.sr import _chunk_channel_order
+    from video_super_resolution_amd.sr_pack import _chunk_channel_order
     p = _chunk_channel_order("cpu")
     assert sorted(p.reshape(-1).tolist()) == list(range(32))
     assert p[1].tolist() == [4, 5, 6, 7, 20, 21, 22, 23]

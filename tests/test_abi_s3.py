@@ -93,7 +93,7 @@ def test_check_reports_from_the_s3_librarys_own_buffer():
 
 
 def test_pack_utd_s3_blob_on_cpu_tensors_has_the_size_the_library_reports():
-    from video_super_resolution_amd.sr import _S3_PHASES, _s3_taps, pack_utd_s3_blob
+    from video_super_resolution_amd.sr_pack import _S3_PHASES, _s3_taps, pack_utd_s3_blob
     g = torch.Generator().manual_seed(0)
     up_w, dn_w = torch.randn(32, 32, 7, 7, generator=g), torch.randn(32, 32, 7, 7, generator=g)
     tr_w = torch.randn(32, 96, generator=g)

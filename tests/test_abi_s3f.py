@@ -150,7 +150,7 @@ def _operands(seed=0):
 
 
 def _pack(slopes, seed=0):
-    from video_super_resolution_amd.sr import pack_utd_s3_post_blob, pack_utd_s3_pre_blob
+    from video_super_resolution_amd.sr_pack import pack_utd_s3_post_blob, pack_utd_s3_pre_blob
     stage, post, (co_w, ci_w, ut_w, pb) = _operands(seed)
     post_blob = pack_utd_s3_post_blob(*stage, post=post)
     blob = pack_utd_s3_pre_blob(post_blob, (co_w, (64, 160), pb[0], slopes[0]), (ci_w, pb[1], slopes[1]), (ut_w, 32, pb[2], slopes[2]))

@@ -126,7 +126,7 @@ def _operands(seed=0):
 
 
 def test_pack_utd_s3_post_blob_has_the_queried_size_the_plain_stage_part_and_the_headers_post_section():
-    from video_super_resolution_amd.sr import pack_utd_s3_blob, pack_utd_s3_post_blob
+    from video_super_resolution_amd.sr_pack import pack_utd_s3_blob, pack_utd_s3_post_blob
     up_w, dn_w, tr_w, ut_w, b = _operands()
     args = (up_w, b[0], 0.25, tr_w, 32, b[1], 0.5, dn_w, b[2], -0.75)
     blob = pack_utd_s3_post_blob(*args, post=(ut_w, 128, b[3], 1.5))
@@ -149,7 +149,7 @@ def test_float64_restatement_of_the_quadrant_products_on_the_decoded_blob(slope)
     """Wave wv multiplies out-channel tile pmt = wv / 2 with pixel tile wv % 2: A[row = lane % 16][k = 8 (lane / 16) + j] from the blob's
     POST section, B[k][col = lane % 16] = the output row's pixel 16 (wv % 2) + col, channels 8 (lane / 16) .. + 7 as they lie in memory,
     C = the bias of channels 16 pmt + 4 (lane / 16) .. + 3; lane (col, g) then holds channels 16 pmt + 4 g + e of its pixel."""
-    from video_super_resolution_amd.sr import pack_utd_s3_post_blob
+    from video_super_resolution_amd.sr_pack import pack_utd_s3_post_blob
     up_w, dn_w, tr_w, ut_w, b = _operands(1)
     # operands of the 1x1 as multiples of 2^-10 below 2: fp16 values whose products are multiples of 2^-20, so every 32-term sum (< 2^8) is
     # exact in float64 in ANY order, while it has more bits than fp16 keeps: the two roundings are exercised and the comparison is an equality

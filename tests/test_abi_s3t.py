@@ -120,7 +120,7 @@ def _perm(g, j):
 
 
 def test_pack_tail_s3_blob_on_cpu_tensors_has_the_queried_sizes_and_the_headers_layout():
-    from video_super_resolution_amd.sr import _S3_PHASES, _s3_taps, pack_tail_s3_blob, pack_utd_s3_blob
+    from video_super_resolution_amd.sr_pack import _S3_PHASES, _s3_taps, pack_tail_s3_blob, pack_utd_s3_blob
     out_w, out_b, cv_w, cv_b, co_w, co_b = _operands()
     T = _lib.load_s3t()
     plain = pack_tail_s3_blob(out_w, out_b, 0.25, cv_w, cv_b)

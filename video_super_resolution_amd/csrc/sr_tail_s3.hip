@@ -67,7 +67,7 @@ constexpr int T3_BLOB_BYTES = T3_BLOB_F32 + 512;
 constexpr int T3_BLOB_CO = T3_BLOB_BYTES;                     // FOLD: [map 2][mt 2][lane 64][8] fp16 (natural channel order), then b_co[32], slope_co (64 floats)
 constexpr int T3_BLOB_FOLD_BYTES = T3_BLOB_CO + 4096 + 256;
 
-// ---- the waves' phase sets and the slot order of their tap fragments (as csrc/sr_utd_s3.hip; sr.py:pack_tail_s3_blob restates these)
+// ---- the waves' phase sets and the slot order of their tap fragments (as csrc/sr_utd_s3.hip; sr_pack.py:pack_tail_s3_blob restates these)
 constexpr int ph_cnt(int wv) { return wv == 3 ? 3 : 2; }
 constexpr int ph_r(int wv, int p) { return wv == 0 ? (p == 0 ? 1 : 0) : wv == 2 ? 1 : (p == 0 ? 0 : 2); }
 constexpr int ph_c(int wv, int p) { return wv == 0 ? (p == 0 ? 1 : 0) : wv == 1 ? 1 : wv == 2 ? (p == 0 ? 0 : 2) : (p == 1 ? 0 : 2); }

@@ -15,7 +15,7 @@
 // register 4 (i / 8) + i % 4.  i = out-channel, j = deconv position / output pixel of the strip (0..31), k = 16 channels of a K block.
 // A lane's accumulator therefore holds channels c(r) = 8 (r / 4) + 4 kh + r % 4 (kh = lane / 32) of pixel j; PReLU'd and packed to
 // fp16 pairs, registers 8 kb .. 8 kb + 7 ARE the B operand of K block kb of the next product, whose weights are packed in that
-// channel order: ch(kb, kh, e) = 16 kb + 8 (e / 4) + 4 kh + e % 4  (sr.py: pack_utd_blob(layout=4)).
+// channel order: ch(kb, kh, e) = 16 kb + 8 (e / 4) + 4 kh + e % 4  (sr_pack.py: pack_utd_blob(layout=4)).
 // The sums run in another order than k_utd3's (two K blocks of 16 instead of one of 32 per instruction): equal to rounding, not bit for bit.
 #include "sr_f16_common.h"
 
@@ -621,7 +621,7 @@ k_utd4(const _Float16* __restrict__ in, const unsigned char* __restrict__ blob, 
 
 namespace vsr {
 
-// launch of the fused stage on k_utd4 (blob: sr.py pack_utd_blob(layout=4)); out2 != nullptr: + the next group's uptran 1x1 (POST)
+// launch of the fused stage on k_utd4 (blob: sr_pack.py pack_utd_blob(layout=4)); out2 != nullptr: + the next group's uptran 1x1 (POST)
 int launch_utd4(const void* in, const void* blob, void* out, void* out2, int N, int h, int w, int rows_per_seg, int slopes_le_one, hipStream_t stream) {
     typedef void (*kern_t)(const _Float16*, const unsigned char*, _Float16*, int, int, int, int, _Float16*);
     static const kern_t kerns[4] = {k_utd4<false, 0>, k_utd4<true, 0>, k_utd4<false, 1>, k_utd4<true, 1>};

@@ -10,7 +10,7 @@
 // Wave (r, c) = (HR row parity, HR column parity) as in k_utd_s2; lane = deconv position n (0..31 <-> LR column x0 - 1 + n) + 32 kh.  The three
 // output rows in flight live in three accumulator tuples whose ROLES rotate from step to step (compile-time, the step is instantiated
 // three times): the kernel rows r, r + 2, r + 4 of a step go to rows m + 1, m, m - 1 in place, no accumulator is ever moved.
-// Channel order of the operands: ch(kb, kh, e) = 16 kb + 8 (e / 4) + 4 kh + e % 4 (sr.py: pack_utd_s2_blob(layout=4)).
+// Channel order of the operands: ch(kb, kh, e) = 16 kb + 8 (e / 4) + 4 kh + e % 4 (sr_pack.py: pack_utd_s2_blob(layout=4)).
 #include <type_traits>
 #include "sr_f16_common.h"
 

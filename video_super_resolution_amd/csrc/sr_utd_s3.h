@@ -82,7 +82,7 @@ constexpr int S3_BLOB_PRE = S3_BLOB_POST_BYTES;
 constexpr int S3_BLOB_PRE_F32 = S3_BLOB_PRE + 12 * 1024;
 constexpr int S3_BLOB_PRE_BYTES = S3_BLOB_PRE_F32 + 512;
 
-// ---- the waves' phase sets and the slot order of their tap fragments (sr.py:pack_utd_s3_blob restates these)
+// ---- the waves' phase sets and the slot order of their tap fragments (sr_pack.py:pack_utd_s3_blob restates these)
 constexpr int ph_cnt(int wv) { return wv == 3 ? 3 : 2; }
 constexpr int ph_r(int wv, int p) { return wv == 0 ? (p == 0 ? 1 : 0) : wv == 2 ? 1 : (p == 0 ? 0 : 2); }
 constexpr int ph_c(int wv, int p) { return wv == 0 ? (p == 0 ? 1 : 0) : wv == 1 ? 1 : wv == 2 ? (p == 0 ? 0 : 2) : (p == 1 ? 0 : 2); }

@@ -29,6 +29,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from .sr_pack import (_append_post_s3, pack_conv_out_frags, pack_conv_out_frags3, pack_dt_frags, pack_tail_s2_blob, pack_tail_s3_blob,
+                      pack_utd_blob, pack_utd_s2_blob, pack_utd_s3_blob, pack_utd_s3_pre_blob)
 
 _NF = 32  # the kernels are specialised for the reference's num_features
 
@@ -92,17 +94,6 @@ class FeedbackBlock(nn.Module):
 
     def forward(self, x):  # pragma: no cover - the block is evaluated by SRProjectionModule's fused pipeline
         raise RuntimeError("FeedbackBlock is a parameter container; call SRProjectionModule.forward")
-
-
-def pack_dt_frags(dt_w: torch.Tensor, col: int) -> torch.Tensor:
-    """The 32 x 32 slice [:, col:col+32] of a downtran weight matrix [32(out), ld(in)] as the 16 A-operand fragments of the fused tail of
-    csrc/sr_f32_mfma.hip:k_deconv_mfma_sh<.., DT>: fragment r, lane l = W[out = l % 32][in = 8 (r // 4) + 4 (l // 32) + r % 4]."""
-    w = dt_w[:, col:col + _NF].detach().float()
-    r = torch.arange(16).view(16, 1)
-    l = torch.arange(64).view(1, 64)
-    ci = 8 * (r // 4) + 4 * (l // 32) + r % 4
-    co = (l % 32).expand(16, 64)
-    return w[co.to(w.device), ci.to(w.device)].contiguous()
 
 
 class SRProjectionModule(nn.Module):
@@ -196,39 +187,38 @@ class SRProjectionModule(nn.Module):
         G = b.num_groups
         P["slopes_le_one"] = all(a <= 1.0 for a in P["up_a"] + P["dn_a"] + P["dt_a"] + [P["out_a"]])
         P["tail_par"] = torch.cat((P["cv_b"], P["sub_s"], P["sub_b"], P["add_s"], P["add_b"])).contiguous()
+        # post[j]: the uptran slice of the group after stage j, applied inside that stage's launch; only where another stage follows
+        post = {j: (P["ut_w"][j + 3], _NF * (j + 4), P["ut_b"][j + 3], P["ut_a"][j + 3]) for j in range(0, G - 5, 3)}
+        # compress_out reads exactly two live maps (lr3, lr6): folded into the tail's LR load path
+        fold_co = (P["co_w"], (_NF * 2, _NF * 5), P["co_b"], P["co_a"]) if G == 6 else None
         if self.upscale_factor != 4:
             # scale extension: the stage in one launch (x2: k_utd_s2, x3: k_utd_s3) or, with fused_s2 / fused_s3 off, as separate
             # launches on the generic NHWC fp16 MFMA convolution (igemm.py)
             def stage(j):
                 args = (b.upBlocks[j + 1], P["dt_w"][j + 1], _NF * (j + 2), P["dt_b"][j + 1], P["dt_a"][j + 1], b.downBlocks[j + 2])
                 if self.upscale_factor == 2 and self.fused_s2:
-                    # (with the next group's uptran slice when another stage follows: applied inside the launch, `fuse_uptran`)
-                    post = (P["ut_w"][j + 3], _NF * (j + 4), P["ut_b"][j + 3], P["ut_a"][j + 3]) if j + 6 <= G else None
-                    return _FusedStageS2(*args, slopes_le_one=P["slopes_le_one"], rows_fn=self._rows_per_segment, wide=self.utd_s2_build == 2, post=post)
+                    # (with the next group's uptran slice: `fuse_uptran`)
+                    return _FusedStageS2(*args, slopes_le_one=P["slopes_le_one"], rows_fn=self._rows_per_segment, wide=self.utd_s2_build == 2, post=post.get(j))
                 if self.upscale_factor == 3 and self.fused_s3:
                     return _FusedStageS3(*args, slopes_le_one=P["slopes_le_one"], rows_fn=self._rows_per_segment)
                 return _UnfusedStage(*args, self.upscale_factor)
             P["stage"] = {j: stage(j) for j in range(0, G - 2, 3)}
             if self.upscale_factor == 3 and self.fused_s3:
                 # the same stage with the next group's uptran slice inside the launch, where another stage follows (as x4's P["utd_post"])
-                P["stage_post"] = {j: _FusedStageS3Post(P["stage"][j], (P["ut_w"][j + 3], _NF * (j + 4), P["ut_b"][j + 3], P["ut_a"][j + 3]),
-                                                        rows_fn=self._rows_per_segment) for j in range(0, G - 5, 3)}
+                P["stage_post"] = {j: _FusedStageS3Post(P["stage"][j], post[j], rows_fn=self._rows_per_segment) for j in post}
                 if G == 6:
                     # ... and with the step-opening 1x1 chain in its LR load path (`fold_chain`; compress_out reads exactly two live maps)
-                    P["stage_pre"] = {0: _FusedStageS3Pre(P["stage_post"][0], (P["co_w"], (_NF * 2, _NF * 5), P["co_b"], P["co_a"]),
-                                                          (P["ci_w"], P["ci_b"], P["ci_a"]), (P["ut_w"][0], _NF, P["ut_b"][0], P["ut_a"][0]),
-                                                          rows_fn=self._rows_per_segment)}
+                    P["stage_pre"] = {0: _FusedStageS3Pre(P["stage_post"][0], fold_co, (P["ci_w"], P["ci_b"], P["ci_a"]),
+                                                          (P["ut_w"][0], _NF, P["ut_b"][0], P["ut_a"][0]), rows_fn=self._rows_per_segment)}
             P["out_deconv"] = _PhaseDeconv(self.out[0].weight, self.out[0].bias, P["out_a"], self.upscale_factor)
             if self.upscale_factor == 2 and self.fused_s2:
                 P["tail_s2"] = pack_tail_s2_blob(self.out[0].weight, self.out[0].bias, P["out_a"], self.conv_out[0].weight,
-                                                 self.conv_out[0].bias,
-                                                 fold_co=(P["co_w"], (_NF * 2, _NF * 5), P["co_b"], P["co_a"]) if G == 6 else None)
-                P["tail_s2_fold"] = G == 6   # compress_out reads exactly two live maps (lr3, lr6): folded into the tail's LR load path
+                                                 self.conv_out[0].bias, fold_co=fold_co)
+                P["tail_s2_fold"] = fold_co is not None
             if self.upscale_factor == 3 and self.fused_tail_s3:
                 P["tail_s3"] = pack_tail_s3_blob(self.out[0].weight, self.out[0].bias, P["out_a"], self.conv_out[0].weight,
-                                                 self.conv_out[0].bias,
-                                                 fold_co=(P["co_w"], (_NF * 2, _NF * 5), P["co_b"], P["co_a"]) if G == 6 else None)
-                P["tail_s3_fold"] = G == 6   # as at x2
+                                                 self.conv_out[0].bias, fold_co=fold_co)
+                P["tail_s3_fold"] = fold_co is not None
             self._pack, self._pack_key = P, key
             self._const.clear()
             self._const_nhwc.clear()
@@ -241,15 +231,13 @@ class SRProjectionModule(nn.Module):
             P["utd"][j] = pack_utd_blob(*args)             # k_utd (every wave both phases)
             P["utd2"][j] = pack_utd_blob(*args, layout=2)  # k_utd2 (producer / consumer waves)
             # k_utd4 (v_mfma_f32_32x32x16_f16; the default build of the stage); with the next group's uptran slice when another stage follows
-            post = (P["ut_w"][j + 3], _NF * (j + 4), P["ut_b"][j + 3], P["ut_a"][j + 3]) if j + 6 <= G else None
-            P["utd4"][j] = pack_utd_blob(*args, layout=4, post=post)
-            if j + 6 <= G:   # another stage follows: its input = the uptran slice of this stage's output, applied inside this launch
-                P["utd_post"][j] = pack_utd_blob(*args, post=post)
+            P["utd4"][j] = pack_utd_blob(*args, layout=4, post=post.get(j))
+            if j in post:   # another stage follows: its input = the uptran slice of this stage's output, applied inside this launch
+                P["utd_post"][j] = pack_utd_blob(*args, post=post[j])
         P["post_slopes_le_one"] = P["slopes_le_one"] and all(a <= 1.0 for a in P["ut_a"])
         P["utd_out"] = pack_utd_blob(self.out[0].weight, self.out[0].bias, P["out_a"], None, 0, None, 1.0, None, None, 1.0)
-        if G == 6:   # compress_out reads exactly two live maps (lr3, lr6): folded into the tail's LR path
-            P["utd_out_fold"] = pack_utd_blob(self.out[0].weight, self.out[0].bias, P["out_a"], None, 0, None, 1.0, None, None, 1.0,
-                                              fold_co=(P["co_w"], (_NF * 2, _NF * 5), P["co_b"], P["co_a"]))
+        if fold_co is not None:
+            P["utd_out_fold"] = pack_utd_blob(self.out[0].weight, self.out[0].bias, P["out_a"], None, 0, None, 1.0, None, None, 1.0, fold_co=fold_co)
         P["cv_frags"] = pack_conv_out_frags(self.conv_out[0].weight)
         P["cv_frags3"] = pack_conv_out_frags3(self.conv_out[0].weight)
         self._pack, self._pack_key = P, key
@@ -1115,118 +1103,6 @@ class _PhaseDeconv:
         return out
 
 
-def pack_utd_s2_blob(up_w, up_b, up_a, tr_w, tr_col0, tr_b, tr_a, dn_w, dn_b, dn_a, layout: int = 1, post=None) -> torch.Tensor:
-    """Weights of one fused x2 stage in the per-wave MFMA fragment order of csrc/sr_utd_s2.hip.  Wave (r, c) = (HR row parity,
-    HR column parity): deconv tap (dy, dx) is kernel element (r + 2 dy, c + 2 dx) of the ConvTranspose2d weight
-    [32(in),32(out),6,6]; conv slot (k, s) is kernel element (r + 2 k, c + 2 s) of the Conv2d weight [32(out),32(in),6,6].
-    post = (w [32,ld], col0, b [32], a): the 1x1 + PReLU that vsr_sr_utd_s2_post_f16 applies to every finished output row (the next
-    group's uptran slice), behind the stage's parameters."""
-    dev = up_w.device
-    nbytes = int(L.load().vsr_sr_query(L.Q_UTD_S2_BLOB_BYTES))
-    lane = torch.arange(64, device=dev)
-    col_l, g = lane & 15, lane >> 4
-    j8 = torch.arange(8, device=dev)
-    perm = _chunk_channel_order(dev)
-    W = torch.arange(4, device=dev).view(4, 1, 1, 1, 1, 1)
-    A3 = torch.arange(3, device=dev).view(1, 3, 1, 1, 1, 1)
-    B3 = torch.arange(3, device=dev).view(1, 1, 3, 1, 1, 1)
-    MT = torch.arange(2, device=dev).view(1, 1, 1, 2, 1, 1)
-    LN = lane.view(1, 1, 1, 1, 64, 1)
-    J = j8.view(1, 1, 1, 1, 1, 8)
-    ky, kx = (W >> 1) + 2 * A3, (W & 1) + 2 * B3
-    co = 16 * MT + (LN & 15)
-    # deconv: A[co][k = 8 g + j] in natural channel order (the B operand comes straight from the LR rows)
-    ci, co_, ky_, kx_ = torch.broadcast_tensors(8 * (LN >> 4) + J, co, ky, kx)
-    up_frag = up_w.detach().float()[ci, co_, ky_, kx_].to(torch.float16).contiguous()        # [4,3,3,2,64,8]
-    # conv: A[co][k = (g, j)] in the accumulator-derived channel order of the operand tiles
-    ci, co_, ky_, kx_ = torch.broadcast_tensors(perm[LN >> 4, J], co, ky, kx)
-    dn_frag = dn_w.detach().float()[co_, ci, ky_, kx_].to(torch.float16).contiguous()
-    MT2 = torch.arange(2, device=dev).view(2, 1, 1)
-    co2, ci2 = torch.broadcast_tensors(16 * MT2 + col_l.view(1, 64, 1), tr_col0 + perm[g].view(1, 64, 8))
-    dt_frag = tr_w.detach().float()[co2, ci2].to(torch.float16).contiguous()
-    if layout == 4:
-        # k_utd_s2w (csrc/sr_utd_s2w.hip, v_mfma_f32_32x32x16_f16): [wave][.][.][K block 2][lane 64][8]; A[co = lane % 32][k = (kh = lane / 32, e)]:
-        # deconv in natural channel order (ci = 16 kb + 8 kh + e), conv / 1x1 in the 32 x 32 accumulator's (16 kb + 8 (e / 4) + 4 kh + e % 4)
-        KB = MT   # (same axis)
-        kh_, e_ = LN >> 5, J
-        ci, co_, ky_, kx_ = torch.broadcast_tensors(16 * KB + 8 * kh_ + e_, LN & 31, ky, kx)
-        up_frag = up_w.detach().float()[ci, co_, ky_, kx_].to(torch.float16).contiguous()
-        ci, co_, ky_, kx_ = torch.broadcast_tensors(16 * KB + 8 * (e_ >> 2) + 4 * kh_ + (e_ & 3), LN & 31, ky, kx)
-        dn_frag = dn_w.detach().float()[co_, ci, ky_, kx_].to(torch.float16).contiguous()
-        KB3, LN3, E3 = torch.arange(2, device=dev).view(2, 1, 1), lane.view(1, 64, 1), j8.view(1, 1, 8)
-        co2, ci2 = torch.broadcast_tensors(LN3 & 31, tr_col0 + 16 * KB3 + 8 * (E3 >> 2) + 4 * (LN3 >> 5) + (E3 & 3))
-        dt_frag = tr_w.detach().float()[co2, ci2].to(torch.float16).contiguous()
-    blob = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-    o_dn, o_dt = 4 * 18 * 1024, 8 * 18 * 1024
-    o_f = o_dt + 2 * 1024
-    blob[0:o_dn] = up_frag.view(torch.uint8).reshape(-1)
-    blob[o_dn:o_dt] = dn_frag.view(torch.uint8).reshape(-1)
-    blob[o_dt:o_f] = dt_frag.view(torch.uint8).reshape(-1)
-    fpar = torch.zeros(128, dtype=torch.float32, device=dev)
-    fpar[0:32], fpar[32:64], fpar[64:96] = up_b.detach().float(), tr_b.detach().float(), dn_b.detach().float()
-    fpar[96], fpar[97], fpar[98] = float(up_a), float(tr_a), float(dn_a)
-    blob[o_f:o_f + 512] = fpar.view(torch.uint8)
-    if post is not None:
-        pw, pcol, pb, pa = post
-        o_p = o_f + 512
-        co2, ci2 = torch.broadcast_tensors(16 * MT2 + col_l.view(1, 64, 1), pcol + 8 * g.view(1, 64, 1) + j8.view(1, 1, 8))   # natural channel order
-        blob[o_p:o_p + 2048] = pw.detach().float()[co2, ci2].to(torch.float16).contiguous().view(torch.uint8).reshape(-1)
-        ppar = torch.zeros(64, dtype=torch.float32, device=dev)
-        ppar[0:32] = pb.detach().float()
-        ppar[32] = float(pa)
-        blob[o_p + 2048:o_p + 2048 + 256] = ppar.view(torch.uint8)
-    return blob
-
-
-def pack_tail_s2_blob(out_w, out_b, out_a, cv_w, cv_b, fold_co=None) -> torch.Tensor:
-    """Weights of the fused x2 tail (csrc/sr_tail_s2.hip): the `out` ConvTranspose2d [32,32,6,6] in k_utd_s2's per-wave
-    fragment order, conv_out [3,32,3,3] as nine A fragments whose rows 0-2 are its output channels (k index in the
-    accumulator-derived channel order of the ring), then b_out[32], b_cv[3] and the PReLU slope.
-    fold_co = (w [32,ld], (col_a, col_b), b [32], a): compress_out over two live maps, for vsr_sr_tail_s2_fold_f16."""
-    dev = out_w.device
-    nbytes = int(L.load().vsr_sr_query(L.Q_TAIL_S2_BLOB_BYTES))
-    lane = torch.arange(64, device=dev)
-    perm = _chunk_channel_order(dev)
-    W = torch.arange(4, device=dev).view(4, 1, 1, 1, 1, 1)
-    A3 = torch.arange(3, device=dev).view(1, 3, 1, 1, 1, 1)
-    B3 = torch.arange(3, device=dev).view(1, 1, 3, 1, 1, 1)
-    MT = torch.arange(2, device=dev).view(1, 1, 1, 2, 1, 1)
-    LN = lane.view(1, 1, 1, 1, 64, 1)
-    J = torch.arange(8, device=dev).view(1, 1, 1, 1, 1, 8)
-    ci, co, ky, kx = torch.broadcast_tensors(8 * (LN >> 4) + J, 16 * MT + (LN & 15), (W >> 1) + 2 * A3, (W & 1) + 2 * B3)
-    up_frag = out_w.detach().float()[ci, co, ky, kx].to(torch.float16).contiguous()
-    cv = torch.zeros((3, 3, 64, 8), dtype=torch.float32, device=dev)
-    row, g = lane & 15, lane >> 4
-    live = row < 3
-    w = cv_w.detach().float()
-    for dy in range(3):
-        for dx in range(3):
-            cv[dy, dx, live] = w[row[live].unsqueeze(1), perm[g[live]], dy, dx]
-    blob = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-    o_cv = 4 * 18 * 1024
-    o_f = o_cv + 9 * 1024
-    blob[0:o_cv] = up_frag.view(torch.uint8).reshape(-1)
-    blob[o_cv:o_f] = cv.to(torch.float16).contiguous().view(torch.uint8).reshape(-1)
-    fpar = torch.zeros(128, dtype=torch.float32, device=dev)
-    fpar[0:32] = out_b.detach().float()
-    fpar[32:35] = cv_b.detach().float()
-    fpar[96] = float(out_a)
-    blob[o_f:o_f + 512] = fpar.view(torch.uint8)
-    if fold_co is not None:
-        co_w, cols, co_b, co_a = fold_co
-        o_co = o_f + 512
-        T2 = torch.tensor(list(cols), device=dev).view(2, 1, 1, 1)
-        MT2 = torch.arange(2, device=dev).view(1, 2, 1, 1)
-        co_, ci_ = torch.broadcast_tensors(16 * MT2 + (lane & 15).view(1, 1, 64, 1),
-                                           T2 + 8 * (lane >> 4).view(1, 1, 64, 1) + torch.arange(8, device=dev).view(1, 1, 1, 8))   # natural order: the raw maps
-        blob[o_co:o_co + 4096] = co_w.detach().float()[co_, ci_].to(torch.float16).contiguous().view(torch.uint8).reshape(-1)
-        cpar = torch.zeros(64, dtype=torch.float32, device=dev)
-        cpar[0:32] = co_b.detach().float()
-        cpar[32] = float(co_a)
-        blob[o_co + 4096:o_co + 4096 + 256] = cpar.view(torch.uint8)
-    return blob
-
-
 class _FusedStageS2:
     """up_i -> downtran slice -> down_j for upscale factor 2 in ONE launch (csrc/sr_utd_s2.hip: the x2 map stays in registers)."""
 
@@ -1265,124 +1141,6 @@ class _FusedStageS2:
         return (out, out2) if post else out
 
 
-# the x3 stage's waves own phase SETS of equal tap count (csrc/sr_utd_s3.hip): (HR row phase, HR column phase) per wave, in slot order
-_S3_PHASES = (((1, 1), (0, 0)), ((0, 1), (2, 1)), ((1, 0), (1, 2)), ((0, 2), (2, 0), (2, 2)))
-
-
-def _s3_taps(x):
-    """Kernel indices of phase x of the (7, 3, 2) geometry in slot order: k = x + 2 - 3 d for d = +1, 0, -1 where 0 <= k <= 6."""
-    return [x + 2 - 3 * d for d in (1, 0, -1) if 0 <= x + 2 - 3 * d <= 6]
-
-
-def pack_utd_s3_blob(up_w, up_b, up_a, tr_w, tr_col0, tr_b, tr_a, dn_w, dn_b, dn_a, layout: int = 1, post=None) -> torch.Tensor:
-    """Weights of one fused x3 stage in the per-wave MFMA fragment order of csrc/sr_utd_s3.hip (include/vsr_hip_s3.h).  A wave's
-    slots run over its phases (r, c) of _S3_PHASES, then the kernel rows ky of r, then the kernel columns kx of c (_s3_taps); slot
-    t of the deconvolution is element (ky, kx) of the ConvTranspose2d weight [32(in),32(out),7,7] and slot t of the convolution
-    the SAME element of the Conv2d weight [32(out),32(in),7,7] (the down-convolution mirrors the tap algebra).  13 slots per
-    wave; the unused ones stay zero.  `layout` and `post` exist for the argument list of pack_utd_s2_blob: one layout, no POST build."""
-    if layout != 1 or post is not None:
-        raise NotImplementedError("k_utd_s3 has one fragment layout and no in-launch uptran slice")
-    dev = up_w.device
-    nbytes = int(L.load_s3().vsr_s3_query(L.Q_S3_BLOB_BYTES))
-    lane = torch.arange(64, device=dev)
-    col_l, g = lane & 15, lane >> 4
-    j8 = torch.arange(8, device=dev)
-    perm = _chunk_channel_order(dev)
-    MT = torch.arange(2, device=dev).view(2, 1, 1)
-    co = 16 * MT + col_l.view(1, 64, 1)
-    # deconv: A[co][k = 8 g + j] in natural channel order (the B operand comes straight from the LR rows);
-    # conv / 1x1: A[co][k = (g, j)] in the accumulator-derived channel order of the operand tiles
-    co_n, ci_n = torch.broadcast_tensors(co, 8 * g.view(1, 64, 1) + j8.view(1, 1, 8))
-    co_p, ci_p = torch.broadcast_tensors(co, perm[g].view(1, 64, 8))
-    upw, dnw = up_w.detach().float(), dn_w.detach().float()
-    slots = 13
-    up_frag = torch.zeros((4, slots, 2, 64, 8), dtype=torch.float16, device=dev)
-    dn_frag = torch.zeros((4, slots, 2, 64, 8), dtype=torch.float16, device=dev)
-    for wv, phases in enumerate(_S3_PHASES):
-        t = 0
-        for r, c in phases:
-            for ky in _s3_taps(r):
-                for kx in _s3_taps(c):
-                    up_frag[wv, t] = upw[ci_n, co_n, ky, kx].to(torch.float16)
-                    dn_frag[wv, t] = dnw[co_p, ci_p, ky, kx].to(torch.float16)
-                    t += 1
-        assert t <= slots
-    dt_frag = tr_w.detach().float()[co_p, tr_col0 + ci_p].to(torch.float16).contiguous()
-    blob = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-    o_dn = 4 * slots * 2 * 1024
-    o_dt = 2 * o_dn
-    o_f = o_dt + 2 * 1024
-    assert nbytes == o_f + 512
-    blob[0:o_dn] = up_frag.contiguous().view(torch.uint8).reshape(-1)
-    blob[o_dn:o_dt] = dn_frag.contiguous().view(torch.uint8).reshape(-1)
-    blob[o_dt:o_f] = dt_frag.view(torch.uint8).reshape(-1)
-    fpar = torch.zeros(128, dtype=torch.float32, device=dev)
-    fpar[0:32], fpar[32:64], fpar[64:96] = up_b.detach().float(), tr_b.detach().float(), dn_b.detach().float()
-    fpar[96], fpar[97], fpar[98] = float(up_a), float(tr_a), float(dn_a)
-    blob[o_f:o_f + 512] = fpar.view(torch.uint8)
-    return blob
-
-
-def pack_tail_s3_blob(out_w, out_b, out_a, cv_w, cv_b, fold_co=None) -> torch.Tensor:
-    """Weights of the fused x3 tail (csrc/sr_tail_s3.hip, include/vsr_hip_s3t.h): the `out` ConvTranspose2d [32,32,7,7] in k_utd_s3's
-    per-wave slot order (_S3_PHASES / _s3_taps, the `up` half of pack_utd_s3_blob), conv_out [3,32,3,3] as nine A fragments whose rows
-    0-2 are its output channels (k index in the accumulator-derived channel order of the HR ring), then b_out[32], b_cv[3] and the
-    PReLU slope.  fold_co = (w [32,ld], (col_a, col_b), b [32], a): compress_out over two live maps, for vsr_s3t_sr_tail_fold_f16
-    (the blob is then VSR_S3T_Q_BLOB_FOLD_BYTES long; the plain entry reads its first VSR_S3T_Q_BLOB_BYTES)."""
-    dev = out_w.device
-    lib = L.load_s3t()
-    nplain = int(lib.vsr_s3t_query(L.Q_S3T_BLOB_BYTES))
-    nbytes = nplain if fold_co is None else int(lib.vsr_s3t_query(L.Q_S3T_BLOB_FOLD_BYTES))
-    lane = torch.arange(64, device=dev)
-    row, g = lane & 15, lane >> 4
-    perm = _chunk_channel_order(dev)
-    MT = torch.arange(2, device=dev).view(2, 1, 1)
-    # deconv: A[co][k = 8 g + j] in natural channel order (the B operand comes straight from the LR rows)
-    co_n, ci_n = torch.broadcast_tensors(16 * MT + row.view(1, 64, 1), 8 * g.view(1, 64, 1) + torch.arange(8, device=dev).view(1, 1, 8))
-    upw = out_w.detach().float()
-    slots = 13
-    up_frag = torch.zeros((4, slots, 2, 64, 8), dtype=torch.float16, device=dev)
-    for wv, phases in enumerate(_S3_PHASES):
-        t = 0
-        for r, c in phases:
-            for ky in _s3_taps(r):
-                for kx in _s3_taps(c):
-                    up_frag[wv, t] = upw[ci_n, co_n, ky, kx].to(torch.float16)
-                    t += 1
-        assert t <= slots
-    cv = torch.zeros((3, 3, 64, 8), dtype=torch.float32, device=dev)
-    live = row < 3
-    w = cv_w.detach().float()
-    for dy in range(3):
-        for dx in range(3):
-            cv[dy, dx, live] = w[row[live].unsqueeze(1), perm[g[live]], dy, dx]
-    blob = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-    o_cv = 4 * slots * 2 * 1024
-    o_f = o_cv + 9 * 1024
-    assert nplain == o_f + 512
-    blob[0:o_cv] = up_frag.contiguous().view(torch.uint8).reshape(-1)
-    blob[o_cv:o_f] = cv.to(torch.float16).contiguous().view(torch.uint8).reshape(-1)
-    fpar = torch.zeros(128, dtype=torch.float32, device=dev)
-    fpar[0:32] = out_b.detach().float()
-    fpar[32:35] = cv_b.detach().float()
-    fpar[96] = float(out_a)
-    blob[o_f:o_f + 512] = fpar.view(torch.uint8)
-    if fold_co is not None:
-        co_w, cols, co_b, co_a = fold_co
-        o_co = nplain
-        assert nbytes == o_co + 4096 + 256
-        T2 = torch.tensor(list(cols), device=dev).view(2, 1, 1, 1)
-        MT2 = torch.arange(2, device=dev).view(1, 2, 1, 1)
-        co_, ci_ = torch.broadcast_tensors(16 * MT2 + row.view(1, 1, 64, 1),
-                                           T2 + 8 * g.view(1, 1, 64, 1) + torch.arange(8, device=dev).view(1, 1, 1, 8))   # natural order: the raw maps
-        blob[o_co:o_co + 4096] = co_w.detach().float()[co_, ci_].to(torch.float16).contiguous().view(torch.uint8).reshape(-1)
-        cpar = torch.zeros(64, dtype=torch.float32, device=dev)
-        cpar[0:32] = co_b.detach().float()
-        cpar[32] = float(co_a)
-        blob[o_co + 4096:o_co + 4096 + 256] = cpar.view(torch.uint8)
-    return blob
-
-
 class _FusedStageS3:
     """up_i -> downtran slice -> down_j for upscale factor 3 in ONE launch (csrc/sr_utd_s3.hip: the x3 map stays in registers)."""
 
@@ -1408,33 +1166,6 @@ class _FusedStageS3:
                                                                  L.dptr(out[n0:n0 + n], torch.float16), n, h, w, rows, int(self.slopes_le_one), L.stream()),
                        "sr_utd_s3_f16", lib=lib, side=side)
         return out
-
-
-def _append_post_s3(stage_blob, post) -> torch.Tensor:
-    """stage_blob (pack_utd_s3_blob's bytes) + the POST section of include/vsr_hip_s3p.h: post = (w [32,ld], col0, b [32], a) as two A
-    fragments in NATURAL channel order (the B operand is the stage's output row as it lies in memory), then b_post[32], slope_post."""
-    dev = stage_blob.device
-    nbytes = int(L.load_s3p().vsr_s3p_query(L.Q_S3P_BLOB_BYTES))
-    o_p = stage_blob.numel()
-    assert nbytes == o_p + 2048 + 256
-    pw, pcol, pb, pa = post
-    lane = torch.arange(64, device=dev)
-    MT2 = torch.arange(2, device=dev).view(2, 1, 1)
-    co2, ci2 = torch.broadcast_tensors(16 * MT2 + (lane & 15).view(1, 64, 1), pcol + 8 * (lane >> 4).view(1, 64, 1) + torch.arange(8, device=dev).view(1, 1, 8))
-    blob = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-    blob[:o_p] = stage_blob
-    blob[o_p:o_p + 2048] = pw.detach().float()[co2, ci2].to(torch.float16).contiguous().view(torch.uint8).reshape(-1)
-    ppar = torch.zeros(64, dtype=torch.float32, device=dev)
-    ppar[0:32] = pb.detach().float()
-    ppar[32] = float(pa)
-    blob[o_p + 2048:o_p + 2048 + 256] = ppar.view(torch.uint8)
-    return blob
-
-
-def pack_utd_s3_post_blob(up_w, up_b, up_a, tr_w, tr_col0, tr_b, tr_a, dn_w, dn_b, dn_a, post) -> torch.Tensor:
-    """The blob of vsr_s3p_sr_utd_post_f16 (include/vsr_hip_s3p.h): pack_utd_s3_blob's bytes, then post = (w [32,ld], col0, b [32], a), the
-    1x1 + PReLU applied to every finished output row (the next group's uptran slice)."""
-    return _append_post_s3(pack_utd_s3_blob(up_w, up_b, up_a, tr_w, tr_col0, tr_b, tr_a, dn_w, dn_b, dn_a), post)
 
 
 class _FusedStageS3Post:
@@ -1465,40 +1196,6 @@ class _FusedStageS3Post:
                                                                        n, h, w, rows, int(self.post_slopes_le_one), L.stream()),
                        "sr_utd_s3_post_f16", lib=lib, side=side)
         return out, out2
-
-
-PRE_SECTION_BYTES = 12 * 1024 + 512
-
-
-def pack_utd_s3_pre_blob(post_blob, co, ci, ut0) -> torch.Tensor:
-    """The blob of vsr_s3f_sr_utd_pre_f16 (include/vsr_hip_s3f.h): post_blob (pack_utd_s3_post_blob's bytes, byte for byte), then the PRE
-    section -- the step-opening 1x1 chain as twelve A fragments [lane 64][8] fp16 (fragment 2 i + mt: rows 16 mt + lane % 16 of matrix i)
-    and a parameter block.  co = (w [32,ld], (col_a, col_b), b [32], a): compress_out over the two live maps; ci = (w [32,64], b, a):
-    compress_in (columns 0:32 multiply `feat`, 32:64 the previous 1x1's tile); ut0 = (w [32,ld], col0, b, a): the first uptran slice.
-    Memory inputs in natural channel order, chained inputs in the accumulator's (_chunk_channel_order); the second half of ci a second time
-    in natural order (step 0, where it multiplies `feat`).  fp32 -> fp16 by round to nearest even, as k_chain1x1_s rounds at load."""
-    dev = post_blob.device
-    nbytes = int(L.load_s3f().vsr_s3f_query(L.Q_S3F_BLOB_BYTES))
-    o_p = post_blob.numel()
-    assert nbytes == o_p + PRE_SECTION_BYTES
-    co_w, (col_a, col_b), co_b, co_a = co
-    ci_w, ci_b, ci_a = ci
-    ut_w, ut_col, ut_b, ut_a = ut0
-    lane = torch.arange(64, device=dev)
-    row = (16 * torch.arange(2, device=dev).view(2, 1, 1) + (lane & 15).view(1, 64, 1)).expand(2, 64, 8)
-    nat = (8 * (lane >> 4).view(1, 64, 1) + torch.arange(8, device=dev).view(1, 1, 8)).expand(2, 64, 8)
-    acc = _chunk_channel_order(dev)[lane >> 4].view(1, 64, 8).expand(2, 64, 8)
-    frag = lambda wm, k: wm.detach().float().to(dev)[row, k].to(torch.float16)
-    frags = torch.stack((frag(co_w, col_a + nat), frag(co_w, col_b + nat), frag(ci_w, nat), frag(ci_w, _NF + acc), frag(ut_w, ut_col + acc),
-                         frag(ci_w, _NF + nat)))   # [6][mt 2][lane 64][8]
-    blob = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-    blob[:o_p] = post_blob
-    blob[o_p:o_p + 12 * 1024] = frags.contiguous().view(torch.uint8).reshape(-1)
-    par = torch.zeros(128, dtype=torch.float32, device=dev)
-    par[0:32], par[32:64], par[64:96] = co_b.detach().float(), ci_b.detach().float(), ut_b.detach().float()
-    par[96], par[97], par[98] = float(co_a), float(ci_a), float(ut_a)
-    blob[o_p + 12 * 1024:] = par.view(torch.uint8)
-    return blob
 
 
 class _FusedStageS3Pre:
@@ -1575,179 +1272,3 @@ def ctypes_ptr(view: torch.Tensor):
     if not view.is_cuda or view.dtype != torch.float32 or view.stride(-1) != 1:
         raise L.VsrHipError("weight view must be a CUDA float32 matrix with unit column stride")
     return ctypes.c_void_p(view.data_ptr())
-
-
-def _chunk_channel_order(device):
-    """Channel held at position j of 16-byte chunk g in the HR ring / the MFMA k index (g, j): the accumulator of a
-    16x16 MFMA gives lane group g the output rows {4g..4g+3} of tile 0 and {16+4g..16+4g+3} of tile 1, and that
-    register block is used as-is as the next product's operand (csrc/sr_f16.hip)."""
-    g = torch.arange(4, device=device).view(4, 1)
-    j = torch.arange(8, device=device).view(1, 8)
-    return torch.where(j < 4, 4 * g + j, 16 + 4 * g + (j - 4))  # [4,8]
-
-
-def pack_utd_blob(up_w, up_b, up_a, tr_w, tr_col0, tr_b, tr_a, dn_w, dn_b, dn_a, layout: int = 1, fold_co=None, post=None) -> torch.Tensor:
-    """Weights of one fused up->tran->down stage in the per-wave MFMA fragment order of csrc/sr_f16.hip.
-
-    up_w [32(in),32(out),8,8] ConvTranspose2d weight; tr_w [32,ld] 1x1 weight whose live slice starts at column
-    tr_col0; dn_w [32(out),32(in),8,8] Conv2d weight.  tr_w/dn_w None -> deconv-only blob (tail).
-    fold_co = (co_w [32,ld], (col0_a, col0_b), co_b [32], co_a): the 1x1 + PReLU over two LR maps (+ constant map) that
-    produces the deconv's input, applied by k_tail3<.., FOLD> on the rows' way into LDS; the deconv fragments then take
-    their K index in the accumulator's channel order (vsr_sr_tail3_fold_f16).
-    post = (w [32,ld], col0, b [32], a): the 1x1 + PReLU that vsr_sr_utd_post_f16 applies to every finished output row (the next
-    group's uptran slice); its two fragments, bias and slope take the first half of the compress_out region (natural channel order).
-    """
-    dev = up_w.device
-    nbytes = int(L.load().vsr_sr_query(L.Q_UTD_BLOB_BYTES))
-    lane = torch.arange(64, device=dev)
-    col_l, g = lane & 15, lane >> 4
-    j8 = torch.arange(8, device=dev)
-    perm = _chunk_channel_order(dev)  # [4,8]
-    # ---- deconv fragments [w 8][c 2][t 4][mt 2][lane 64][j 8]: A[co][k = 8g + j] for tap t of phase (py, px)
-    W = torch.arange(8, device=dev).view(8, 1, 1, 1, 1, 1)
-    C = torch.arange(2, device=dev).view(1, 2, 1, 1, 1, 1)
-    T = torch.arange(4, device=dev).view(1, 1, 4, 1, 1, 1)
-    MT = torch.arange(2, device=dev).view(1, 1, 1, 2, 1, 1)
-    LN = lane.view(1, 1, 1, 1, 64, 1)
-    J = j8.view(1, 1, 1, 1, 1, 8)
-    ci = 8 * (LN >> 4) + J if fold_co is None else perm[LN >> 4, J]
-    co = 16 * MT + (LN & 15)
-    ky = (W >> 1) + 4 * (T >> 1)
-    kx = 2 * (W & 1) + C + 4 * (T & 1)
-    if layout == 2:  # [producer p 4][phase c 4][tap 4][mt 2]: HR row phase p, column phase c
-        PP = torch.arange(4, device=dev).view(4, 1, 1, 1, 1, 1)
-        CC = torch.arange(4, device=dev).view(1, 4, 1, 1, 1, 1)
-        ky = PP + 4 * (T >> 1)
-        kx = CC + 4 * (T & 1)
-    ci, co, ky, kx = torch.broadcast_tensors(ci, co, ky, kx)
-    up_frag = up_w.detach().float()[ci, co, ky, kx].to(torch.float16).contiguous()
-    blob = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-    off_dn = 8 * 16 * 1024
-    off_dt = off_dn + 8 * 16 * 1024
-    off_f = off_dt + 2 * 1024
-    if layout == 4:
-        # k_utd4 (csrc/sr_utd4.hip, v_mfma_f32_32x32x16_f16): [wave 4][column phase 4][tap (dy, dx) 4][K block 2][lane 64][8]:
-        # A[co = lane % 32][k = (kh = lane / 32, e)] = W[ci = 16 kb + 8 kh + e][co][ky = wave + 4 dy][kx = phase + 4 dx]
-        WV = torch.arange(4, device=dev).view(4, 1, 1, 1, 1, 1)
-        PX = torch.arange(4, device=dev).view(1, 4, 1, 1, 1, 1)
-        T4 = torch.arange(4, device=dev).view(1, 1, 4, 1, 1, 1)
-        KB = torch.arange(2, device=dev).view(1, 1, 1, 2, 1, 1)
-        ci4, co4, ky4, kx4 = torch.broadcast_tensors(16 * KB + 8 * (LN >> 5) + J, LN & 31, WV + 4 * (T4 >> 1), PX + 4 * (T4 & 1))
-        up_frag = up_w.detach().float()[ci4, co4, ky4, kx4].to(torch.float16).contiguous()
-    blob[0:off_dn] = up_frag.view(torch.uint8).reshape(-1)
-    fpar = torch.zeros(128, dtype=torch.float32, device=dev)
-    fpar[0:32] = up_b.detach().float()
-    fpar[96] = float(up_a)
-    if dn_w is not None:
-        # ---- down fragments [w 8][lo/hi 2][kx 8][lane 64][j 8]: wave w owns kernel rows w&3 (lo) and (w&3)+4 (hi) for
-        #      out-channel half w>>2; A[co][k = (g, j)] with the ring's channel order
-        W = torch.arange(8, device=dev).view(8, 1, 1, 1, 1)
-        HL = torch.arange(2, device=dev).view(1, 2, 1, 1, 1)
-        KX = torch.arange(8, device=dev).view(1, 1, 8, 1, 1)
-        co = 16 * (W >> 2) + col_l.view(1, 1, 1, 64, 1)
-        ci = perm[g].view(1, 1, 1, 64, 8)
-        ky = (W & 3) + 4 * HL
-        if layout == 2:  # [consumer q 4][lo/hi 2][kx 8][mt 2][lane][j]: kernel rows q and q+4, both channel halves
-            Q = torch.arange(4, device=dev).view(4, 1, 1, 1, 1, 1)
-            HL6 = torch.arange(2, device=dev).view(1, 2, 1, 1, 1, 1)
-            KX6 = torch.arange(8, device=dev).view(1, 1, 8, 1, 1, 1)
-            MT6 = torch.arange(2, device=dev).view(1, 1, 1, 2, 1, 1)
-            co = 16 * MT6 + col_l.view(1, 1, 1, 1, 64, 1)
-            ci = perm[g].view(1, 1, 1, 1, 64, 8)
-            ky = Q + 4 * HL6
-            KX = KX6
-        co, ci, ky, kx = torch.broadcast_tensors(co, ci, ky, KX)
-        dn_frag = dn_w.detach().float()[co, ci, ky, kx].to(torch.float16).contiguous()
-        # ---- 1x1 fragments [mt 2][lane 64][j 8]
-        MT = torch.arange(2, device=dev).view(2, 1, 1)
-        co = 16 * MT + col_l.view(1, 64, 1)
-        ci = tr_col0 + perm[g].view(1, 64, 8)
-        co, ci = torch.broadcast_tensors(co, ci)
-        dt_frag = tr_w.detach().float()[co, ci].to(torch.float16).contiguous()
-        if layout == 4:
-            # k_utd4: K index (kb, kh, e) <-> channel 16 kb + 8 (e / 4) + 4 kh + e % 4 (the 32 x 32 accumulator's channel order);
-            # down [wave 4][0: kernel row wave (next output row), 1: wave + 4 (current)][kx 8][K block 2][lane 64][8]; 1x1 [K block 2][lane 64][8]
-            WV = torch.arange(4, device=dev).view(4, 1, 1, 1, 1, 1)
-            HL = torch.arange(2, device=dev).view(1, 2, 1, 1, 1, 1)
-            KX8 = torch.arange(8, device=dev).view(1, 1, 8, 1, 1, 1)
-            KB = torch.arange(2, device=dev).view(1, 1, 1, 2, 1, 1)
-            LN6 = lane.view(1, 1, 1, 1, 64, 1)
-            E6 = j8.view(1, 1, 1, 1, 1, 8)
-            ch6 = 16 * KB + 8 * (E6 >> 2) + 4 * (LN6 >> 5) + (E6 & 3)
-            co6, ci6, ky6, kx6 = torch.broadcast_tensors(LN6 & 31, ch6, WV + 4 * HL, KX8)
-            dn_frag = dn_w.detach().float()[co6, ci6, ky6, kx6].to(torch.float16).contiguous()
-            KB3 = torch.arange(2, device=dev).view(2, 1, 1)
-            LN3 = lane.view(1, 64, 1)
-            E3 = j8.view(1, 1, 8)
-            co3, ci3 = torch.broadcast_tensors(LN3 & 31, tr_col0 + 16 * KB3 + 8 * (E3 >> 2) + 4 * (LN3 >> 5) + (E3 & 3))
-            dt_frag = tr_w.detach().float()[co3, ci3].to(torch.float16).contiguous()
-        blob[off_dn:off_dt] = dn_frag.view(torch.uint8).reshape(-1)
-        blob[off_dt:off_f] = dt_frag.view(torch.uint8).reshape(-1)
-        fpar[32:64] = tr_b.detach().float()
-        fpar[64:96] = dn_b.detach().float()
-        fpar[97] = float(tr_a)
-        fpar[98] = float(dn_a)
-    blob[off_f:off_f + 512] = fpar.view(torch.uint8)
-    if fold_co is not None:
-        co_w, cols, co_b, co_a = fold_co
-        off_co = off_f + 512
-        T2 = torch.arange(2, device=dev).view(2, 1, 1, 1)
-        MT = torch.arange(2, device=dev).view(1, 2, 1, 1)
-        col0 = torch.tensor(list(cols), device=dev).view(2, 1, 1, 1)
-        co = 16 * MT + col_l.view(1, 1, 64, 1)
-        ci = col0 + 8 * g.view(1, 1, 64, 1) + j8.view(1, 1, 1, 8)   # the 1x1 reads the raw maps: natural channel order
-        co, ci = torch.broadcast_tensors(co, ci)
-        blob[off_co:off_co + 4096] = co_w.detach().float()[co, ci].to(torch.float16).contiguous().view(torch.uint8).reshape(-1)
-        cpar = torch.zeros(64, dtype=torch.float32, device=dev)
-        cpar[0:32] = co_b.detach().float()
-        cpar[32] = float(co_a)
-        blob[off_co + 4096:off_co + 4096 + 256] = cpar.view(torch.uint8)
-    if post is not None:
-        assert fold_co is None
-        pw, pcol, pb, pa = post
-        off_co = off_f + 512
-        MT = torch.arange(2, device=dev).view(2, 1, 1)
-        co = 16 * MT + col_l.view(1, 64, 1)
-        ci = pcol + 8 * g.view(1, 64, 1) + j8.view(1, 1, 8)
-        co, ci = torch.broadcast_tensors(co, ci)
-        blob[off_co:off_co + 2048] = pw.detach().float()[co, ci].to(torch.float16).contiguous().view(torch.uint8).reshape(-1)
-        cpar = torch.zeros(64, dtype=torch.float32, device=dev)
-        cpar[0:32] = pb.detach().float()
-        cpar[32] = float(pa)
-        blob[off_co + 4096:off_co + 4096 + 256] = cpar.view(torch.uint8)
-    return blob
-
-
-def pack_conv_out_frags3(weight) -> torch.Tensor:
-    """conv_out weight [3,32,3,3] -> the 3 MFMA A-fragments (one per dx) of csrc/sr_tail3.hip:k_tail3, [dx][lane 64][8]
-    fp16: accumulator row m = 4 dy + co holds the contribution of an HR row to output row (HR row + 1 - dy), channel co;
-    k index (g, j) follows the operand tiles' channel order."""
-    dev = weight.device
-    w = weight.detach().float()
-    lane = torch.arange(64, device=dev)
-    m, g = lane & 15, lane >> 4
-    dy, co = m >> 2, m & 3
-    live = (dy < 3) & (co < 3)
-    perm = _chunk_channel_order(dev)  # [4,8]
-    frags = torch.zeros((3, 64, 8), dtype=torch.float32, device=dev)
-    ci = perm[g[live]]  # [n_live, 8]
-    for dx in range(3):
-        frags[dx, live] = w[co[live].unsqueeze(1), ci, dy[live].unsqueeze(1), dx]
-    return frags.to(torch.float16).contiguous()
-
-
-def pack_conv_out_frags(weight) -> torch.Tensor:
-    """conv_out weight [3,32,3,3] -> the 9 MFMA A-fragments of csrc/sr_f16.hip:k_tail, [tap][lane 64][8] fp16:
-    accumulator row m = lane & 15 carries output channel c iff m == 4c; k index (g, j) follows the ring's channel order."""
-    dev = weight.device
-    w = weight.detach().float()
-    lane = torch.arange(64, device=dev)
-    m, g = lane & 15, lane >> 4
-    perm = _chunk_channel_order(dev)  # [4,8]
-    frags = torch.zeros((9, 64, 8), dtype=torch.float32, device=dev)
-    for c in range(3):
-        sel = m == 4 * c
-        ci = perm[g[sel]]  # [n_sel, 8]
-        for t in range(9):
-            frags[t, sel] = w[c, ci, t // 3, t % 3]
-    return frags.to(torch.float16).contiguous()
