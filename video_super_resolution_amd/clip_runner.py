@@ -1,0 +1,291 @@
+"""`ClipRunner`: a 4:2:0 clip streamed through the model on top of `frames`: every source frame uploaded once from pinned memory on a
+copy stream, converted once into a three-slot LR ring, the window formed on the device, the HR frame written out as 4:2:0 and copied
+back on a second copy stream.  What a run scores (`score=`, `baseline=`, `temporal=`) is a list of series, each a range of rows of one
+float64 tensor of sums (`sums_layout`); `driver` imports `ClipRunner`, so `driver.ClipRunner` resolves as before.
+"""
+from __future__ import annotations
+
+from types import SimpleNamespace
+from typing import Dict, Optional, Tuple
+
+import numpy as np
+import torch
+
+from .frames import (METRIC_CHANNELS, FrameResizer, ewarp, frame_metrics, psnr_ssim, truth_flows, warp_error, yuv_coefficients,
+                     yuv_frame_bytes, yuv_ingest, yuv_write)
+
+# series of `sums_layout` -> the keys of `ClipRunner.metrics` its host step (`psnr_ssim` for a frame series, `ewarp` for a pair series)
+# fills; the occlusion mask depends on the flows alone, so the estimate's pairs give the one `valid_share`
+METRIC_KEYS = {"estimate": ("psnr", "ssim"), "baseline": ("psnr_baseline", "ssim_baseline"), "ewarp": ("ewarp", "valid_share"),
+               "ewarp_truth": ("ewarp_truth", None), "ewarp_baseline": ("ewarp_baseline", None)}
+
+
+def sums_layout(T: int, score: Optional[str], baseline: Optional[str] = None,
+                temporal: Optional[str] = None) -> Optional[Dict[str, Tuple[int, int, str]]]:
+    """What a scored run of `T` source frames sums up, as rows of ONE [rows,4] float64 tensor: series name -> (row0, rows, kind), in
+    row order.  A "frame" series has a row per output frame (T - 2: `frame_metrics`' sums), a "pair" series a row per pair of consecutive
+    output frames (T - 3, none for T = 3: `warp_error`'s sums).  `estimate` always; `baseline` with a baseline; `ewarp` (the estimate's
+    pairs) and `ewarp_truth` with `temporal`, `ewarp_baseline` with both.  None when nothing is scored (`score` is None)."""
+    if score is None:
+        return None
+    series = [("estimate", "frame")]
+    if baseline is not None:
+        series.append(("baseline", "frame"))
+    if temporal is not None:
+        series += [("ewarp", "pair"), ("ewarp_truth", "pair")]
+        if baseline is not None:
+            series.append(("ewarp_baseline", "pair"))
+    layout, row0 = {}, 0
+    for name, kind in series:
+        rows = T - 2 if kind == "frame" else T - 3
+        layout[name] = (row0, rows, kind)
+        row0 += rows
+    return layout
+
+
+class ClipRunner:
+    """A 4:2:0 clip streamed through `model` frame by frame.  `shape` = (H, W) of the source frames in `fmt_in`; the model sees them
+    decimated by `scale_down` (1: as they are) and returns frames of (S * (H // scale_down), S * (W // scale_down)), written out as
+    `fmt_out`.  `run(frames)`: host array [T, frame_bytes] -> host array [T-2, out_frame_bytes] (one frame per 3-frame window).
+
+    Per source frame: one upload from one of two pinned slots on the copy-in stream, one conversion into a slot of a three-slot LR
+    ring; per window: the ring's slots stacked on the device, `model(x, None, None, est, train=False)` on the current stream with the
+    estimate fed back (as `run_item`), `frames_to_yuv`'s kernel into one of two device slots, the copy back into one of two pinned
+    slots on the copy-out stream.  Events order every reuse of a slot; the host waits on events only, never on the device.
+    `overlap=False`: both copy streams ARE the current stream -- the same work in one stream's order (the cross-check).
+    `h2d_bytes`, `d2h_bytes`, `frames_in`, `frames_out` count what the last `run()` moved (reset when a run starts).
+
+    `score="rgb" | "y"` (only where the output frame has the source's shape, `scale_down == S`): output frame j is scored against source
+    frame j + 1, the middle frame of its window (`target = datas[:, 1:2]` in the reference's loop), which is still resident in its
+    upload slot when the window runs: one more conversion at full size into a reused HR buffer and `frame_metrics` of the float
+    estimate (quantised as write-out does, `shave` pixels dropped on every side, default S; "y" is `frame_metrics`' BT.601 luma whatever
+    `matrix` the frames are coded with) into row j of its series in the run's one tensor of sums (`sums_layout`); nothing
+    extra is uploaded, and one copy at the end gives `metrics = {"psnr": [T-2], "ssim": [T-2]}`.
+
+    `decimate="nearest"` (default): the LR frame is the conversion's own nearest-neighbour decimation (the reference's `interpolate` at
+    main.py:157).  `decimate="bicubic"`: every uploaded frame is converted at full size into a reused HR buffer of its own (not the one the
+    scored window's truth lives in) and reduced into its ring slot by `FrameResizer(quantise=True)`: the antialiased bicubic LR frame as an
+    8-bit file would hold it, the evaluation protocol of the literature.  `baseline="bicubic"` (needs `score`): per window the middle LR
+    frame of the ring is enlarged to the output shape into a reused buffer and scored against the same truth with the same quantise,
+    shave and channels as the estimate, into a second series of T - 2 rows of the same tensor: `metrics` gains `psnr_baseline` and
+    `ssim_baseline`.  Neither uploads or downloads a byte more; with both at their defaults the launches are the ones described above.
+
+    `temporal="warp"` (needs `score`): the temporal warping error of the output (`warp_error`, Lai et al. 2018).  For every output frame
+    j >= 1 the pair (j - 1, j) is scored along the flows between the source frames j and j + 1 (`truth_flows`, both directions in one
+    FlowNet2 batch, in the model's precision): the previous estimate and the previous truth frame are kept (`_truth` is then two
+    alternating buffers), and the pair of truth frames is scored along the same flows: the floor any method sits above.  With
+    `baseline="bicubic"` the baseline pair is scored too (`_base` is then two alternating buffers).  Same channels, quantise and shave
+    (counted inside the flow's centre crop) as the per-frame scores, `occ` as `warp_error`'s (default: the published constants), into series of
+    T - 3 rows each that travel in the one copy at the end:
+    `metrics` gains `ewarp`, `ewarp_truth`, `valid_share` (the occlusion mask depends on the flows alone: one share for all) and, with a
+    baseline, `ewarp_baseline`, each [T-3] (empty for T = 3).  No upload, download or host wait is added; with `temporal=None` the
+    launches are the ones described above."""
+
+    DECIMATE = ("nearest", "bicubic")
+    BASELINE = (None, "bicubic")
+    TEMPORAL = (None, "warp")
+
+    def __init__(self, model, shape: Tuple[int, int], fmt_in: str, fmt_out: str, scale_down: int = 1, overlap: bool = True,
+                 matrix: str = "bt709", full_range: bool = False, siting: str = "left", score: Optional[str] = None,
+                 shave: Optional[int] = None, decimate: str = "nearest", baseline: Optional[str] = None, temporal: Optional[str] = None,
+                 occ=None):
+        if decimate not in self.DECIMATE:
+            raise ValueError(f"decimate must be 'nearest' or 'bicubic', got {decimate!r}")
+        if baseline not in self.BASELINE:
+            raise ValueError(f"baseline must be None or 'bicubic', got {baseline!r}")
+        if baseline is not None and score is None:
+            raise ValueError(f"baseline={baseline!r} is scored beside the estimate: it needs score='rgb' or 'y'")
+        if temporal not in self.TEMPORAL:
+            raise ValueError(f"temporal must be None or 'warp', got {temporal!r}")
+        if temporal is not None and score is None:
+            raise ValueError(f"temporal={temporal!r} is scored beside the estimate: it needs score='rgb' or 'y'")
+        if occ is not None and temporal is None:
+            raise ValueError("occ is given but no temporal score is asked for (temporal=None)")
+        self.decimate, self.baseline, self.temporal, self.occ = decimate, baseline, temporal, occ
+        self.model, self.fmt_in, self.fmt_out, self.overlap, self.siting = model, fmt_in, fmt_out, bool(overlap), siting
+        H, W = int(shape[0]), int(shape[1])
+        self.shape = (H, W)
+        self.lr_shape = (int(H / scale_down), int(W / scale_down))
+        S = int(model.model.upscale_factor)
+        self.out_shape = (S * self.lr_shape[0], S * self.lr_shape[1])
+        if score is not None and score not in METRIC_CHANNELS:
+            raise ValueError(f"score must be None, 'rgb' or 'y', got {score!r}")
+        if score is None and shave is not None:
+            raise ValueError("shave is given but nothing is scored (score=None)")
+        if score is not None and self.out_shape != self.shape:
+            raise ValueError(f"score={score!r} needs output frames of the source's shape: {self.shape} in, {self.out_shape} out "
+                             f"(scale_down {scale_down}, x{S})")
+        self.score, self.shave = score, (S if shave is None else int(shave))
+        if score is not None and (self.shave < 0 or min(self.shape) - 2 * self.shave < 11):
+            raise ValueError(f"shave {self.shave} leaves less than SSIM's 11 pixels of {self.shape}")
+        self.metrics = None   # of the last run(): {"psnr": [T-2], "ssim": [T-2]} when scoring
+        self.in_bytes = yuv_frame_bytes(fmt_in, H, W)
+        self.out_bytes = yuv_frame_bytes(fmt_out, *self.out_shape)
+        self.coef_in = yuv_coefficients(fmt_in, matrix, full_range, inverse=True)
+        self.coef_out = yuv_coefficients(fmt_out, matrix, full_range)
+        self.device = next(model.parameters()).device
+        dev = self.device
+        self._pin_in = [torch.empty(self.in_bytes, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+        self._pin_out = [torch.empty(self.out_bytes, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+        self._dev_in = [torch.empty(self.in_bytes, dtype=torch.uint8, device=dev) for _ in range(2)]
+        self._dev_out = [torch.empty(self.out_bytes, dtype=torch.uint8, device=dev) for _ in range(2)]
+        self._ring = [torch.empty(self.lr_shape + (3,), dtype=torch.float32, device=dev) for _ in range(3)]
+        self._truth = torch.empty(self.shape + (3,), dtype=torch.float32, device=dev) if score is not None else None
+        if temporal is not None:   # the truth frame of the previous window stays: two alternating buffers
+            self._truth = [self._truth, torch.empty(self.shape + (3,), dtype=torch.float32, device=dev)]
+        self._full = self._down = self._up = self._base = None
+        if decimate == "bicubic":
+            self._full = torch.empty(self.shape + (3,), dtype=torch.float32, device=dev)   # the frame being reduced; `_truth` is the window's
+            self._down = FrameResizer(self.shape, self.lr_shape, "bicubic", dev)
+        if baseline is not None:
+            self._base = torch.empty(self.out_shape + (3,), dtype=torch.float32, device=dev)
+            self._up = FrameResizer(self.lr_shape, self.out_shape, baseline, dev)
+            if temporal is not None:
+                self._base = [self._base, torch.empty(self.out_shape + (3,), dtype=torch.float32, device=dev)]
+        self._s_in = torch.cuda.Stream(dev) if self.overlap else None
+        self._s_out = torch.cuda.Stream(dev) if self.overlap else None
+        self.h2d_bytes = self.d2h_bytes = self.frames_in = self.frames_out = 0   # of the last run()
+
+    @property
+    def h2d_bytes_per_frame(self) -> float:
+        return self.h2d_bytes / max(self.frames_in, 1)
+
+    @staticmethod
+    def _slot(buf, j: int):
+        """Buffer of window `j`: `_truth` and `_base` are one tensor, or two alternating ones when the previous window's is kept."""
+        return buf[j % 2] if isinstance(buf, list) else buf
+
+    def run(self, frames: np.ndarray) -> np.ndarray:
+        frames = np.asarray(frames)
+        if frames.dtype != np.uint8 or frames.ndim != 2 or frames.shape[1] != self.in_bytes or frames.shape[0] < 3:
+            raise ValueError(f"expected uint8 [T >= 3, {self.in_bytes}], got {frames.dtype} {frames.shape}")
+        T = frames.shape[0]
+        self.h2d_bytes = self.d2h_bytes = self.frames_in = self.frames_out = 0
+        self.metrics = None
+        with torch.cuda.device(self.device), torch.no_grad():
+            st = self._begin(T)
+            for i in range(T):
+                self._upload(st, i, frames[i])
+                if i < 2:
+                    continue
+                self._forward(st, i)
+                if st.layout is not None:
+                    self._score(st, i - 2)
+                self._write_out(st, i - 2)
+            self._drain(st)
+            if st.layout is not None:
+                self.metrics = self._collect(st)
+        return st.out
+
+    def _begin(self, T: int):
+        """The state of one run: the output array, the one tensor of sums, the streams and the events that order every reuse of a slot."""
+        layout = sums_layout(T, self.score, self.baseline, self.temporal)
+        rows = sum(n for _, n, _ in layout.values()) if layout is not None else 0
+        main = torch.cuda.current_stream(self.device)
+        s_in, s_out = (self._s_in, self._s_out) if self.overlap else (main, main)
+        return SimpleNamespace(
+            out=np.empty((T - 2, self.out_bytes), dtype=np.uint8), layout=layout,
+            sums=None if layout is None else torch.empty((rows, 4), dtype=torch.float64, device=self.device),
+            main=main, s_in=s_in, s_out=s_out, est=None, prev_est=None,
+            uploaded=[None, None],    # per input slot: the upload from its pinned buffer has finished (event on s_in)
+            converted=[None, None],   # per input slot: the conversion has read its device buffer (event on main)
+            copied=[None, None])      # per output slot: (frame index, event on s_out: the copy into its pinned buffer has finished)
+
+    def _upload(self, st, i: int, frame: np.ndarray) -> None:
+        """Source frame `i`: from its pinned slot to the device on the copy-in stream, converted into ring slot i % 3 on the current one."""
+        a = i % 2
+        if st.uploaded[a] is not None:
+            st.uploaded[a].synchronize()   # the pinned slot is free again (host wait on one event)
+        self._pin_in[a].numpy()[:] = frame
+        if st.converted[a] is not None:
+            st.s_in.wait_event(st.converted[a])
+        with torch.cuda.stream(st.s_in):
+            self._dev_in[a].copy_(self._pin_in[a], non_blocking=True)
+            st.uploaded[a] = torch.cuda.Event()
+            st.uploaded[a].record(st.s_in)
+        self.h2d_bytes += self.in_bytes
+        self.frames_in += 1
+        st.main.wait_event(st.uploaded[a])
+        # (ring slot i % 3 was last read by the window of frames i-3 .. i-1, stacked on this stream)
+        if self._down is None:
+            yuv_ingest(self._dev_in[a], self.shape, self.fmt_in, self.coef_in, self.siting, self.lr_shape, lr_out=self._ring[i % 3])
+        else:   # (the HR buffer was last read by the previous frame's reduction, on this stream)
+            yuv_ingest(self._dev_in[a], self.shape, self.fmt_in, self.coef_in, self.siting, lr_out=self._full)
+            self._down(self._full, quantise=True, out=self._ring[i % 3])
+        st.converted[a] = torch.cuda.Event()
+        st.converted[a].record(st.main)
+
+    def _forward(self, st, i: int) -> None:
+        """The window of source frames i - 2 .. i through the model, the estimate fed back (as `run_item`)."""
+        x = torch.stack([self._ring[(i - 2) % 3], self._ring[(i - 1) % 3], self._ring[i % 3]])
+        st.est, _ = self.model(x, None, None, st.est, train=False)
+
+    def _score(self, st, j: int) -> None:
+        """Output frame `j` against source frame j + 1, and the pair (j - 1, j); every launch writes its row of `st.sums`."""
+        def row(name, k):
+            row0 = st.layout[name][0]
+            return st.sums[row0 + k:row0 + k + 1]
+        # source frame j + 1 is still in its upload slot (the other one of the pair): converted at full size into the reused HR buffer,
+        # then scored; the slot's next upload waits for this read as it does for the LR conversion
+        c = (j + 1) % 2
+        est, truth, base = st.est[0], self._slot(self._truth, j), self._slot(self._base, j)
+        yuv_ingest(self._dev_in[c], self.shape, self.fmt_in, self.coef_in, self.siting, lr_out=truth)
+        frame_metrics(est, truth, self.score, True, self.shave, out=row("estimate", j))
+        if base is not None:
+            self._up(self._ring[(j + 1) % 3], quantise=False, out=base)
+            frame_metrics(base, truth, self.score, True, self.shave, out=row("baseline", j))
+        if self.temporal is not None and j >= 1:
+            # the pair (j - 1, j) along the flows between source frames j and j + 1: the other truth buffer still holds source frame j,
+            # `prev_est` the estimate of the window before
+            truth_prev = self._slot(self._truth, j - 1)
+            flows = truth_flows(self.model, truth_prev, truth)
+            pairs = [("ewarp", st.prev_est, est), ("ewarp_truth", truth_prev, truth)]
+            if base is not None:
+                pairs.append(("ewarp_baseline", self._slot(self._base, j - 1), base))
+            for name, before, after in pairs:
+                warp_error(before, after, flows, self.score, True, self.shave, self.occ, out=row(name, j - 1))
+        st.prev_est = est
+        st.converted[c] = torch.cuda.Event()
+        st.converted[c].record(st.main)
+
+    def _write_out(self, st, j: int) -> None:
+        """Output frame `j`: written as 4:2:0 into device slot j % 2 on the current stream, copied back on the copy-out stream."""
+        b = j % 2
+        if st.copied[b] is not None:   # frame j-2 leaves the slot pair: wait for its copy, take it from the pinned buffer
+            self._take(st, b)
+            st.main.wait_event(st.copied[b][1])
+        yuv_write(st.est[0], self.fmt_out, self.coef_out, self.siting, out=self._dev_out[b])
+        ready = torch.cuda.Event()
+        ready.record(st.main)
+        st.s_out.wait_event(ready)
+        with torch.cuda.stream(st.s_out):
+            self._pin_out[b].copy_(self._dev_out[b], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(st.s_out)
+        st.copied[b] = (j, ev)
+        self.d2h_bytes += self.out_bytes
+        self.frames_out += 1
+
+    def _take(self, st, b: int) -> None:
+        """The frame in pinned output slot `b` into the output array, once its copy has finished (host wait on one event)."""
+        jj, ev = st.copied[b]
+        ev.synchronize()
+        st.out[jj] = self._pin_out[b].numpy()
+
+    def _drain(self, st) -> None:
+        """The last two output frames, and every slot idle when run() returns."""
+        for b in range(2):
+            if st.copied[b] is not None:
+                self._take(st, b)
+        for ev in st.uploaded + st.converted:
+            if ev is not None:
+                ev.synchronize()
+
+    def _collect(self, st) -> dict:
+        """`metrics` from the sums: one copy of the whole tensor (it waits for the current stream), then the host step of each series."""
+        host = st.sums.cpu().numpy()
+        metrics = {}
+        for name, (row0, rows, kind) in st.layout.items():
+            values = (psnr_ssim if kind == "frame" else ewarp)(host[row0:row0 + rows])
+            metrics.update((k, v) for k, v in zip(METRIC_KEYS[name], values) if k is not None)
+        return metrics

@@ -21,6 +21,7 @@
 //
 // The whole file is compiled without floating-point contraction (Makefile and the pragma below): luma, the SSE terms and the SSIM
 // formula round operation by operation as the header writes them; the window sums ask for their fmas by name.
+#include "frame_sums.h"
 #include "vsr_common.h"
 
 #include "../../include/vsr_hip_metric.h"
@@ -28,6 +29,9 @@
 #pragma clang fp contract(off)
 
 namespace {
+
+using vsr::sums::Luma;
+using vsr::sums::quant;
 
 constexpr int SW = VSR_METRIC_STRIP_WIDTH, SR = VSR_METRIC_SEGMENT_ROWS, FT = VSR_METRIC_FINISH_THREADS;
 constexpr int NW = 4;              // waves per workgroup = input rows per step
@@ -39,26 +43,6 @@ constexpr int XS = 80;             // doubles of one converted row (74 used)
 struct Win {
     double w[K];
 };
-struct Luma {
-    double a0, a1, a2, o;
-};
-
-__device__ inline float quant(float v) {
-    v = v >= 0.0f ? v : 0.0f;   // negatives and NaN
-    v = v > 255.0f ? 255.0f : v;
-    return rintf(v);
-}
-
-// fixed-order tree over N (a power of two) values in LDS; the total ends in red[0]
-template <int N>
-__device__ inline void tree(double* red, int tid) {
-#pragma unroll
-    for (int s = N / 2; s > 0; s >>= 1) {
-        __syncthreads();
-        if (tid < s) red[tid] += red[tid + s];
-    }
-    __syncthreads();
-}
 
 template <bool SSIM, bool YMODE, bool QUANT, bool WIDE>
 __global__ void __launch_bounds__(NW * 64)
@@ -132,8 +116,8 @@ k_metric(const float* __restrict__ a, const float* __restrict__ b, int H, int W,
                                 rb[c] = QUANT ? quant(qb[c]) : qb[c];
                             }
                             if (YMODE) {
-                                const double ya = ((lu.o + lu.a0 * (double)ra[0]) + lu.a1 * (double)ra[1]) + lu.a2 * (double)ra[2];
-                                const double yb = ((lu.o + lu.a0 * (double)rb[0]) + lu.a1 * (double)rb[1]) + lu.a2 * (double)rb[2];
+                                const double ya = vsr::sums::luma(lu, ra[0], ra[1], ra[2]);
+                                const double yb = vsr::sums::luma(lu, rb[0], rb[1], rb[2]);
                                 if (owned) {
                                     const double d = ya - yb;
                                     sse += d * d;
@@ -201,31 +185,14 @@ k_metric(const float* __restrict__ a, const float* __restrict__ b, int H, int W,
         }
         __syncthreads();   // a pass is over: the ring and the staging rows are free for the next plane
     }
-    red[0][tid] = sse;
-    red[1][tid] = ssim;
-    tree<NW * 64>(red[0], tid);
-    tree<NW * 64>(red[1], tid);
-    if (tid == 0) {
-        const size_t wg = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-        ws[2 * wg] = red[0][0];
-        ws[2 * wg + 1] = red[1][0];
-    }
+    vsr::sums::workgroup_pair<NW * 64>(red, tid, sse, ssim, ws);
 }
 
 __global__ void __launch_bounds__(FT)
 k_finish(const double* __restrict__ ws, double* __restrict__ sums, unsigned nwg, int what, double n_sse, double n_ssim) {
     __shared__ double red[2][FT];
     const int tid = threadIdx.x;
-    const double* p = ws + (size_t)blockIdx.x * nwg * 2;
-    double s0 = 0.0, s1 = 0.0;
-    for (unsigned i = tid; i < nwg; i += FT) {
-        s0 += p[2 * (size_t)i];
-        s1 += p[2 * (size_t)i + 1];
-    }
-    red[0][tid] = s0;
-    red[1][tid] = s1;
-    tree<FT>(red[0], tid);
-    tree<FT>(red[1], tid);
+    vsr::sums::finish_pair<FT>(ws, nwg, red, tid);
     if (tid == 0) {
         double* out = sums + (size_t)blockIdx.x * 4;
         out[0] = (what & VSR_METRIC_SSE) ? red[0][0] : 0.0;
@@ -297,8 +264,7 @@ int vsr_metric_frames(const float* a, const float* b, int F, int H, int W, int w
     Win win = {};
     if (ssim)
         for (int i = 0; i < K; ++i) win.w[i] = win11[i];
-    Luma lu = {};
-    if (ymode) lu = {(double)luma4[0], (double)luma4[1], (double)luma4[2], (double)luma4[3]};
+    const Luma lu = ymode ? vsr::sums::luma_of(luma4) : Luma{};
     // 16-byte loads: both bases aligned and a row pitch (so a frame) of a whole number of 16-byte groups
     const bool wide = ((pa | pb) & 15) == 0 && W % 4 == 0;
     const int planes = ymode ? 1 : 3;

@@ -25,6 +25,7 @@
 //
 // A pixel's two chains are evaluated by one thread each, in tap order, whatever the tile or group: the bits do not depend on geometry.
 // The whole file is compiled without floating-point contraction (Makefile and the pragma below); the fmas are asked for by name.
+#include "frame_sums.h"
 #include "vsr_common.h"
 
 #include "../../include/vsr_hip_resize.h"
@@ -42,11 +43,7 @@ constexpr int CH = 9;         // taps loaded together in the row pass
 static_assert(TW % 4 == 0, "a 16-byte group must not straddle two tiles");
 static_assert(ROWS_S >= MT && ROWS_L >= ROWS_S, "one output row's taps must fit the intermediate");
 
-__device__ inline float quant(float v) {
-    v = v >= 0.0f ? v : 0.0f;   // negatives and NaN
-    v = v > 255.0f ? 255.0f : v;
-    return rintf(v);
-}
+using vsr::sums::quant;
 
 __device__ inline int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 

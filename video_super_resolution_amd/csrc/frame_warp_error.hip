@@ -14,6 +14,7 @@
 //
 // The whole file is compiled without floating-point contraction (Makefile and the pragma below): every product and sum of the
 // header's steps rounds once, as a float64 restatement in numpy does.
+#include "frame_sums.h"
 #include "vsr_common.h"
 
 #include "../../include/vsr_hip_warp.h"
@@ -22,32 +23,15 @@
 
 namespace {
 
+using vsr::sums::Luma;
+using vsr::sums::quant;
+
 constexpr int TW = VSR_WARP_TILE_W, TH = VSR_WARP_TILE_H, FT = VSR_WARP_FINISH_THREADS;
 constexpr int NW = 4;   // waves per workgroup = rows of a tile in flight
 
-struct Luma {
-    double a0, a1, a2, o;
-};
 struct Occ {
     double c1, c2, g1, g2;
 };
-
-__device__ inline float quant(float v) {
-    v = v >= 0.0f ? v : 0.0f;   // negatives and NaN
-    v = v > 255.0f ? 255.0f : v;
-    return rintf(v);
-}
-
-// fixed-order tree over N (a power of two) values in LDS; the total ends in red[0]
-template <int N>
-__device__ inline void tree(double* red, int tid) {
-#pragma unroll
-    for (int s = N / 2; s > 0; s >>= 1) {
-        __syncthreads();
-        if (tid < s) red[tid] += red[tid + s];
-    }
-    __syncthreads();
-}
 
 // the planes of one source pixel: quantised when asked, then the three channels or their luma
 template <bool YMODE, bool QUANT>
@@ -56,7 +40,7 @@ __device__ inline void planes_of(const float* __restrict__ px, const Luma& lu, d
 #pragma unroll
     for (int c = 0; c < 3; ++c) r[c] = QUANT ? quant(px[c]) : px[c];
     if (YMODE) {
-        out[0] = ((lu.o + lu.a0 * (double)r[0]) + lu.a1 * (double)r[1]) + lu.a2 * (double)r[2];
+        out[0] = vsr::sums::luma(lu, r[0], r[1], r[2]);
     } else {
 #pragma unroll
         for (int c = 0; c < 3; ++c) out[c] = (double)r[c];
@@ -132,31 +116,14 @@ k_warp(const float* __restrict__ a, const float* __restrict__ b, int H, int W, i
             nvalid += 1.0;
         }
     }
-    red[0][tid] = sse;
-    red[1][tid] = nvalid;
-    tree<NW * 64>(red[0], tid);
-    tree<NW * 64>(red[1], tid);
-    if (tid == 0) {
-        const size_t wg = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-        ws[2 * wg] = red[0][0];
-        ws[2 * wg + 1] = red[1][0];
-    }
+    vsr::sums::workgroup_pair<NW * 64>(red, tid, sse, nvalid, ws);
 }
 
 __global__ void __launch_bounds__(FT)
 k_finish(const double* __restrict__ ws, double* __restrict__ sums, unsigned nwg, double planes, double n_pixels) {
     __shared__ double red[2][FT];
     const int tid = threadIdx.x;
-    const double* p = ws + (size_t)blockIdx.x * nwg * 2;
-    double s0 = 0.0, s1 = 0.0;
-    for (unsigned i = tid; i < nwg; i += FT) {
-        s0 += p[2 * (size_t)i];
-        s1 += p[2 * (size_t)i + 1];
-    }
-    red[0][tid] = s0;
-    red[1][tid] = s1;
-    tree<FT>(red[0], tid);
-    tree<FT>(red[1], tid);
+    vsr::sums::finish_pair<FT>(ws, nwg, red, tid);
     if (tid == 0) {
         double* out = sums + (size_t)blockIdx.x * 4;
         out[0] = red[0][0];
@@ -232,8 +199,7 @@ int vsr_warp_error(const float* frames_a, const float* frames_b, int P, int H, i
                 "warp_error: the flows must be aligned to their element (%d bytes)", (int)fmask + 1);
     VSR_REQUIRE(((reinterpret_cast<uintptr_t>(sums) | reinterpret_cast<uintptr_t>(ws)) & 7) == 0,
                 "warp_error: sums and the workspace must be 8-byte aligned");
-    Luma lu = {};
-    if (ymode) lu = {(double)luma4[0], (double)luma4[1], (double)luma4[2], (double)luma4[3]};
+    const Luma lu = ymode ? vsr::sums::luma_of(luma4) : Luma{};
     const Occ oc = {occ[0], occ[1], occ[2], occ[3]};
     const dim3 grid(g.tiles_x, g.tiles_y, P);
     hipStream_t s = vsr::S(stream);

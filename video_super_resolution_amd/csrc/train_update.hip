@@ -16,6 +16,7 @@
 #include <cstdint>
 #include <cstring>
 
+#include "frame_sums.h"
 #include "vsr_common.h"
 
 #include "../../include/vsr_hip_opt.h"
@@ -147,16 +148,6 @@ k_adam(const void* __restrict__ plan, const float* __restrict__ ctl, Scalars s) 
     }
 }
 
-// fixed-order tree over the NT values in LDS; the total ends in red[0]
-__device__ inline void tree(double* red, unsigned tid) {
-#pragma unroll
-    for (unsigned s = NT / 2; s > 0; s >>= 1) {
-        __syncthreads();
-        if (tid < s) red[tid] += red[tid + s];
-    }
-    __syncthreads();
-}
-
 __global__ void __launch_bounds__(NT)
 k_norm_part(const void* __restrict__ plan, double* __restrict__ ws) {
     __shared__ double red[NT];
@@ -183,7 +174,7 @@ k_norm_part(const void* __restrict__ plan, double* __restrict__ ws) {
         }
     }
     red[tid] = acc;
-    tree(red, tid);
+    vsr::sums::tree<NT>(red, tid);
     if (tid == 0) ws[blockIdx.x] = red[0];
 }
 
@@ -194,7 +185,7 @@ k_norm_fin(const double* __restrict__ ws, unsigned n_chunks, double max_norm, vs
     double acc = 0.0;
     for (unsigned i = tid; i < n_chunks; i += NT) acc += ws[i];
     red[tid] = acc;
-    tree(red, tid);
+    vsr::sums::tree<NT>(red, tid);
     if (tid == 0) {
         const double sumsq = red[0];
         const double r = max_norm / (sqrt(sumsq) + 1e-6);

@@ -1,0 +1,448 @@
+"""Frames in, out, resampled and scored on the device: the Python side of four side libraries, one section each.
+
+    read_clip_yuv / ingest_item_yuv / frames_to_yuv     ingest, and write-out for what decoders emit: packed Y'CbCr 4:2:0 frames
+                            (yuv420p, nv12, yuv420p10le, p010le), converted on the device (include/vsr_hip_yuv.h); the matrix
+                            coefficients come from `yuv_coefficients` alone
+    resize_tables / FrameResizer   float32 RGB frames resampled on the device by a separable filter given as tables
+                            (include/vsr_hip_resize.h): antialiased bicubic (Keys, a = -0.5, Pillow's convention) or bilinear; the tables
+                            come from `resize_tables` alone
+    frame_metrics / psnr_ssim   HR frames scored against ground truth on the device: the float64 sums behind PSNR and SSIM per frame
+                            (include/vsr_hip_metric.h), and the host step that forms the two numbers from them
+    truth_flows / warp_error / ewarp   the temporal warping error on the device (include/vsr_hip_warp.h): forward and backward FlowNet2
+                            flows between ground-truth frames, frame t + 1 warped back onto frame t and the squared difference summed
+                            over the pixels that are not occluded, in float64, and the host step that forms E_warp from the sums
+
+`clip_runner.ClipRunner` streams a clip through all four; `driver` imports every public name here, so `driver.frame_metrics` and the rest
+resolve as before.  Transfer functions and 4:2:2 / 4:4:4 stay out.
+"""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+
+# ------------------------------------------------------------------------------------------------ Y'CbCr 4:2:0 in and out
+YUV_FORMATS = {"yuv420p": 0, "nv12": 1, "yuv420p10le": 2, "p010le": 3}      # the `fmt` codes of include/vsr_hip_yuv.h
+YUV_SITINGS = {"left": 0, "center": 1}
+_YUV_KR_KB = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722), "bt2020": (0.2627, 0.0593)}   # bt2020: non-constant luminance
+
+
+def _yuv_depth(fmt: str) -> int:
+    if fmt not in YUV_FORMATS:
+        raise ValueError(f"unknown pixel format {fmt!r} (known: {', '.join(YUV_FORMATS)})")
+    return 10 if fmt in ("yuv420p10le", "p010le") else 8
+
+
+def yuv_frame_bytes(fmt: str, H: int, W: int) -> int:
+    """Bytes of one packed 4:2:0 frame: 3/2 samples per pixel, 1 byte (8-bit formats) or 2 bytes (10-bit formats) per sample."""
+    d = _yuv_depth(fmt)
+    if H <= 0 or W <= 0 or H % 2 or W % 2:
+        raise ValueError(f"4:2:0 needs positive even H and W, got {H} x {W}")
+    return H * W * 3 // 2 * (2 if d == 10 else 1)
+
+
+def yuv_coefficients(fmt: str, matrix: str = "bt709", full_range: bool = False, inverse: bool = False, dtype=np.float32) -> np.ndarray:
+    """The 12 values the device entries take: a row-major 3x3 matrix, then 3 offsets.  Forward (`inverse=False`): the model's R'G'B'
+    in 0..255 -> the code values (Y, Cb, Cr) of `fmt`, what `frames_to_yuv` applies; `inverse=True`: code values -> R'G'B' in 0..255,
+    what `ingest_item_yuv` applies.  With (Kr, Kb) of `matrix`, Kg = 1 - Kr - Kb, E'Y = Kr R + Kg G + Kb B, E'Cb = (B - E'Y) / (2 (1 - Kb)),
+    E'Cr = (R - E'Y) / (2 (1 - Kr)) on R'G'B' in 0..1 and d the bit depth: limited range Y = (16 + 219 E'Y) 2^(d-8),
+    C = (128 + 224 E'C) 2^(d-8); full range Y = (2^d - 1) E'Y, C = 2^(d-1) + (2^d - 1) E'C.  Computed in float64 and rounded once to
+    `dtype`; this is the single source of the coefficients (the C side computes none)."""
+    d = _yuv_depth(fmt)
+    if matrix not in _YUV_KR_KB:
+        raise ValueError(f"unknown matrix {matrix!r} (known: {', '.join(_YUV_KR_KB)})")
+    kr, kb = _YUV_KR_KB[matrix]
+    kg = 1.0 - kr - kb
+    if full_range:
+        sy = sc = float(2 ** d - 1)
+        oy, oc = 0.0, float(2 ** (d - 1))
+    else:
+        m = float(2 ** (d - 8))
+        sy, sc, oy, oc = 219.0 * m, 224.0 * m, 16.0 * m, 128.0 * m
+    gy, gc = sy / 255.0, sc / 255.0
+    if not inverse:
+        A = np.array([[gy * kr, gy * kg, gy * kb],
+                      [-gc * kr / (2 * (1 - kb)), -gc * kg / (2 * (1 - kb)), gc * 0.5],
+                      [gc * 0.5, -gc * kg / (2 * (1 - kr)), -gc * kb / (2 * (1 - kr))]], dtype=np.float64)
+        o = np.array([oy, oc, oc], dtype=np.float64)
+    else:
+        A = np.array([[1 / gy, 0.0, 2 * (1 - kr) / gc],
+                      [1 / gy, -2 * (1 - kb) * kb / kg / gc, -2 * (1 - kr) * kr / kg / gc],
+                      [1 / gy, 2 * (1 - kb) / gc, 0.0]], dtype=np.float64)
+        o = -A @ np.array([oy, oc, oc], dtype=np.float64)
+    return np.concatenate([A.reshape(-1), o]).astype(dtype)
+
+
+def read_clip_yuv(path: str, shape: Tuple[int, int], fmt: str) -> np.ndarray:
+    """A headerless 4:2:0 clip (`ffmpeg -f rawvideo -pix_fmt <fmt>`) as uint8 [T, frame_bytes]; `shape` = (H, W)."""
+    fb = yuv_frame_bytes(fmt, shape[0], shape[1])
+    a = np.fromfile(path, dtype=np.uint8)
+    if a.size == 0 or a.size % fb:
+        raise ValueError(f"{path}: {a.size} bytes is not a whole number of {fmt} frames of {shape[0]}x{shape[1]} ({fb} bytes each)")
+    return a.reshape(-1, fb)
+
+
+def _coef12(coef12) -> np.ndarray:
+    c = np.ascontiguousarray(np.asarray(coef12, dtype=np.float32).reshape(-1))
+    if c.size != 12:
+        raise ValueError(f"expected 12 coefficients (3x3 matrix, 3 offsets), got {c.size}")
+    return c
+
+
+@L.on_device
+def yuv_ingest(frames: torch.Tensor, shape: Tuple[int, int], fmt: str, coef12, siting: str = "left", lr_shape: Optional[Tuple[int, int]] = None,
+               want_hr: bool = False, lr_out: Optional[torch.Tensor] = None):
+    """The low-level call (vsr_yuv_ingest) with any 12 coefficients: uint8 [..., frame_bytes] on the device -> float32 RGB
+    (lr [..., h, w, 3], hr [..., H, W, 3] | None); `lr_shape` = (h, w), default the full size; `lr_out`: write lr there."""
+    import ctypes
+    H, W = int(shape[0]), int(shape[1])
+    fb = yuv_frame_bytes(fmt, H, W)
+    if frames.dtype != torch.uint8 or frames.dim() < 1 or frames.shape[-1] != fb:
+        raise ValueError(f"expected uint8 [..., {fb}] ({fmt} {H}x{W}), got {frames.dtype} {tuple(frames.shape)}")
+    h, w = (H, W) if lr_shape is None else (int(lr_shape[0]), int(lr_shape[1]))
+    lead = tuple(frames.shape[:-1])
+    F = int(np.prod(lead)) if lead else 1
+    c = _coef12(coef12)
+    lr = torch.empty(lead + (h, w, 3), dtype=torch.float32, device=frames.device) if lr_out is None else lr_out
+    if tuple(lr.shape) != lead + (h, w, 3):
+        raise ValueError(f"lr_out must be {lead + (h, w, 3)}, got {tuple(lr.shape)}")
+    hr = torch.empty(lead + (H, W, 3), dtype=torch.float32, device=frames.device) if want_hr else None
+    Y = L.load_yuv()
+    L.check(Y.vsr_yuv_ingest(L.dptr(frames, torch.uint8), YUV_FORMATS[fmt], c.ctypes.data_as(ctypes.c_void_p), YUV_SITINGS[siting], L.dptr(lr),
+                             L.optr(hr), F, H, W, h, w, L.stream()), "yuv_ingest", lib=Y)
+    return lr, hr
+
+
+@L.on_device
+def yuv_write(frames: torch.Tensor, fmt: str, coef12, siting: str = "left", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The low-level call (vsr_yuv_write) with any 12 coefficients: float32 [..., H, W, 3] -> uint8 [..., frame_bytes]."""
+    import ctypes
+    if frames.dim() < 3 or frames.shape[-1] != 3:
+        raise ValueError(f"expected float32 [..., H, W, 3], got {tuple(frames.shape)}")
+    f = frames.detach().to(torch.float32).contiguous()
+    H, W = int(f.shape[-3]), int(f.shape[-2])
+    fb = yuv_frame_bytes(fmt, H, W)
+    lead = tuple(f.shape[:-3])
+    F = int(np.prod(lead)) if lead else 1
+    c = _coef12(coef12)
+    if out is None:
+        out = torch.empty(lead + (fb,), dtype=torch.uint8, device=f.device)
+    elif tuple(out.shape) != lead + (fb,):
+        raise ValueError(f"out must be {lead + (fb,)}, got {tuple(out.shape)}")
+    Y = L.load_yuv()
+    L.check(Y.vsr_yuv_write(L.dptr(f), L.dptr(out, torch.uint8), YUV_FORMATS[fmt], c.ctypes.data_as(ctypes.c_void_p), YUV_SITINGS[siting],
+                            F, H, W, L.stream()), "yuv_write", lib=Y)
+    return out
+
+
+def ingest_item_yuv(frames: torch.Tensor, shape: Tuple[int, int], fmt: str, scale: int = 4, want_hr: bool = True, matrix: str = "bt709",
+                    full_range: bool = False, siting: str = "left"):
+    """`ingest_item` for 4:2:0 frames: uint8 [T,3,frame_bytes] on the device -> (data [T,3,H//s,W//s,3], target [T,1,H,W,3] | None,
+    high_frames [T,3,H,W,3] | None), float32 R'G'B' in 0..255."""
+    if frames.dim() != 3 or frames.shape[1] != 3:
+        raise ValueError(f"expected uint8 [T,3,frame_bytes], got {frames.dtype} {tuple(frames.shape)}")
+    H, W = shape
+    lr, hr = yuv_ingest(frames.contiguous(), shape, fmt, yuv_coefficients(fmt, matrix, full_range, inverse=True), siting,
+                        (int(H / scale), int(W / scale)), want_hr)
+    if hr is None:
+        return lr, None, None
+    return lr, hr[:, 1:2].clone(), hr   # (the clone: as in ingest_item)
+
+
+def frames_to_yuv(frames: torch.Tensor, fmt: str, matrix: str = "bt709", full_range: bool = False, siting: str = "left") -> torch.Tensor:
+    """float32 HR frames [...,H,W,3] (R'G'B' in 0..255) -> packed 4:2:0 frames uint8 [...,frame_bytes]: values clamped to 0..255, chroma
+    from the filtered R'G'B', round half to even, clamped to the code range."""
+    return yuv_write(frames, fmt, yuv_coefficients(fmt, matrix, full_range), siting)
+
+
+# ------------------------------------------------------------------------------------------------ resampling
+RESIZE_KERNELS = {"bicubic": 2.0, "bilinear": 1.0}   # the support of the filter at scale 1
+RESIZE_MAX_TAPS = 33                                 # VSR_RESIZE_MAX_TAPS of include/vsr_hip_resize.h
+
+
+def _resize_filter(kernel: str, x: np.ndarray) -> np.ndarray:
+    x = np.abs(x)
+    if kernel == "bilinear":
+        return np.where(x < 1.0, 1.0 - x, 0.0)
+    a = -0.5   # Keys' cubic
+    return np.where(x < 1.0, ((a + 2.0) * x - (a + 3.0)) * x * x + 1.0, np.where(x < 2.0, a * (((x - 5.0) * x + 8.0) * x - 4.0), 0.0))
+
+
+def resize_tables(n_in: int, n_out: int, kernel: str = "bicubic") -> Tuple[np.ndarray, np.ndarray]:
+    """One axis of an antialiased resize from `n_in` to `n_out` samples as the two tables vsr_resize_frames takes:
+    (first int32 [n_out], weight float32 [n_out, K]); output i is sum_k weight[i, k] * in[clamp(first[i] + k)].  Pillow's convention,
+    which is also that of torch's `interpolate(antialias=True, align_corners=False)`: scale = n_in / n_out, fs = max(scale, 1), support =
+    2 fs ("bicubic": Keys' cubic with a = -0.5) or fs ("bilinear": the triangle), K = 2 ceil(support) + 1; for output i, c = scale (i + 0.5),
+    lo = max(int(c - support + 0.5), 0), hi = min(int(c + support + 0.5), n_in), w_j = filter((j + lo - c + 0.5) / fs) for j < hi - lo over
+    their sum, first = lo; the taps from hi - lo to K - 1 carry weight 0.  Computed in float64, the weights rounded once to float32;
+    this is the single source of the coefficients (the C side computes none)."""
+    if kernel not in RESIZE_KERNELS:
+        raise ValueError(f"unknown kernel {kernel!r} (known: {', '.join(RESIZE_KERNELS)})")
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in <= 0 or n_out <= 0:
+        raise ValueError(f"sizes must be positive, got {n_in} -> {n_out}")
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    support = RESIZE_KERNELS[kernel] * fs
+    K = 2 * int(np.ceil(support)) + 1
+    if K > RESIZE_MAX_TAPS:
+        raise ValueError(f"{kernel} from {n_in} to {n_out} needs {K} taps, beyond the {RESIZE_MAX_TAPS} of the library")
+    c = scale * (np.arange(n_out, dtype=np.float64) + 0.5)
+    lo = np.maximum((c - support + 0.5).astype(np.int64), 0)       # (int(): truncation; the arguments of the ones that matter are >= 0)
+    hi = np.minimum((c + support + 0.5).astype(np.int64), n_in)
+    j = np.arange(K, dtype=np.float64)[None, :]
+    wt = _resize_filter(kernel, (j + lo[:, None] - c[:, None] + 0.5) / fs)
+    wt = np.where(j < (hi - lo)[:, None], wt, 0.0)
+    wt = wt / wt.sum(axis=1, keepdims=True)
+    return lo.astype(np.int32), np.ascontiguousarray(wt.astype(np.float32))
+
+
+@L.on_device
+def resize_frames(src: torch.Tensor, out_shape: Tuple[int, int], x_first: torch.Tensor, x_weight: torch.Tensor, y_first: torch.Tensor,
+                  y_weight: torch.Tensor, quantise: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The low-level call (vsr_resize_frames) with any tables on the device: src float32 [F,H,W,3] (or [H,W,3]) -> [F,h,w,3] ([h,w,3]);
+    x_first int32 [w], x_weight float32 [w,KX], y_first int32 [h], y_weight float32 [h,KY]."""
+    if src.dim() not in (3, 4) or src.shape[-1] != 3:
+        raise ValueError(f"expected float32 [F,H,W,3] or [H,W,3], got {tuple(src.shape)}")
+    h, w = int(out_shape[0]), int(out_shape[1])
+    H, W = int(src.shape[-3]), int(src.shape[-2])
+    lead = tuple(src.shape[:-3])
+    F = int(src.shape[0]) if src.dim() == 4 else 1
+    if tuple(x_first.shape) != (w,) or x_weight.dim() != 2 or x_weight.shape[0] != w or tuple(y_first.shape) != (h,) or y_weight.dim() != 2 \
+            or y_weight.shape[0] != h:
+        raise ValueError(f"tables do not fit {h} x {w}: x {tuple(x_first.shape)} / {tuple(x_weight.shape)}, y {tuple(y_first.shape)} / "
+                         f"{tuple(y_weight.shape)}")
+    R = L.load_resize()
+    ps = L.dptr(src)   # (raises on CPU tensors, on anything but float32 and on strided views)
+    if out is None:
+        out = torch.empty(lead + (h, w, 3), dtype=torch.float32, device=src.device)
+    elif tuple(out.shape) != lead + (h, w, 3) or out.device != src.device:
+        raise ValueError(f"out must be float32 {lead + (h, w, 3)} on {src.device}, got {tuple(out.shape)} on {out.device}")
+    L.check(R.vsr_resize_frames(ps, L.dptr(out), F, H, W, h, w, L.dptr(x_first, torch.int32), L.dptr(x_weight), int(x_weight.shape[1]),
+                                L.dptr(y_first, torch.int32), L.dptr(y_weight), int(y_weight.shape[1]), 1 if quantise else 0, L.stream()),
+            "resize_frames", lib=R)
+    return out
+
+
+class FrameResizer:
+    """Frames of `in_shape` = (H, W) resampled to `out_shape` = (h, w) by `kernel` ("bicubic" | "bilinear", antialiased: `resize_tables`):
+    the four tables are built and uploaded once; `resizer(src [F,H,W,3] or [H,W,3] float32 on the device, quantise=False, out=None)`
+    enqueues one launch on the current stream.  `quantise`: the result as an 8-bit file would hold it (clamped to 0..255, rounded half to
+    even); without it a bicubic result may leave 0..255."""
+
+    def __init__(self, in_shape: Tuple[int, int], out_shape: Tuple[int, int], kernel: str = "bicubic", device="cuda"):
+        self.in_shape = (int(in_shape[0]), int(in_shape[1]))
+        self.out_shape = (int(out_shape[0]), int(out_shape[1]))
+        self.kernel = kernel
+        yf, yw = resize_tables(self.in_shape[0], self.out_shape[0], kernel)
+        xf, xw = resize_tables(self.in_shape[1], self.out_shape[1], kernel)
+        self.device = torch.device(device)
+        self.y_first, self.y_weight, self.x_first, self.x_weight = (torch.from_numpy(a).to(self.device) for a in (yf, yw, xf, xw))
+
+    def __call__(self, src: torch.Tensor, quantise: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if not src.is_cuda:
+            raise L.VsrHipError("device path called with a CPU tensor (no CPU fallback exists)")
+        if src.dim() not in (3, 4) or tuple(src.shape[-3:]) != self.in_shape + (3,):
+            raise ValueError(f"expected float32 [F,{self.in_shape[0]},{self.in_shape[1]},3], got {tuple(src.shape)}")
+        if src.device != self.x_first.device:
+            raise ValueError(f"the tables live on {self.x_first.device}, the frames on {src.device}")
+        return resize_frames(src, self.out_shape, self.x_first, self.x_weight, self.y_first, self.y_weight, quantise, out)
+
+
+# ------------------------------------------------------------------------------------------------ PSNR / SSIM
+METRIC_CHANNELS = {"rgb": 0, "y": 1}     # the `channels` codes of include/vsr_hip_metric.h
+METRIC_WHAT = {"psnr": 1, "ssim": 2}     # the bits of `what`: PSNR needs the SSE
+
+
+def ssim_window() -> np.ndarray:
+    """The normalised 1-D window of SSIM (Wang et al. 2004): 11 taps of exp(-(i - 5)^2 / (2 * 1.5^2)) over their sum, float64; the 2-D
+    window is its outer product."""
+    g = np.exp(-((np.arange(11, dtype=np.float64) - 5.0) ** 2) / (2.0 * 1.5 ** 2))
+    return g / g.sum()
+
+
+# the arguments and the sums `frame_metrics` and `warp_error` have in common
+def _channel_code(channels: str) -> int:
+    if channels not in METRIC_CHANNELS:
+        raise ValueError(f"unknown channels {channels!r} (known: {', '.join(METRIC_CHANNELS)})")
+    return METRIC_CHANNELS[channels]
+
+
+def _frame_pair(a: torch.Tensor, b: torch.Tensor, many: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Two frame sets of one shape, [H,W,3] (one frame) or [`many`,H,W,3] -> both as contiguous [N,H,W,3]."""
+    if tuple(a.shape) != tuple(b.shape) or a.dim() not in (3, 4) or a.shape[-1] != 3:
+        raise ValueError(f"expected two float32 tensors of one shape [H,W,3] or [{many},H,W,3], got {tuple(a.shape)} and {tuple(b.shape)}")
+    if a.dim() == 3:
+        a, b = a[None], b[None]
+    return a.detach().contiguous(), b.detach().contiguous()
+
+
+def _luma4(channels: str, matrix: str, full_range: bool) -> Optional[np.ndarray]:
+    """{a0, a1, a2, o} of the luma the kernels form in "y" mode: row 0 of `yuv_coefficients` and its offset, float32."""
+    if channels != "y":
+        return None
+    c = yuv_coefficients("yuv420p", matrix, full_range)
+    return np.ascontiguousarray(np.array([c[0], c[1], c[2], c[9]], dtype=np.float32))
+
+
+def _sums_out(out: Optional[torch.Tensor], n: int, device) -> torch.Tensor:
+    """The [n,4] float64 tensor the sums go to: `out` if it fits (rows of a larger tensor will do), else a new one."""
+    if out is None:
+        return torch.empty((n, 4), dtype=torch.float64, device=device)
+    if tuple(out.shape) != (n, 4) or out.device != device:
+        raise ValueError(f"out must be float64 {(n, 4)} on {device}, got {tuple(out.shape)} on {out.device}")
+    return out
+
+
+def _sums_array(sums) -> np.ndarray:
+    """Sums [n,4] (a tensor, copied to the host here, or an array) as a float64 array [n,4]."""
+    s = sums.detach().cpu().numpy() if isinstance(sums, torch.Tensor) else np.asarray(sums)
+    return np.asarray(s, dtype=np.float64).reshape(-1, 4)
+
+
+@L.on_device
+def frame_metrics(a: torch.Tensor, b: torch.Tensor, channels: str = "rgb", quantise: bool = True, shave: int = 0, what=("psnr", "ssim"),
+                  matrix: str = "bt601", full_range: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """float32 RGB frames `a`, `b` ([H,W,3], [1,H,W,3] or [F,H,W,3], 0..255) -> the device tensor [F,4] float64 of
+    {sse, n_sse, ssim_sum, n_ssim} per frame (vsr_metric_frames); nothing is synchronised, `psnr_ssim` is the host step.
+    `quantise`: score what write-out stores (clamp to 0..255, round half to even); `shave`: pixels dropped on every side;
+    `channels="y"`: on the luma of `matrix` / `full_range` (row 0 of `yuv_coefficients`; the default is BT.601 limited range, the
+    literature's "Y"); `what`: "psnr" and / or "ssim" (the slots of the other are 0); `out`: write the sums there ([F,4] float64)."""
+    import ctypes
+    code = _channel_code(channels)
+    names = (what,) if isinstance(what, str) else tuple(what)
+    if not names or any(n not in METRIC_WHAT for n in names):
+        raise ValueError(f"what must name 'psnr' and / or 'ssim', got {what!r}")
+    bits = 0
+    for n in names:
+        bits |= METRIC_WHAT[n]
+    fa, fb = _frame_pair(a, b, "F")
+    shave = int(shave)
+    F, H, W = int(fa.shape[0]), int(fa.shape[1]), int(fa.shape[2])
+    if shave < 0 or 2 * shave >= min(H, W):
+        raise ValueError(f"shave {shave} leaves nothing of {H} x {W}")
+    if bits & 2 and min(H, W) - 2 * shave < 11:
+        raise ValueError(f"SSIM needs 11 pixels each way after the shave, got {min(H, W) - 2 * shave}")
+    luma4 = _luma4(channels, matrix, full_range)
+    win = ssim_window()
+    M = L.load_metric()
+    pa, pb = L.dptr(fa), L.dptr(fb)   # (raises on CPU tensors and on anything but float32)
+    if fb.device != fa.device:
+        raise ValueError("the two tensors live on different devices")
+    out = _sums_out(out, F, fa.device)
+    ws = torch.empty(int(M.vsr_metric_ws_bytes(F, H, W, shave, bits)), dtype=torch.uint8, device=fa.device)
+    L.check(M.vsr_metric_frames(pa, pb, F, H, W, bits, code, 1 if quantise else 0, shave,
+                                None if luma4 is None else luma4.ctypes.data_as(ctypes.c_void_p), win.ctypes.data_as(ctypes.c_void_p),
+                                L.dptr(out, torch.float64), L.dptr(ws, torch.uint8), L.stream()), "metric_frames", lib=M)
+    return out
+
+
+def psnr_ssim(sums) -> Tuple[np.ndarray, np.ndarray]:
+    """The host step after `frame_metrics`: sums [F,4] (a tensor, copied to the host here, or an array) -> (PSNR [F] in dB,
+    SSIM [F]).  PSNR = 10 log10(255^2 n_sse / sse), `inf` where sse == 0; SSIM = ssim_sum / n_ssim.  A metric that was not asked for
+    (its count is 0) comes back as NaN."""
+    s = _sums_array(sums)
+    sse, n_sse, ssim_sum, n_ssim = s[:, 0], s[:, 1], s[:, 2], s[:, 3]
+    psnr = np.full(s.shape[0], np.nan)
+    ssim = np.full(s.shape[0], np.nan)
+    on = n_sse > 0
+    psnr[on & (sse == 0)] = np.inf
+    pos = on & (sse > 0)
+    psnr[pos] = 10.0 * np.log10(255.0 ** 2 * n_sse[pos] / sse[pos])
+    on = n_ssim > 0
+    ssim[on] = ssim_sum[on] / n_ssim[on]
+    return psnr, ssim
+
+
+# ------------------------------------------------------------------------------------------------ temporal warping error
+WARP_OCC = (0.01, 0.5, 0.01, 0.002)   # {c1, c2, g1, g2} of the occlusion rule (Ruder, Dosovitskiy, Brox 2016)
+_truth_flow_exec = None               # model -> its FlowNet2 executor for `truth_flows` (made on first use)
+
+
+def truth_flows(model, frames_t: torch.Tensor, frames_t1: torch.Tensor):
+    """The optical flow between ground-truth frames, the guide of `warp_error`: float32 RGB frames [P,H,W,3] (or [H,W,3]) at time t and
+    at time t + 1 -> (forward flows t -> t + 1, backward flows t + 1 -> t, crop (y0, x0, h, w)), all 2 P flows as one FlowNet2 batch over
+    the centre crop to multiples of 64, in the precision `model.precision` selects: "fp32" planar float32 [P,2,h,w]; "fp16" the executor's
+    NHWC half map [P,h,w,ld] with the flow in channels 0 and 1.  The executor is one of this function's own per model: its buffers hold
+    the geometry of the truth frames, and `model._flow_exec`, whose buffers hold the LR geometry of the windows, is left alone."""
+    global _truth_flow_exec
+    if frames_t.dim() == 3:
+        frames_t, frames_t1 = frames_t[None], frames_t1[None]
+    if tuple(frames_t.shape) != tuple(frames_t1.shape) or frames_t.dim() != 4 or frames_t.shape[-1] != 3:
+        raise ValueError(f"expected two float32 tensors of one shape [H,W,3] or [P,H,W,3], got {tuple(frames_t.shape)} and {tuple(frames_t1.shape)}")
+    P = int(frames_t.shape[0])
+    net = None
+    if model._fast():
+        import weakref
+        from .trunk_exec import FlowNet2Exec, TrunkExecCache
+        if _truth_flow_exec is None:
+            _truth_flow_exec = weakref.WeakKeyDictionary()
+        if model not in _truth_flow_exec:
+            _truth_flow_exec[model] = TrunkExecCache(model.FlowModule.net, FlowNet2Exec)
+        net = _truth_flow_exec[model].get()
+    pairs = [(frames_t[p], frames_t1[p]) for p in range(P)] + [(frames_t1[p], frames_t[p]) for p in range(P)]
+    flows, crop = model.FlowModule.flow_pairs(pairs, net)
+    return flows[:P], flows[P:], crop
+
+
+@L.on_device
+def warp_error(a: torch.Tensor, b: torch.Tensor, flows, channels: str = "rgb", quantise: bool = True, shave: int = 0, occ=None,
+               out: Optional[torch.Tensor] = None, matrix: str = "bt601", full_range: bool = False, luma4=None) -> torch.Tensor:
+    """float32 RGB frames `a` (time t) and `b` (time t + 1) ([H,W,3] or [P,H,W,3], 0..255) and `flows` = (forward, backward, crop) as
+    `truth_flows` returns them -> the device tensor [P,4] float64 of {sse, n_terms, n_valid, n_pixels} per pair (vsr_warp_error,
+    include/vsr_hip_warp.h): frame b warped back onto frame a along the forward flow, the squared difference summed over the pixels of
+    the crop that are in frame, forward-backward consistent and off a motion boundary.  Nothing is synchronised, `ewarp` is the host
+    step.  `quantise`, `shave` (counted inside the crop), `channels`, `matrix`, `full_range`: as `frame_metrics`; `luma4`: four float32
+    {a0, a1, a2, o} in place of the matrix's luma row; `occ`: {c1, c2, g1, g2}, default `WARP_OCC`; `out`: write the sums there ([P,4]
+    float64, rows of a larger tensor will do)."""
+    import ctypes
+    code = _channel_code(channels)
+    fwd, bwd, crop = flows
+    fa, fb = _frame_pair(a, b, "P")
+    P, H, W = int(fa.shape[0]), int(fa.shape[1]), int(fa.shape[2])
+    y0, x0, h, w = (int(v) for v in crop)
+    shave = int(shave)
+    if h <= 0 or w <= 0 or y0 < 0 or x0 < 0 or y0 + h > H or x0 + w > W:
+        raise ValueError(f"the crop {(y0, x0, h, w)} leaves the frame of {H} x {W}")
+    if shave < 0 or 2 * shave >= min(h, w):
+        raise ValueError(f"shave {shave} leaves nothing of the crop of {h} x {w}")
+    if fwd.dtype != bwd.dtype or tuple(fwd.shape) != tuple(bwd.shape) or fwd.stride() != bwd.stride():
+        raise ValueError("the forward and the backward flows must have one dtype, shape and layout")
+    if fwd.dtype == torch.float32 and tuple(fwd.shape) == (P, 2, h, w):
+        ftype, strides = 0, (2 * h * w, h * w, 1)                                # VSR_WARP_FLOW_F32, planar
+    elif fwd.dtype == torch.float16 and fwd.dim() == 4 and tuple(fwd.shape[:3]) == (P, h, w) and fwd.shape[3] >= 2:
+        ftype, strides = 1, (h * w * int(fwd.shape[3]), 1, int(fwd.shape[3]))    # VSR_WARP_FLOW_F16, NHWC with the flow in channels 0, 1
+    else:
+        raise ValueError(f"flows must be float32 {(P, 2, h, w)} or float16 {(P, h, w)} + (ld,), got {fwd.dtype} {tuple(fwd.shape)}")
+    if luma4 is not None:
+        luma4 = np.ascontiguousarray(np.asarray(luma4, dtype=np.float32).reshape(4))
+    else:
+        luma4 = _luma4(channels, matrix, full_range)
+    occ4 = np.ascontiguousarray(np.asarray(WARP_OCC if occ is None else occ, dtype=np.float64).reshape(4))
+    M = L.load_warp()
+    pa, pb = L.dptr(fa), L.dptr(fb)   # (raises on CPU tensors and on anything but float32)
+    pf, pg = L.dptr(fwd, fwd.dtype), L.dptr(bwd, bwd.dtype)
+    if any(t.device != fa.device for t in (fb, fwd, bwd)):
+        raise ValueError("the frames and the flows live on different devices")
+    out = _sums_out(out, P, fa.device)
+    ws = torch.empty(int(M.vsr_warp_ws_bytes(P, h, w, shave)), dtype=torch.uint8, device=fa.device)
+    L.check(M.vsr_warp_error(pa, pb, P, H, W, y0, x0, h, w, pf, pg, ftype, strides[0], strides[1], strides[2], code,
+                             1 if quantise else 0, shave, None if luma4 is None else luma4.ctypes.data_as(ctypes.c_void_p),
+                             occ4.ctypes.data_as(ctypes.c_void_p), L.dptr(out, torch.float64), L.dptr(ws, torch.uint8), L.stream()),
+            "warp_error", lib=M)
+    return out
+
+
+def ewarp(sums) -> Tuple[np.ndarray, np.ndarray]:
+    """The host step after `warp_error`: sums [P,4] (a tensor, copied to the host here, or an array) -> (E_warp [P] = sse / n_terms /
+    255^2, the mean squared warping error over the valid pixels in the 0..1 range of Lai et al. 2018; valid share [P] = n_valid /
+    n_pixels).  E_warp is NaN where no pixel is valid."""
+    s = _sums_array(sums)
+    e = np.full(s.shape[0], np.nan)
+    on = s[:, 2] > 0
+    e[on] = s[on, 0] / s[on, 1] / 255.0 ** 2
+    return e, s[:, 2] / s[:, 3]
