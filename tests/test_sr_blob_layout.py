@@ -6,6 +6,7 @@ section changes a digest).  No kernel of the project runs; packing needs the mai
 import hashlib
 import json
 import os
+import subprocess
 
 import numpy as np
 import pytest
@@ -74,6 +75,42 @@ def _compare(got):
 
 def test_blobs_are_the_bytes_recorded_before_the_packers_moved():
     _compare(collect("cpu"))
+
+
+_TAP_TABLE_MAIN = r"""
+#include <cstdio>
+#include "sr_s3_taps.h"
+int main() {
+    const int ds[3] = {1, 0, -1};
+    for (int wv = 0; wv < 4; ++wv)
+        for (int p = 0; p < ph_cnt(wv); ++p)
+            for (int dy : ds)
+                for (int dx : ds) {
+                    const int r = ph_r(wv, p), c = ph_c(wv, p);
+                    if (tap_ok(r, dy) && tap_ok(c, dx)) std::printf("%d %d %d %d\n", wv, tap_slot(wv, p, dy, dx), r + 2 - 3 * dy, c + 2 - 3 * dx);
+                }
+    return 0;
+}
+"""
+
+
+def test_x3_tap_table_of_the_kernels_header_is_the_packers_slot_order(tmp_path):
+    """csrc/sr_s3_taps.h (the one statement of the x3 phase sets and tap slots both x3 kernels compile) against sr_pack._s3_slots (the
+    order the packers fill the slots in): a plain C++17 host program prints (wave, slot, ky, kx) of every live tap from the header's
+    constexpr functions; the 13 + 12 + 12 + 12 = 49 rows are the packers', each exactly once.  No kernel and no library is involved."""
+    from video_super_resolution_amd import _lib, sr_pack
+    csrc = os.path.join(os.path.dirname(os.path.abspath(_lib.__file__)), "csrc")
+    src, exe = tmp_path / "tap_table.cpp", tmp_path / "tap_table"
+    src.write_text(_TAP_TABLE_MAIN)
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")   # the compiler _lib.build() runs through csrc/Makefile
+    subprocess.run([hipcc, "-std=c++17", "-x", "c++", "-Wall", "-I", csrc, str(src), "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
+    rows = [tuple(int(v) for v in line.split()) for line in out.splitlines()]
+    want = list(sr_pack._s3_slots())
+    assert len(want) == 49 and [sum(1 for r in want if r[0] == wv) for wv in range(4)] == [13, 12, 12, 12]
+    assert len(set(rows)) == len(rows) == 49
+    assert sorted(rows) == sorted(want)
+    assert rows == want   # and in the packers' order: a wave's slots ascend as its phases, rows and columns are walked
 
 
 @pytest.mark.gpu

@@ -234,10 +234,7 @@ extern "C" int vsr_hg_front_f16(const void* in4, const void* w1_packed, const fl
     p.ntiles = (int)ntiles;
     const int lds = 2 * ST_PATCH + ST_OUT + 64 * (2 * c2 + 16);
     static unsigned long long raised = 0;
-    if (lds > 64 * 1024 && !vsr::device_marked(raised)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_hg_front), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        vsr::mark_device(raised);
-    }
+    if (lds > 64 * 1024) vsr::raise_lds_limit_once(raised, &k_hg_front, 160 * 1024);
     const unsigned grid = (unsigned)(ntiles < 512 ? ntiles : 512);   // two 4-wave workgroups resident per CU
     vsr::route("hg_front");
     hipLaunchKernelGGL(k_hg_front, dim3(grid), dim3(256), lds, vsr::S(stream), p);

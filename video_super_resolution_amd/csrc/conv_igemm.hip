@@ -1828,11 +1828,7 @@ struct BigLds {   // a kernel whose dynamic LDS can exceed 64 KB: the limit is r
     conv_kernel_t k;
     unsigned long long raised;
 };
-static void raise_lds(BigLds& e) {
-    if (vsr::device_marked(e.raised)) return;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(e.k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    vsr::mark_device(e.raised);
-}
+static void raise_lds(BigLds& e) { vsr::raise_lds_limit_once(e.raised, e.k, 160 * 1024); }
 
 // Launches the route `r` of the layer in `p` (p.splits / p.ws set from r) and, after a split-K launch, the finish.
 static int launch_route(const ConvP& p, const ConvRoute& r, hipStream_t st) {

@@ -181,10 +181,7 @@ template <int KH, int MT, int WPS>
 int launch_pf(const ConvP& p, int N, hipStream_t stream) {
     typedef PfGeom<KH, MT> G;
     static unsigned long long raised = 0;
-    if (G::LDS > 64 * 1024 && !vsr::device_marked(raised)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_patch_pf<KH, MT, WPS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        vsr::mark_device(raised);
-    }
+    if (G::LDS > 64 * 1024) vsr::raise_lds_limit_once(raised, &k_conv_patch_pf<KH, MT, WPS>, 160 * 1024);
     const int tiles_x = (int)vsr::cdiv(p.Wo, P8_W), tiles_y = (int)vsr::cdiv(p.Ho, P8_H);
     const long long nwork = (long long)N * tiles_x * tiles_y * (p.cout_pad / (16 * MT));
     if (nwork >= (1ll << 30)) return vsr::fail(VSR_E_ARG, "conv2d/patch_pf: %lld work items", nwork);

@@ -245,10 +245,7 @@ int launch_bn(const ConvP& p, hipStream_t stream) {
     if (lds > 160 * 1024) return vsr::fail(VSR_E_ARG, "conv2d/tile: %d K steps per workgroup exceed the walk table (split K further)", ks_per);
     if ((unsigned long long)npair * p.cout_pad * 64 >= (1ull << 30)) return vsr::fail(VSR_E_ARG, "conv2d/tile: packed weights beyond 1 GiB");
     static unsigned long long raised = 0;
-    if (lds > 64 * 1024 && !vsr::device_marked(raised)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_tile<BN>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        vsr::mark_device(raised);
-    }
+    if (lds > 64 * 1024) vsr::raise_lds_limit_once(raised, &k_conv_tile<BN>, 160 * 1024);
     const unsigned grid = (unsigned)((nwg + 7) / 8 * 8);
     hipLaunchKernelGGL((k_conv_tile<BN>), dim3(grid), dim3(256), lds, stream, p, gx, gy, (int)nwg);
     return VSR_OK;

@@ -1202,11 +1202,6 @@ k_fc_planes(const float* __restrict__ prefc, const float* __restrict__ w1, const
 #pragma clang fp contract(off)
 #endif  // VSR_X
 
-__device__ __forceinline__ float fc_lerp4(float v00, float v01, float v10, float v11, float lx, float ly) {
-    const float top = __builtin_fmaf(lx, v01, (1.0f - lx) * v00), bot = __builtin_fmaf(lx, v11, (1.0f - lx) * v10);
-    return __builtin_fmaf(ly, bot, (1.0f - ly) * top);
-}
-
 template <int NPL, int HID>
 __global__ void __launch_bounds__(256)
 k_fc_planes_skip(const float* __restrict__ raw, const float* __restrict__ x, const float* __restrict__ tpar,
@@ -1229,7 +1224,7 @@ k_fc_planes_skip(const float* __restrict__ raw, const float* __restrict__ x, con
         const float* xp = x + ((size_t)i * 3 + c) * (size_t)h * w;
         const float v00 = __builtin_fmaf(xp[(size_t)y0 * w + x0i], sub_s, sub_b), v01 = __builtin_fmaf(xp[(size_t)y0 * w + x1i], sub_s, sub_b);
         const float v10 = __builtin_fmaf(xp[(size_t)y1 * w + x0i], sub_s, sub_b), v11 = __builtin_fmaf(xp[(size_t)y1 * w + x1i], sub_s, sub_b);
-        v[i] = __builtin_fmaf(fc_lerp4(v00, v01, v10, v11, lx, ly) + raw[((size_t)i * 3 + c) * P + p], add_s, add_b);
+        v[i] = __builtin_fmaf(lerp4(v00, v01, v10, v11, lx, ly) + raw[((size_t)i * 3 + c) * P + p], add_s, add_b);
     }
     float o = b2[0];
 #pragma unroll
@@ -1280,7 +1275,7 @@ k_fc_planes_skip4(const float* __restrict__ raw, const float* __restrict__ x, co
         for (int j = 0; j < 4; ++j) {
             const float v00 = xa[j] == q ? a1 : (xa[j] == cm ? a0 : a2), v01 = xb[j] == q ? a1 : (xb[j] == cm ? a0 : a2);
             const float v10 = xa[j] == q ? c1 : (xa[j] == cm ? c0 : c2), v11 = xb[j] == q ? c1 : (xb[j] == cm ? c0 : c2);
-            v[i][j] = __builtin_fmaf(fc_lerp4(v00, v01, v10, v11, lx[j], ly) + rw[j], add_s, add_b);
+            v[i][j] = __builtin_fmaf(lerp4(v00, v01, v10, v11, lx[j], ly) + rw[j], add_s, add_b);
         }
     }
     f2 o[2] = {f2{b2[0], b2[0]}, f2{b2[0], b2[0]}};
@@ -1376,12 +1371,7 @@ int vsr_sr_utd_f16(const void* in, const void* blob, void* out, int N, int h, in
     typedef void (*kern_t)(const _Float16*, const unsigned char*, _Float16*, int, int, int);
     static const kern_t kerns[4] = {k_utd<0, false>, k_utd<0, true>, k_utd<1, false>, k_utd<1, true>};
     static unsigned long long attr_devs = 0;   // one bit per device: the attribute is per device
-    if (!vsr::device_marked(attr_devs)) {
-        for (kern_t k : kerns)
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, UTD_LDS) != hipSuccess)
-                return vsr::fail(VSR_E_LAUNCH, "sr_utd: cannot reserve %d bytes of LDS", UTD_LDS);
-        vsr::mark_device(attr_devs);
-    }
+    if (!vsr::raise_lds_limit(attr_devs, kerns, 4, UTD_LDS)) return vsr::fail(VSR_E_LAUNCH, "sr_utd: cannot reserve %d bytes of LDS", UTD_LDS);
     // fused stage: one wave per SIMD (k_utd3, sr_utd3.hip) unless the two-waves-per-SIMD build is selected
     if (!deconv_only && (g_utd_variant == 0 || g_utd_variant == 2 || g_utd_variant == 4))
         return vsr::launch_utd3(in, blob, out, N, h, w, rows_per_seg, slopes_le_one, g_utd_variant / 2, vsr::S(stream));
@@ -1490,13 +1480,10 @@ int vsr_sr_utd2_f16(const void* in, const void* blob_v2, void* out, int N, int h
                     (reinterpret_cast<uintptr_t>(out) & 15) == 0, "sr_utd2: pointers must be 16-byte aligned");
     const unsigned strips = vsr::cdiv(w, TX), segs = vsr::cdiv(h, rows_per_seg);
     VSR_REQUIRE(segs <= 65535, "sr_utd2: too many row segments");
+    typedef void (*kern_t)(const _Float16*, const unsigned char*, _Float16*, int, int, int);
+    static const kern_t kerns[2] = {k_utd2<false>, k_utd2<true>};
     static unsigned long long attr_devs = 0;   // one bit per device: the attribute is per device
-    if (!vsr::device_marked(attr_devs)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_utd2<false>), hipFuncAttributeMaxDynamicSharedMemorySize, UTD_LDS) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_utd2<true>), hipFuncAttributeMaxDynamicSharedMemorySize, UTD_LDS) != hipSuccess)
-            return vsr::fail(VSR_E_LAUNCH, "sr_utd2: cannot reserve %d bytes of LDS", UTD_LDS);
-        vsr::mark_device(attr_devs);
-    }
+    if (!vsr::raise_lds_limit(attr_devs, kerns, 2, UTD_LDS)) return vsr::fail(VSR_E_LAUNCH, "sr_utd2: cannot reserve %d bytes of LDS", UTD_LDS);
     if (slopes_le_one)
         hipLaunchKernelGGL(k_utd2<true>, dim3(strips, segs, N), dim3(512), UTD_LDS, vsr::S(stream), (const _Float16*)in,
                            (const unsigned char*)blob_v2, (_Float16*)out, h, w, rows_per_seg);
@@ -1518,12 +1505,7 @@ static int tail_launch(const void* hid_nhwc, const void* blob, const void* conv_
     typedef void (*kern_t)(const _Float16*, const unsigned char*, const unsigned char*, const float*, const float*, float*, int, int, int);
     static const kern_t kerns[4] = {k_tail<false, false>, k_tail<true, false>, k_tail<false, true>, k_tail<true, true>};
     static unsigned long long attr_devs = 0;   // one bit per device: the attribute is per device
-    if (!vsr::device_marked(attr_devs)) {
-        for (kern_t k : kerns)
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess)
-                return vsr::fail(VSR_E_LAUNCH, "sr_tail_f16: cannot reserve %d bytes of LDS", LDS);
-        vsr::mark_device(attr_devs);
-    }
+    if (!vsr::raise_lds_limit(attr_devs, kerns, 4, LDS)) return vsr::fail(VSR_E_LAUNCH, "sr_tail_f16: cannot reserve %d bytes of LDS", LDS);
     hipLaunchKernelGGL(kerns[(dec ? 2 : 0) + (slopes_le_one ? 1 : 0)], dim3(strips, segs, N), dim3(512), LDS, vsr::S(stream),
                        (const _Float16*)hid_nhwc, (const unsigned char*)blob, (const unsigned char*)conv_out_frags, tail_params, x,
                        prefc, h, w, rows_per_seg);

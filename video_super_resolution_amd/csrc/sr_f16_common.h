@@ -1,7 +1,7 @@
 // sr_f16_common.h -- constants, LDS layout and small device helpers shared by the fused-stage kernels
-// (sr_f16.hip: k_utd, k_utd2, k_tail;  sr_utd3.hip: k_utd3).
+// (sr_f16.hip: k_utd, k_utd2, k_tail;  sr_utd3.hip: k_utd3;  the x4, x2 and x3 stages and tails behind them).
 #pragma once
-#include "vsr_common.h"
+#include "sr_pixel_math.h"
 
 namespace {
 
@@ -9,6 +9,7 @@ typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef float f2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u4v __attribute__((ext_vector_type(4)));
 
 constexpr int NF = 32;
 constexpr int TX = 31;              // LR output columns per strip (TX + 1 = 32 deconv positions = 2 MFMA tiles)
@@ -39,7 +40,8 @@ constexpr int BLOB_BYTES = BLOB_CO + BLOB_CO_BYTES;
 static_assert(RING_BYTES % 16 == 0 && PART_BYTES % 16 == 0 && LR_SLOT % 16 == 0, "LDS carve must stay 16-B aligned");
 static_assert(UTD_LDS <= 160 * 1024, "LDS budget");
 
-__device__ __forceinline__ float prelu(float v, float a) { return v >= 0.0f ? v : v * a; }
+// nothing is scheduled across it: the hand-placed step schedules fence every MFMA gap
+#define VSR_FENCE() __builtin_amdgcn_sched_barrier(0)
 
 // PReLU on packed fp16 pairs: max(v, a*v) for a <= 1, min(v, a*v) for a > 1 (one v_pk_mul + one v_pk_max/min per pair)
 __device__ __forceinline__ h2 prelu_h2(h2 v, h2 a, bool use_max) {
@@ -98,6 +100,34 @@ __device__ __forceinline__ int ring_off(int cc, int chunk) { return cc * COL_PIT
 // byte offset of (pixel p, 16-byte chunk) inside an LR ring slot (64-byte pitch, chunk XOR pixel bits 1-2)
 __device__ __forceinline__ int lr_off(int p, int chunk) { return p * 64 + ((chunk ^ ((p >> 1) & 3)) << 4); }
 
+// byte offset of (HR column xr, 16-byte chunk) inside a row of the x2 / x3 tails' HR ring (sr_tail_s2.hip: 64 columns, sr_tail_s3.hip:
+// 96): chunk XOR column bits 1-2.  The deconvolution writes columns S n + c from 16 lanes (a ds_write_b128 lane group is 8 lanes of one
+// chunk, 128- or 192-byte stride), the 3x3 reads 16 consecutive columns (a ds_read_b128 group: 16 lanes of two chunks): the XOR puts
+// either on distinct banks.
+__device__ __forceinline__ int hr_off(int xr, int chunk) { return xr * 64 + ((chunk ^ ((xr >> 1) & 3)) << 4); }
+
+// tile pair T (pixel tiles 0, 1: deconv positions n = 16 nt + lane&15) moved down SH lanes: B[nt] lane <- position n + SH
+// (the down-convolutions of k_utd_s2 and k_utd_s3 read their tile shifted by the tap)
+template <int SH>
+__device__ __forceinline__ void shift_tiles(const h8 (&T)[2], h8 (&B)[2]) {
+    if (SH == 0) {
+        B[0] = T[0];
+        B[1] = T[1];
+        return;
+    }
+    const u4v v0 = __builtin_bit_cast(u4v, T[0]), v1 = __builtin_bit_cast(u4v, T[1]);
+    u4v b0, b1;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        // lanes 16-SH .. 15 of tile 0 take lanes 0 .. SH-1 of tile 1 (row_ror:16-SH), the others their right neighbour (row_shl:SH)
+        const unsigned ror = (unsigned)__builtin_amdgcn_mov_dpp((int)v1[q], 0x120 + (16 - SH), 0xF, 0xF, false);
+        b0[q] = (unsigned)__builtin_amdgcn_update_dpp((int)ror, (int)v0[q], 0x100 + SH, 0xF, 0xF, false);
+        b1[q] = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v1[q], 0x100 + SH, 0xF, 0xF, true);   // positions >= 32: zeros (discarded outputs)
+    }
+    B[0] = __builtin_bit_cast(h8, b0);
+    B[1] = __builtin_bit_cast(h8, b1);
+}
+
 // bilinear x4, align_corners=False, as ATen's upsample_bilinear2d: src = (dst+0.5)/4-0.5 clamped at 0
 __device__ __forceinline__ void bil4(int dst, int n, int& i0, int& i1, float& l1) {
     float src = ((float)dst + 0.5f) * 0.25f - 0.5f;
@@ -109,6 +139,8 @@ __device__ __forceinline__ void bil4(int dst, int n, int& i0, int& i1, float& l1
 
 template <bool B>
 struct BoolC { static constexpr bool value = B; };
+template <int V>
+struct IntC { static constexpr int value = V; };
 
 // host: do the byte ranges [a, a + na) and [b, b + nb) share a byte (the entries refuse overlapping buffers before they launch)
 inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {

@@ -8,14 +8,12 @@
 // Thread mapping everywhere: one thread = one pixel, all 32 output channels in registers; lanes
 // run along x so activations are coalesced and every weight address is wave-uniform (scalar
 // loads, no LDS needed).  These kernels are VALU-bound, not the throughput path.
-#include "vsr_common.h"
+#include "sr_pixel_math.h"
 
 namespace {
 
 constexpr int NF = 32;  // num_features of the reference (SRProjectionModule.py:97)
 constexpr int kBlock = 256;
-
-__device__ __forceinline__ float prelu(float v, float slope) { return v >= 0.0f ? v : v * slope; }
 
 // ---- head: sub_mean -> conv3x3(3->nmid)+PReLU -> conv1x1(nmid->32)+PReLU (SRProjectionModule.py:135-138)
 __global__ void __launch_bounds__(kBlock) k_head(const float* __restrict__ x, const float* __restrict__ sub_scale,
@@ -161,17 +159,6 @@ __global__ void __launch_bounds__(kBlock) k_conv(const float* __restrict__ in, c
     }
 #pragma unroll
     for (int k = 0; k < NF; ++k) out[((size_t)n * NF + k) * hw + (size_t)iy * w + ix] = prelu(acc[k], slope);
-}
-
-// bilinear xS, align_corners=False, as ATen's upsample_bilinear2d: src = (dst+0.5)/S-0.5 clamped at 0,
-// i1 = min(i0+1, n-1).  `inv` = 1/S as ATen forms it (0.25, 0.5 exact; 1/3 rounded once, like `1.0 / scale_factor`
-// cast to float there).
-__device__ __forceinline__ void bil(int dst, int n, float inv, int& i0, int& i1, float& l1) {
-    float src = ((float)dst + 0.5f) * inv - 0.5f;
-    if (src < 0.0f) src = 0.0f;
-    i0 = (int)src;
-    i1 = i0 + (i0 < n - 1 ? 1 : 0);
-    l1 = src - (float)i0;
 }
 
 // ---- conv_out 3x3 (32->3) + bilinear skip of sub_mean(x) + add_mean (SRProjectionModule.py:136,142-143)

@@ -10,14 +10,12 @@
 // D[i][j]: lane = 32 (i/4 % 2) + j, register = 4 (i / 8) + i % 4.  Here i = out-channel, j = pixel, k = input-channel parity:
 // A = 64 consecutive floats of the packed weights [ky][kx][ci][co] (ci = 2 cp + k), one coalesced 256-byte load per MFMA pair.
 #include <algorithm>
-#include "vsr_common.h"
+#include "sr_pixel_math.h"
 
 namespace {
 
 constexpr int NF = 32;
 typedef float f16v __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ float prelu(float v, float slope) { return v >= 0.0f ? v : v * slope; }
 
 #if VSR_X   // the per-tap build (reloads the pixel operand per tap; measurements / cross-check library only)
 // Conv2d(32,32,K,S,p2) + PReLU: out[co, iy, ix] = b + sum_{ky,kx,ci} in[ci, S iy - 2 + ky, S ix - 2 + kx] W[ky][kx][ci][co].
@@ -527,10 +525,8 @@ bool launch_head_f32_mfma(const float* x, const float* sub_scale3, const float* 
     if ((nmid & 31) != 0 || nmid > 256) return false;
     const size_t lds = (size_t)(nmid >> 5) * 30 * 64 * 4;
     static unsigned long long attr_devs = 0;
-    if (lds > 48 * 1024 && !vsr::device_marked(attr_devs)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_head_mfma), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) != hipSuccess) return false;
-        vsr::mark_device(attr_devs);
-    }
+    const auto kern = &k_head_mfma;
+    if (lds > 48 * 1024 && !vsr::raise_lds_limit(attr_devs, &kern, 1, 64 * 1024)) return false;
     const long long tiles = ((long long)h * w + 31) / 32;
     const unsigned gx = (unsigned)std::min<long long>((tiles + 3) / 4, 512);
     hipLaunchKernelGGL(k_head_mfma, dim3(gx, N), dim3(256), lds, stream, x, sub_scale3, sub_bias3, w_in, b_in, slope_in, nmid, w_feat, b_feat, slope_feat, out, h, w);

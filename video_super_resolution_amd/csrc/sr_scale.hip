@@ -10,20 +10,12 @@
 //                      product-sum is an explicit fma, so the decimated frame equals the full frame at (S i, S j) bit
 //                      for bit.
 // Both are HBM-bound passes: 64 B (fp16 HR pixel, read ~once through L2) -> 12 B, and 8 x 4 B x 3 -> 3 x 4 B per pixel.
-#include "vsr_common.h"
+#include "sr_pixel_math.h"
 
 namespace {
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 constexpr int NF = 32;
-
-__device__ __forceinline__ void bil(int dst, int n, float inv, int& i0, int& i1, float& l1) {
-    float src = ((float)dst + 0.5f) * inv - 0.5f;   // ATen upsample_bilinear2d, align_corners=False
-    if (src < 0.0f) src = 0.0f;
-    i0 = (int)src;
-    i1 = i0 + (i0 < n - 1 ? 1 : 0);
-    l1 = src - (float)i0;
-}
 
 // One thread per output pixel, lanes along x: the 3 x 3 x 64-byte neighbourhood of adjacent lanes overlaps (L1/L2
 // hits), weights [tap 9][ci 32][co 4 (3 live)] fp32 in LDS (broadcast reads).
@@ -75,12 +67,6 @@ k_convout_planes(const _Float16* __restrict__ hr, const float* __restrict__ wgt,
 }
 
 #pragma clang fp contract(off)
-__device__ __forceinline__ float lerp4(float v00, float v01, float v10, float v11, float lx, float ly) {
-    const float top = __builtin_fmaf(lx, v01, (1.0f - lx) * v00);
-    const float bot = __builtin_fmaf(lx, v11, (1.0f - lx) * v10);
-    return __builtin_fmaf(ly, bot, (1.0f - ly) * top);
-}
-
 template <int NPL, int HID>
 __global__ void __launch_bounds__(256)
 k_fc_planes_skip_s(const float* __restrict__ raw, const float* __restrict__ x, const float* __restrict__ tpar,

@@ -20,8 +20,6 @@ namespace {
 
 typedef float f2v __attribute__((ext_vector_type(2)));
 
-#define VSR_FENCE() __builtin_amdgcn_sched_barrier(0)
-
 constexpr int T3_ROWS = 16;                              // output-row window of the partial sums
 constexpr int T3_PLANE = 128 * 16;                       // one (row, dy) plane: 128 HR columns x 16 B
 constexpr int T3_PART = (T3_ROWS * 3 + 1) * T3_PLANE;    // + one dump plane for the idle lane group
@@ -749,12 +747,8 @@ int launch_tail3(const void* hid_nhwc, const void* blob, const void* conv3_frags
     constexpr int g_t3_diag = 0;
 #endif
     static unsigned long long attr_devs = 0;   // one bit per device: the attribute is per device
-    if (!vsr::device_marked(attr_devs)) {
-        for (kern_t k : kerns)
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, T3_LDS) != hipSuccess)
-                return vsr::fail(VSR_E_LAUNCH, "sr_tail3: cannot reserve %d bytes of LDS", T3_LDS);
-        vsr::mark_device(attr_devs);
-    }
+    if (!vsr::raise_lds_limit(attr_devs, kerns, (int)(sizeof(kerns) / sizeof(kerns[0])), T3_LDS))
+        return vsr::fail(VSR_E_LAUNCH, "sr_tail3: cannot reserve %d bytes of LDS", T3_LDS);
     if ((size_t)N * h * w * NF * 2 >= (1ull << 31)) return vsr::fail(VSR_E_UNSUPPORTED, "sr_tail3: input beyond 2 GiB");
     const unsigned strips = vsr::cdiv(w, TX), segs = vsr::cdiv(h, rows_per_seg);
     if (in2 && (size_t)h * w * NF * 4 >= (1ull << 31)) return vsr::fail(VSR_E_UNSUPPORTED, "sr_tail3: constant map beyond 2 GiB");

@@ -20,19 +20,15 @@
 //     lane), so the deconvolution reads what the separate launch would have written: bit-identical, and that launch (HBM-bound, a
 //     third of this kernel's time at LR 1080 x 1920) is gone.  The fold costs 48 registers (212: two workgroups per CU instead of three); a build
 //     with the 1x1's fragments in LDS held to 168 registers spilled and was slower (1.98 vs 1.72 ms; chain + plain tail: 1.85).
-#include "sr_f16_common.h"
+#include "sr_strip30.h"
 
 namespace {
 
-constexpr int T2_TX = 30;
-constexpr int T2_LRC = 34;
-constexpr int T2_LR_SLOT = T2_LRC * 64;
-constexpr int T2_LR_BYTES = 4 * T2_LR_SLOT;
 constexpr int T2_HR_ROW = 64 * 64;            // 64 HR columns x 32 channels fp16
 constexpr int T2_HR_ROWS = 6;                 // rows 2m-2 .. 2m+1 are read while 2m+2, 2m+3 may already be written
 constexpr int T2_HR_BYTES = T2_HR_ROWS * T2_HR_ROW;
 constexpr int T2_BIAS_BYTES = 256;
-constexpr int T2_LDS = T2_LR_BYTES + T2_HR_BYTES + T2_BIAS_BYTES;
+constexpr int T2_LDS = S30_LR_BYTES + T2_HR_BYTES + T2_BIAS_BYTES;
 
 constexpr int T2_BLOB_UP = 0;                             // [wave 4][tap 9][mt 2][lane 64][8] fp16 (as k_utd_s2)
 constexpr int T2_BLOB_CV = 4 * 18 * 1024;                 // [dy 3][dx 3][lane 64][8] fp16: rows 0-2 = conv_out's channels
@@ -42,25 +38,21 @@ constexpr int T2_BLOB_BYTES = T2_BLOB_CO + 4096 + 256;
 
 typedef unsigned int u4t __attribute__((ext_vector_type(4)));
 
-// byte offset of (HR column xr in 0..63, 16-byte chunk) inside a ring row: the deconvolution writes columns 2n + c from 16
-// lanes (128-byte stride), the 3x3 reads 16 consecutive columns: chunk XOR column bits 1-2 spreads both over the banks
-__device__ __forceinline__ int hr_off(int xr, int chunk) { return xr * 64 + ((chunk ^ ((xr >> 1) & 3)) << 4); }
-
 template <bool ALLMAX, bool FOLD>
 __global__ void __launch_bounds__(256, 2)
 k_tail_s2(const _Float16* __restrict__ in, const unsigned char* __restrict__ blob, float* __restrict__ raw, int h, int w,
           int rows_per_seg, int dec, const _Float16* __restrict__ in2, const float* __restrict__ cmap) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* const lrr = smem;
-    unsigned char* const hrr = smem + T2_LR_BYTES;
-    float* const bias_s = reinterpret_cast<float*>(smem + T2_LR_BYTES + T2_HR_BYTES);
+    unsigned char* const hrr = smem + S30_LR_BYTES;
+    float* const bias_s = reinterpret_cast<float*>(smem + S30_LR_BYTES + T2_HR_BYTES);
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, g = lane >> 4;
     const int r = wv >> 1, c = wv & 1;
-    const int x0 = blockIdx.x * T2_TX;
+    const int x0 = blockIdx.x * S30_TX;
     const int n = blockIdx.z;
     const int r0 = blockIdx.y * rows_per_seg;
     const int r1 = min(h, r0 + rows_per_seg);
@@ -93,7 +85,7 @@ k_tail_s2(const _Float16* __restrict__ in, const unsigned char* __restrict__ blo
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(FOLD ? cmap : fpar), 0, FOLD ? (int)((size_t)h * w * NF * 4) : 0, 0x00020000);
     // FOLD: loader lanes are MFMA operand lanes -- pixel 16 wv + l15 (waves 0-2: 48 >= 34 columns), channel chunk g
     const int lr_px = FOLD ? 16 * wv + l15 : tid >> 2, lr_ch = FOLD ? g : tid & 3, lr_col = x0 - 2 + lr_px;
-    const bool lr_loader = FOLD ? (wv < 3 && lr_px < T2_LRC) : tid < T2_LRC * 4;
+    const bool lr_loader = FOLD ? (wv < 3 && lr_px < S30_LRC) : tid < S30_LRC * 4;
     const bool lr_col_ok = lr_loader && lr_col >= 0 && lr_col < w;
     const int lr_st = lr_off(lr_px, lr_ch);
     // FOLD: where the two halves of a lane's activated tile pair (channels 4g..4g+3 and 16+4g..16+4g+3) lie in natural order
@@ -133,7 +125,7 @@ k_tail_s2(const _Float16* __restrict__ in, const unsigned char* __restrict__ blo
     // products: k_chain1x1's order -- and zero outside the image (the deconvolution's padding applies to the 1x1's OUTPUT).  The MFMAs
     // run on whole waves (wave-uniform guard), the stores on the loader lanes.
     auto store_lr = [&](const RawRow& v, int row) __attribute__((always_inline)) {
-        unsigned char* const slot = lrr + ((row + 4) & 3) * T2_LR_SLOT;
+        unsigned char* const slot = lrr + ((row + 4) & 3) * S30_LR_SLOT;
         if (!FOLD) {
             if (lr_loader) *reinterpret_cast<u4t*>(slot + lr_st) = v.a;
             return;
@@ -154,7 +146,7 @@ k_tail_s2(const _Float16* __restrict__ in, const unsigned char* __restrict__ blo
             }
         }
     };
-    auto lr_slot = [&](int row) __attribute__((always_inline)) { return ((row + 4) & 3) * T2_LR_SLOT; };
+    auto lr_slot = [&](int row) __attribute__((always_inline)) { return ((row + 4) & 3) * S30_LR_SLOT; };
     auto hr_slot = [&](int Y) __attribute__((always_inline)) { return ((Y + 12) % T2_HR_ROWS) * T2_HR_ROW; };   // (Y >= -12)
 
     store_lr(fetch_lr(r0 - 2), r0 - 2);
@@ -172,7 +164,7 @@ k_tail_s2(const _Float16* __restrict__ in, const unsigned char* __restrict__ blo
     const int xr = 16 * wv + l15;                 // ring column 0..63  <->  X = 2 (x0 - 1) + xr
     const int Xo = 2 * (x0 - 1) + xr;
     // live output columns of the strip: X in [2 x0, 2 x0 + 60) and inside the image
-    const bool xo_ok = (g == 0) && xr >= 2 && xr < 2 + 2 * T2_TX && Xo < 2 * w && (!dec || (Xo & 1) == 0);
+    const bool xo_ok = (g == 0) && xr >= 2 && xr < 2 + 2 * S30_TX && Xo < 2 * w && (!dec || (Xo & 1) == 0);
     const int Ho = dec ? h : 2 * h, Wo = dec ? w : 2 * w;
     const size_t plane = (size_t)Ho * Wo;
     float* const raw_n = raw + (size_t)n * 3 * plane;
@@ -260,8 +252,6 @@ k_tail_s2(const _Float16* __restrict__ in, const unsigned char* __restrict__ blo
 
 extern "C" {
 
-
-
 static int launch_tail_s2(const void* in, const void* in2, const float* cmap, const void* blob, float* raw, int N, int h, int w, int rows_per_seg,
                           int slopes_le_one, int decimate, vsr_stream_t stream, const char* what) {
     VSR_REQUIRE(in && blob && raw, "sr_tail_s2: null pointer");
@@ -270,7 +260,7 @@ static int launch_tail_s2(const void* in, const void* in2, const float* cmap, co
                     (reinterpret_cast<uintptr_t>(cmap) & 15) == 0, "sr_tail_s2: pointers must be 16-byte aligned");
     if ((size_t)N * h * w * NF * 2 >= (1ull << 32) - 16) return vsr::fail(VSR_E_UNSUPPORTED, "sr_tail_s2: input beyond 4 GiB");
     if (in2 && (size_t)h * w * NF * 4 >= (1ull << 32) - 16) return vsr::fail(VSR_E_UNSUPPORTED, "sr_tail_s2: constant map beyond 4 GiB");
-    const unsigned strips = vsr::cdiv(w, T2_TX), segs = vsr::cdiv(h, rows_per_seg);
+    const unsigned strips = vsr::cdiv(w, S30_TX), segs = vsr::cdiv(h, rows_per_seg);
     VSR_REQUIRE(segs <= 65535, "sr_tail_s2: too many row segments");
     typedef void (*kern_t)(const _Float16*, const unsigned char*, float*, int, int, int, int, const _Float16*, const float*);
     const kern_t k = in2 ? (slopes_le_one ? k_tail_s2<true, true> : k_tail_s2<false, true>) : (slopes_le_one ? k_tail_s2<true, false> : k_tail_s2<false, false>);

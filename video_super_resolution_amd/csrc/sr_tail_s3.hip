@@ -39,22 +39,19 @@
 // 230 / 237, no AGPRs, scratch 0 bytes per lane, occupancy 2 waves per SIMD.
 // Measured on an MI355X (tools/tail_s3_time.py): 8 x 720 x 1280 in 2.36 ms = 362 TFLOP/s at 115,904 FLOP per pixel and plane, against
 // 7.21 ms of the unfused launches; decimated 1.48 against 4.07 ms; FOLD 2.65 ms against 2.74 ms for chain launch + plain build.
-#include "sr_f16_common.h"
+#include "sr_s3_taps.h"
+#include "sr_strip30.h"
 
 #include "../../include/vsr_hip_s3t.h"
 
 namespace {
 
-constexpr int T3_TX = 30;                     // LR output columns per strip (32 deconv positions = 2 MFMA pixel tiles)
-constexpr int T3_LRC = 34;                    // staged LR columns x0-2 .. x0+31
-constexpr int T3_LR_SLOT = T3_LRC * 64;
-constexpr int T3_LR_BYTES = 4 * T3_LR_SLOT;   // rows m-1, m, m+1 + the row being loaded
 constexpr int T3_HR_COLS = 96;                // HR columns 3 (x0-1) .. 3 (x0+30) + 2
 constexpr int T3_HR_ROW = T3_HR_COLS * 64;    // x 32 channels fp16
 constexpr int T3_HR_ROWS = 8;                 // rows 3m-2 .. 3m+2 are read while 3m+3 .. 3m+5 may already be written
 constexpr int T3_HR_BYTES = T3_HR_ROWS * T3_HR_ROW;
 constexpr int T3_BIAS_BYTES = 256;
-constexpr int T3_LDS = T3_LR_BYTES + T3_HR_BYTES + T3_BIAS_BYTES;
+constexpr int T3_LDS = S30_LR_BYTES + T3_HR_BYTES + T3_BIAS_BYTES;
 constexpr int T3_CO_BYTES = 4096 + 128;       // FOLD: compress_out's four fragments + b_co[32] (read at use: the register budget)
 static_assert(T3_LDS + T3_CO_BYTES <= 64 * 1024, "dynamic LDS without the large-LDS attribute");
 static_assert(2 * (T3_LDS + T3_CO_BYTES) <= 160 * 1024, "two workgroups per CU");
@@ -67,33 +64,7 @@ constexpr int T3_BLOB_BYTES = T3_BLOB_F32 + 512;
 constexpr int T3_BLOB_CO = T3_BLOB_BYTES;                     // FOLD: [map 2][mt 2][lane 64][8] fp16 (natural channel order), then b_co[32], slope_co (64 floats)
 constexpr int T3_BLOB_FOLD_BYTES = T3_BLOB_CO + 4096 + 256;
 
-// ---- the waves' phase sets and the slot order of their tap fragments (as csrc/sr_utd_s3.hip; sr_pack.py:pack_tail_s3_blob restates these)
-constexpr int ph_cnt(int wv) { return wv == 3 ? 3 : 2; }
-constexpr int ph_r(int wv, int p) { return wv == 0 ? (p == 0 ? 1 : 0) : wv == 2 ? 1 : (p == 0 ? 0 : 2); }
-constexpr int ph_c(int wv, int p) { return wv == 0 ? (p == 0 ? 1 : 0) : wv == 1 ? 1 : wv == 2 ? (p == 0 ? 0 : 2) : (p == 1 ? 0 : 2); }
-// phase x (a row or a column phase) and offset d in {+1, 0, -1}: kernel index x + 2 - 3 d, live when it lies in 0 .. 6
-constexpr bool tap_ok(int x, int d) { return x + 2 - 3 * d >= 0 && x + 2 - 3 * d <= 6; }
-constexpr int tap_cnt(int x) { return x == 1 ? 3 : 2; }
-constexpr int tap_rank(int x, int d) { return 1 - d - (x == 0 ? 1 : 0); }   // position of d among the live offsets, +1 first
-constexpr int ph_base(int wv, int p) {
-    int s = 0;
-    for (int i = 0; i < p; ++i) s += tap_cnt(ph_r(wv, i)) * tap_cnt(ph_c(wv, i));
-    return s;
-}
-constexpr int tap_slot(int wv, int p, int dy, int dx) {
-    return ph_base(wv, p) + tap_rank(ph_r(wv, p), dy) * tap_cnt(ph_c(wv, p)) + tap_rank(ph_c(wv, p), dx);
-}
-static_assert(ph_base(0, 2) == 13 && ph_base(1, 2) == 12 && ph_base(2, 2) == 12 && ph_base(3, 3) == 12, "tap counts of the phase sets");
-
-template <int V>
-struct IntC { static constexpr int value = V; };
-
 typedef unsigned int u4t __attribute__((ext_vector_type(4)));
-
-// byte offset of (HR column xr in 0..95, 16-byte chunk) inside a ring row: chunk XOR column bits 1-2 (k_tail_s2's hr_off).  A
-// ds_write_b128 lane group is 8 lanes of one chunk at columns 3n + c (192-byte stride), a ds_read_b128 group 16 lanes of two
-// chunks at consecutive columns: the XOR puts either on distinct banks.
-__device__ __forceinline__ int hr_off(int xr, int chunk) { return xr * 64 + ((chunk ^ ((xr >> 1) & 3)) << 4); }
 
 template <bool ALLMAX, bool FOLD>
 __global__ void __launch_bounds__(256, 2)
@@ -101,14 +72,14 @@ k_tail_s3(const _Float16* __restrict__ in, const unsigned char* __restrict__ blo
           int rows_per_seg, int dec, const _Float16* __restrict__ in2, const float* __restrict__ cmap) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* const lrr = smem;
-    unsigned char* const hrr = smem + T3_LR_BYTES;
-    float* const bias_s = reinterpret_cast<float*>(smem + T3_LR_BYTES + T3_HR_BYTES);
+    unsigned char* const hrr = smem + S30_LR_BYTES;
+    float* const bias_s = reinterpret_cast<float*>(smem + S30_LR_BYTES + T3_HR_BYTES);
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, g = lane >> 4;
-    const int x0 = blockIdx.x * T3_TX;
+    const int x0 = blockIdx.x * S30_TX;
     const int n = blockIdx.z;
     const int r0 = blockIdx.y * rows_per_seg;
     const int r1 = min(h, r0 + rows_per_seg);
@@ -144,7 +115,7 @@ k_tail_s3(const _Float16* __restrict__ in, const unsigned char* __restrict__ blo
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(FOLD ? cmap : fpar), 0, FOLD ? (int)((size_t)h * w * NF * 4) : 0, 0x00020000);
     // FOLD: loader lanes are MFMA operand lanes -- pixel 16 wv + l15 (waves 0-2: 48 >= 34 columns), channel chunk g
     const int lr_px = FOLD ? 16 * wv + l15 : tid >> 2, lr_ch = FOLD ? g : tid & 3, lr_col = x0 - 2 + lr_px;
-    const bool lr_loader = FOLD ? (wv < 3 && lr_px < T3_LRC) : tid < T3_LRC * 4;
+    const bool lr_loader = FOLD ? (wv < 3 && lr_px < S30_LRC) : tid < S30_LRC * 4;
     const bool lr_col_ok = lr_loader && lr_col >= 0 && lr_col < w;
     const int lr_st = lr_off(lr_px, lr_ch);
     // FOLD: where the two halves of a lane's activated tile pair (channels 4g..4g+3 and 16+4g..16+4g+3) lie in natural order
@@ -182,7 +153,7 @@ k_tail_s3(const _Float16* __restrict__ in, const unsigned char* __restrict__ blo
     // products: k_chain1x1's order -- and zero outside the image (the deconvolution's padding applies to the 1x1's OUTPUT).  The MFMAs
     // run on whole waves (wave-uniform guard), the stores on the loader lanes.
     auto store_lr = [&](const RawRow& v, int row) __attribute__((always_inline)) {
-        unsigned char* const slot = lrr + ((row + 4) & 3) * T3_LR_SLOT;
+        unsigned char* const slot = lrr + ((row + 4) & 3) * S30_LR_SLOT;
         if (!FOLD) {
             if (lr_loader) *reinterpret_cast<u4t*>(slot + lr_st) = v.a;
             return;
@@ -203,7 +174,7 @@ k_tail_s3(const _Float16* __restrict__ in, const unsigned char* __restrict__ blo
             }
         }
     };
-    auto lr_slot = [&](int row) __attribute__((always_inline)) { return ((row + 4) & 3) * T3_LR_SLOT; };   // (row >= -4)
+    auto lr_slot = [&](int row) __attribute__((always_inline)) { return ((row + 4) & 3) * S30_LR_SLOT; };   // (row >= -4)
     auto hr_slot = [&](int Y) __attribute__((always_inline)) { return (Y & (T3_HR_ROWS - 1)) * T3_HR_ROW; };  // (two's complement: Y may be negative)
 
     // ---- prologue: LR rows r0-2, r0-1, r0 (the first triple, m = r0-1, reads them)
@@ -317,7 +288,7 @@ k_tail_s3(const _Float16* __restrict__ in, const unsigned char* __restrict__ blo
             // live output columns of the strip: X in [3 x0, 3 x0 + 90) and inside the image
             const int X = 3 * (x0 - 1) + xr;
             int Xd = X, Yd = Y;
-            bool ok = (g == 0) && xr >= 3 && xr < 3 + 3 * T3_TX && X < 3 * w;
+            bool ok = (g == 0) && xr >= 3 && xr < 3 + 3 * S30_TX && X < 3 * w;
             if (dec) {
                 Xd = (int)((unsigned)X / 3u);
                 Yd = m;
@@ -362,7 +333,7 @@ int launch_tail_s3(const void* in, const void* in2, const float* cmap, const voi
     if (in_bytes >= (1ull << 32) - 16) return vsr::fail(VSR_E_UNSUPPORTED, "%s: input beyond 4 GiB (split the planes)", what);
     if (in2 && cm_bytes >= (1ull << 32) - 16) return vsr::fail(VSR_E_UNSUPPORTED, "%s: constant map beyond 4 GiB", what);
     if (rows_per_seg == 0) rows_per_seg = h;   // one march per strip
-    const unsigned strips = vsr::cdiv(w, T3_TX), segs = vsr::cdiv(h, rows_per_seg);
+    const unsigned strips = vsr::cdiv(w, S30_TX), segs = vsr::cdiv(h, rows_per_seg);
     VSR_REQUIRE(segs <= 65535, "%s: too many row segments", what);
     const kern_t k = in2 ? (slopes_le_one ? k_tail_s3<true, true> : k_tail_s3<false, true>) : (slopes_le_one ? k_tail_s3<true, false> : k_tail_s3<false, false>);
     hipLaunchKernelGGL(k, dim3(strips, segs, N), dim3(256), T3_LDS + (in2 ? T3_CO_BYTES : 0), vsr::S(stream), (const _Float16*)in, (const unsigned char*)blob, raw, h, w,
@@ -381,7 +352,7 @@ size_t vsr_s3t_query(int what) {
     switch (what) {
         case VSR_S3T_Q_BLOB_BYTES: return T3_BLOB_BYTES;
         case VSR_S3T_Q_BLOB_FOLD_BYTES: return T3_BLOB_FOLD_BYTES;
-        case VSR_S3T_Q_STRIP_WIDTH: return T3_TX;
+        case VSR_S3T_Q_STRIP_WIDTH: return S30_TX;
         default: return 0;
     }
 }

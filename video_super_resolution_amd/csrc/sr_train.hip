@@ -14,7 +14,7 @@
 //   fusion MLP              k_fc_bwd         per-pixel hidden gradients; its parameter gradients are k_corr_dw / k_chan_sum
 // Thread = one output pixel with a block of 32 output channels in registers, lanes along x (coalesced activations,
 // wave-uniform weight addresses).  VALU kernels: the train step is not the path the benchmark times.
-#include "vsr_common.h"
+#include "sr_pixel_math.h"
 
 namespace {
 
@@ -213,13 +213,6 @@ __global__ void __launch_bounds__(kB) k_affine_ch(const float* __restrict__ a, c
     y[i] = v * scale[c] + (shift ? shift[c] : 0.0f);
 }
 
-__device__ __forceinline__ void bil(int dst, int n, float inv, int& i0, int& i1, float& l1) {   // ATen upsample_bilinear2d, align_corners=False
-    float src = ((float)dst + 0.5f) * inv - 0.5f;
-    if (src < 0.0f) src = 0.0f;
-    i0 = (int)src;
-    i1 = i0 + (i0 < n - 1 ? 1 : 0);
-    l1 = src - (float)i0;
-}
 // F.interpolate(x, scale_factor=S, mode='bilinear', align_corners=False) (SRProjectionModule.py:136), planes [NC,h,w] -> [NC,Sh,Sw]
 __global__ void __launch_bounds__(kB) k_bilinear_up(const float* __restrict__ x, float* __restrict__ y, int h, int w, int S) {
     const int X = blockIdx.x * kB + threadIdx.x, Y = blockIdx.y, nc = blockIdx.z;

@@ -28,8 +28,6 @@ __device__ unsigned long long* g_stamp3_ptr = nullptr;
 
 typedef float f2v __attribute__((ext_vector_type(2)));
 
-#define VSR_FENCE() __builtin_amdgcn_sched_barrier(0)
-
 constexpr int UTD3_LR_PAD = 2 * LR_SLOT + 16 * (256 - LR_COLS * 4);   // where the lanes without an LR piece store (slot offset + lane)
 constexpr int UTD3_LDS = PART_BYTES + LR_BYTES + UTD3_LR_PAD;   // no HR ring: the x4 map never leaves the registers
 
@@ -626,12 +624,8 @@ int launch_utd3(const void* in, const void* blob, void* out, int N, int h, int w
     constexpr int LDS_POST = UTD3_LDS + 2 * OROW + 2048 + 128;
     const int lds = out2 ? LDS_POST : UTD3_LDS;
     static unsigned long long attr_devs = 0;   // one bit per device: the attribute is per device
-    if (!vsr::device_marked(attr_devs)) {
-        for (int q = 0; q < NK; ++q)
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(kerns[q]), hipFuncAttributeMaxDynamicSharedMemorySize, q >= POST0 ? LDS_POST : UTD3_LDS) != hipSuccess)
-                return vsr::fail(VSR_E_LAUNCH, "sr_utd3: cannot reserve %d bytes of LDS", LDS_POST);
-        vsr::mark_device(attr_devs);
-    }
+    if (!vsr::raise_lds_limit(attr_devs, kerns, NK, [](int q) { return q >= POST0 ? LDS_POST : UTD3_LDS; }))
+        return vsr::fail(VSR_E_LAUNCH, "sr_utd3: cannot reserve %d bytes of LDS", LDS_POST);
     if ((size_t)N * h * w * NF * 2 >= (1ull << 31)) return vsr::fail(VSR_E_UNSUPPORTED, "sr_utd3: tensors beyond 2 GiB");
     const kern_t k = out2 ? kerns[POST0 + (slopes_le_one ? 1 : 0)] : (diag ? kerns[1 + diag] : kerns[slopes_le_one ? 1 : 0]);
     if (rows_per_seg < 0) {   // flat mode: -rows_per_seg workgroups share the N * strips * h rows evenly

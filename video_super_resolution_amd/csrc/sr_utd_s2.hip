@@ -18,18 +18,12 @@
 //     fixed order + bias + PReLU by all 256 threads.  One barrier per step.
 // Per wave and step: 36 + 4 + 36 MFMA against ~48 activation VALU + 24 DPP: a better MFMA : VALU ratio than the x4 kernel
 // (144 : 316), and 38 weight fragments (152 registers) instead of 64, so two workgroups share a CU.
-#include "sr_f16_common.h"
+#include "sr_strip30.h"
 
 namespace {
 
-constexpr int S2_TX = 30;                    // LR output columns per strip (32 deconv positions = 2 MFMA pixel tiles)
-constexpr int S2_LRC = 34;                   // staged LR columns x0-2 .. x0+31
-constexpr int S2_LR_SLOT = S2_LRC * 64;
-constexpr int S2_LR_BYTES = 4 * S2_LR_SLOT;  // rows m-1, m, m+1 + the row being loaded
-constexpr int S2_PART_W = 32 * PART_PX_PITCH;
-constexpr int S2_PART_BUF = 4 * S2_PART_W;
 constexpr int S2_BIAS_BYTES = 256 + 2048;    // b_up[32], b_dt[32] fp32 + the two 1x1 fragments (read at use: the kernel sits at the 256-register line)
-constexpr int S2_LDS = S2_LR_BYTES + 2 * S2_PART_BUF + S2_BIAS_BYTES;
+constexpr int S2_LDS = S30_LR_BYTES + 2 * S30_PART_BUF + S2_BIAS_BYTES;
 
 constexpr int S2_BLOB_UP = 0;                           // [wave 4][tap 9 = dy*3+dx][mt 2][lane 64][8] fp16
 constexpr int S2_BLOB_DN = 4 * 18 * 1024;               // [wave 4][kernel-row slot 3][shift 3][mt 2][lane 64][8] fp16
@@ -37,31 +31,7 @@ constexpr int S2_BLOB_DT = S2_BLOB_DN + 4 * 18 * 1024;  // [mt 2][lane 64][8] fp
 constexpr int S2_BLOB_F32 = S2_BLOB_DT + 2 * 1024;      // b_up[32] b_dt[32] b_dn[32] slope_up slope_dt slope_dn
 constexpr int S2_BLOB_POST = S2_BLOB_F32 + 512;         // POST: [mt 2][lane 64][8] fp16 (natural channel order), then b_post[32], slope_post (64 floats)
 constexpr int S2_BLOB_BYTES = S2_BLOB_POST + 2048 + 256;
-constexpr int S2_OROW = 2048;                           // POST: a finished output row as fp16 [32 px][64 B], 16-byte pieces swizzled (lr_off)
-constexpr int S2_LDS_POST = 2 * S2_OROW + 2048 + 256;   // two rows + the 1x1's fragments + bias
-
-typedef unsigned int u4v __attribute__((ext_vector_type(4)));
-
-// tile pair T (pixel tiles 0, 1: deconv positions n = 16 nt + lane&15) moved down SH lanes: B[nt] lane <- position n + SH
-template <int SH>
-__device__ __forceinline__ void shift_tiles(const h8 (&T)[2], h8 (&B)[2]) {
-    if (SH == 0) {
-        B[0] = T[0];
-        B[1] = T[1];
-        return;
-    }
-    const u4v v0 = __builtin_bit_cast(u4v, T[0]), v1 = __builtin_bit_cast(u4v, T[1]);
-    u4v b0, b1;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        // lanes 16-SH .. 15 of tile 0 take lanes 0 .. SH-1 of tile 1 (row_ror:16-SH), the others their right neighbour (row_shl:SH)
-        const unsigned ror = (unsigned)__builtin_amdgcn_mov_dpp((int)v1[q], 0x120 + (16 - SH), 0xF, 0xF, false);
-        b0[q] = (unsigned)__builtin_amdgcn_update_dpp((int)ror, (int)v0[q], 0x100 + SH, 0xF, 0xF, false);
-        b1[q] = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v1[q], 0x100 + SH, 0xF, 0xF, true);   // positions >= 32: zeros (discarded outputs)
-    }
-    B[0] = __builtin_bit_cast(h8, b0);
-    B[1] = __builtin_bit_cast(h8, b1);
-}
+constexpr int S2_LDS_POST = 2 * S30_OROW + 2048 + 256;   // two rows + the 1x1's fragments + bias
 
 // FLAT: one basic block per step -- pairs outside the image are computed and zeroed (two steps per march), the partial tiles
 // are always stored and the reduce of a row that is not output stores to an out-of-range buffer offset -- so that the
@@ -77,16 +47,16 @@ k_utd_s2(const _Float16* __restrict__ in, const unsigned char* __restrict__ blob
          int rows_per_seg, _Float16* __restrict__ out2) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* const lrr = smem;
-    unsigned char* const part = smem + S2_LR_BYTES;
+    unsigned char* const part = smem + S30_LR_BYTES;
     unsigned char* const orow = smem + S2_LDS;          // (POST only: the launch allocates S2_LDS + S2_LDS_POST)
-    unsigned char* const postw = orow + 2 * S2_OROW;
+    unsigned char* const postw = orow + 2 * S30_OROW;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, g = lane >> 4;
     const int r = wv >> 1, c = wv & 1;          // HR row parity / HR column parity this wave owns
-    const int x0 = blockIdx.x * S2_TX;
+    const int x0 = blockIdx.x * S30_TX;
     const int n = blockIdx.z;
     const int r0 = blockIdx.y * rows_per_seg;
     const int r1 = min(h, r0 + rows_per_seg);
@@ -107,9 +77,9 @@ k_utd_s2(const _Float16* __restrict__ in, const unsigned char* __restrict__ blob
             for (int mt = 0; mt < 2; ++mt)
                 Adn[k][s][mt] = *reinterpret_cast<const h8*>(blob + S2_BLOB_DN + ((((wv * 3 + k) * 3 + s) * 2 + mt) * 64 + lane) * 16);
     const float* fpar = reinterpret_cast<const float*>(blob + S2_BLOB_F32);
-    float* const bias_s = reinterpret_cast<float*>(smem + S2_LR_BYTES + 2 * S2_PART_BUF);
+    float* const bias_s = reinterpret_cast<float*>(smem + S30_LR_BYTES + 2 * S30_PART_BUF);
     if (tid < 64) bias_s[tid] = fpar[tid];   // (visible after the prologue's barrier)
-    unsigned char* const adt_s = smem + S2_LR_BYTES + 2 * S2_PART_BUF + 256;
+    unsigned char* const adt_s = smem + S30_LR_BYTES + 2 * S30_PART_BUF + 256;
     if (tid < 128) *reinterpret_cast<u4v*>(adt_s + tid * 16) = *reinterpret_cast<const u4v*>(blob + S2_BLOB_DT + tid * 16);
     auto adt = [&](int mt) __attribute__((always_inline)) { return *reinterpret_cast<const h8*>(adt_s + (mt * 64 + lane) * 16); };
     // this lane's accumulator rows are channels {4g..4g+3} of tile mt
@@ -131,7 +101,7 @@ k_utd_s2(const _Float16* __restrict__ in, const unsigned char* __restrict__ blob
     // ---- LR loader: 34 columns x 4 chunks of 16 bytes per row; out-of-image pieces read zeros (out-of-range buffer offset)
     const __amdgpu_buffer_rsrc_t in_rsrc =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(in), 0, (int)((size_t)gridDim.z * h * w * NF * 2), 0x00020000);
-    const bool lr_loader = tid < S2_LRC * 4;
+    const bool lr_loader = tid < S30_LRC * 4;
     const int lr_px = tid >> 2, lr_ch = tid & 3, lr_col = x0 - 2 + lr_px;
     const bool lr_col_ok = lr_loader && lr_col >= 0 && lr_col < w;
     const int lr_st = lr_off(lr_px, lr_ch);
@@ -139,22 +109,22 @@ k_utd_s2(const _Float16* __restrict__ in, const unsigned char* __restrict__ blob
         const unsigned off = (lr_col_ok && row >= 0 && row < h) ? (unsigned)(((((size_t)n * h + row) * w + lr_col) * NF + lr_ch * 8) * 2) : 0xFFFFFFFFu;
         return __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, off, 0, 0);
     };
-    auto lr_slot = [&](int row) __attribute__((always_inline)) { return ((row + 4) & 3) * S2_LR_SLOT; };   // (row >= -3)
+    auto lr_slot = [&](int row) __attribute__((always_inline)) { return ((row + 4) & 3) * S30_LR_SLOT; };   // (row >= -3)
 
     // ---- reduce role: output pixel tid>>3 (32 of them, 30 live), channels 4*(tid&7) .. +3
     const int rj = tid >> 3, rc4 = tid & 7;
     const f4 bdn = *reinterpret_cast<const f4*>(fpar + 64 + 4 * rc4);
-    const bool red_ok = (rj < S2_TX) && (x0 + rj < w);
+    const bool red_ok = (rj < S30_TX) && (x0 + rj < w);
     const __amdgpu_buffer_rsrc_t out_rsrc =
         __builtin_amdgcn_make_buffer_rsrc(out, 0, (int)((size_t)gridDim.z * h * w * NF * 2), 0x00020000);
     typedef unsigned int u2v __attribute__((ext_vector_type(2)));
     typedef float f2v __attribute__((ext_vector_type(2)));
-    const int part_wr = wv * S2_PART_W + l15 * PART_PX_PITCH + 4 * g * 4;   // + 64 mt + 16 nt PART_PX_PITCH
-    const int part_rd = rj * PART_PX_PITCH + rc4 * 16;                       // + k S2_PART_W
+    const int part_wr = wv * S30_PART_W + l15 * PART_PX_PITCH + 4 * g * 4;   // + 64 mt + 16 nt PART_PX_PITCH
+    const int part_rd = rj * PART_PX_PITCH + rc4 * 16;                       // + k S30_PART_W
     auto reduce_store = [&](int i, const unsigned char* pbase, bool ok) __attribute__((always_inline)) {
         f4 s = *reinterpret_cast<const f4*>(pbase + part_rd);
 #pragma unroll
-        for (int k = 1; k < 4; ++k) s += *reinterpret_cast<const f4*>(pbase + part_rd + k * S2_PART_W);
+        for (int k = 1; k < 4; ++k) s += *reinterpret_cast<const f4*>(pbase + part_rd + k * S30_PART_W);
         s += bdn;
         float v[4];
 #pragma unroll
@@ -163,15 +133,15 @@ k_utd_s2(const _Float16* __restrict__ in, const unsigned char* __restrict__ blob
         const unsigned hi = __builtin_bit_cast(unsigned, __builtin_convertvector(f2v{v[2], v[3]}, h2));
         const unsigned off = (red_ok && ok) ? (unsigned)(((((size_t)n * h + i) * w + x0 + rj) * NF + 4 * rc4) * 2) : 0xFFFFFFFFu;
         __builtin_amdgcn_raw_buffer_store_b64(u2v{lo, hi}, out_rsrc, off, 0, 0);
-        if (POST) *reinterpret_cast<u2v*>(orow + (i & 1) * S2_OROW + lr_off(rj, rc4 >> 1) + (rc4 & 1) * 8) = u2v{lo, hi};
+        if (POST) *reinterpret_cast<u2v*>(orow + (i & 1) * S30_OROW + lr_off(rj, rc4 >> 1) + (rc4 & 1) * 8) = u2v{lo, hi};
     };
     // POST: the 1x1 on finished row i (its fp16 values lie in orow[i & 1] since the barrier that followed its reduce): this wave's quadrant
     const __amdgpu_buffer_rsrc_t out2_rsrc =
         __builtin_amdgcn_make_buffer_rsrc(POST ? out2 : out, 0, (int)((size_t)gridDim.z * h * w * NF * 2), 0x00020000);
     const int pmt = wv >> 1, ppx = 16 * (wv & 1) + l15;
-    const bool post_px_ok = ppx < S2_TX && x0 + ppx < w;
+    const bool post_px_ok = ppx < S30_TX && x0 + ppx < w;
     auto post_row = [&](int i) __attribute__((always_inline)) {
-        const h8 b = *reinterpret_cast<const h8*>(orow + (i & 1) * S2_OROW + lr_off(ppx, g));
+        const h8 b = *reinterpret_cast<const h8*>(orow + (i & 1) * S30_OROW + lr_off(ppx, g));
         const h8 a = *reinterpret_cast<const h8*>(postw + (pmt * 64 + lane) * 16);
         const f4 e = mfma16(a, b, *reinterpret_cast<const f4*>(postw + 2048 + (16 * pmt + 4 * g) * 4));
         const h2 p0 = prelu_h2(__builtin_convertvector(f2v{e[0], e[1]}, h2), a_post2, post_max);
@@ -271,7 +241,7 @@ k_utd_s2(const _Float16* __restrict__ in, const unsigned char* __restrict__ blob
         }
         // ---- output row m-1 has all its kernel rows: partial tile of this wave -> LDS; rotate the accumulator sets
         const bool row_out = (m - 1 >= r0) && (m - 1 < r1);
-        unsigned char* const pbase = part + (m & 1) * S2_PART_BUF;
+        unsigned char* const pbase = part + (m & 1) * S30_PART_BUF;
         if (FLAT || row_out) {
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt)
@@ -313,7 +283,6 @@ int vsr_sr_utd_s2_variant(int v) {
 }
 #endif
 
-
 static int launch_utd_s2(const void* in, const void* blob, void* out, void* out2, int N, int h, int w, int rows_per_seg, int slopes_le_one,
                          vsr_stream_t stream, const char* what) {
     VSR_REQUIRE(in && blob && out, "sr_utd_s2: null pointer");
@@ -321,7 +290,7 @@ static int launch_utd_s2(const void* in, const void* blob, void* out, void* out2
     VSR_REQUIRE((reinterpret_cast<uintptr_t>(in) & 15) == 0 && (reinterpret_cast<uintptr_t>(blob) & 15) == 0 &&
                     (reinterpret_cast<uintptr_t>(out) & 15) == 0 && (reinterpret_cast<uintptr_t>(out2) & 15) == 0, "sr_utd_s2: pointers must be 16-byte aligned");
     if ((size_t)N * h * w * NF * 2 >= (1ull << 32) - 16) return vsr::fail(VSR_E_UNSUPPORTED, "sr_utd_s2: tensors beyond 4 GiB");
-    const unsigned strips = vsr::cdiv(w, S2_TX), segs = vsr::cdiv(h, rows_per_seg);
+    const unsigned strips = vsr::cdiv(w, S30_TX), segs = vsr::cdiv(h, rows_per_seg);
     VSR_REQUIRE(segs <= 65535, "sr_utd_s2: too many row segments");
     typedef void (*kern_t)(const _Float16*, const unsigned char*, _Float16*, int, int, int, _Float16*);
     kern_t k;
@@ -352,4 +321,4 @@ int vsr_sr_utd_s2_post_f16(const void* in, const void* blob, void* out, void* ou
 
 }  // extern "C"
 
-namespace vsr { size_t utd_s2_blob_bytes() { return S2_BLOB_BYTES; }  int utd_s2_strip_width() { return S2_TX; } }
+namespace vsr { size_t utd_s2_blob_bytes() { return S2_BLOB_BYTES; }  int utd_s2_strip_width() { return S30_TX; } }

@@ -12,107 +12,31 @@
 // three times): the kernel rows r, r + 2, r + 4 of a step go to rows m + 1, m, m - 1 in place, no accumulator is ever moved.
 // Channel order of the operands: ch(kb, kh, e) = 16 kb + 8 (e / 4) + 4 kh + e % 4 (sr_pack.py: pack_utd_s2_blob(layout=4)).
 #include <type_traits>
-#include "sr_f16_common.h"
+#include "sr_mfma32.h"
+#include "sr_strip30.h"
 
 namespace {
 
-typedef float f16v __attribute__((ext_vector_type(16)));
-typedef float f2w __attribute__((ext_vector_type(2)));
-typedef unsigned int u4x __attribute__((ext_vector_type(4)));
-typedef unsigned int u2x __attribute__((ext_vector_type(2)));
-
-constexpr int W2_TX = 30;                    // LR output columns per strip (32 deconv positions)
-constexpr int W2_LRC = 34;                   // staged LR columns x0-2 .. x0+31
-constexpr int W2_LR_SLOT = W2_LRC * 64;
-constexpr int W2_LR_BYTES = 4 * W2_LR_SLOT;  // rows m-1, m, m+1 + the row being loaded
-constexpr int W2_PART_W = 32 * PART_PX_PITCH;
-constexpr int W2_PART_BUF = 4 * W2_PART_W;
-constexpr int W2_LR_PAD = 16 * (256 - W2_LRC * 4);     // where the lanes without an LR piece store (no branch in the iteration)
-constexpr int W2_LDS = W2_LR_BYTES + W2_LR_PAD + 2 * W2_PART_BUF;
+constexpr int W2_LR_PAD = 16 * (256 - S30_LRC * 4);     // where the lanes without an LR piece store (no branch in the iteration)
+constexpr int W2_LDS = S30_LR_BYTES + W2_LR_PAD + 2 * S30_PART_BUF;
 constexpr int W2_BLOB_UP = 0;                           // [wave 4][tap 9 = dy*3+dx][K block 2][lane 64][8] fp16
 constexpr int W2_BLOB_DN = 4 * 18 * 1024;               // [wave 4][kernel-row slot 3][shift 3][K block 2][lane 64][8] fp16
 constexpr int W2_BLOB_DT = W2_BLOB_DN + 4 * 18 * 1024;  // [K block 2][lane 64][8] fp16
 constexpr int W2_BLOB_F32 = W2_BLOB_DT + 2 * 1024;      // b_up[32] b_dt[32] b_dn[32] slope_up slope_dt slope_dn
-
-__device__ __forceinline__ f16v mfma32w(h8 a, h8 b, f16v c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-
-struct Ob2 {
-    h2 d[8];
-};
-__device__ __forceinline__ h8 opk2(const Ob2& o, int kb) {
-    return h8{o.d[4 * kb][0], o.d[4 * kb][1], o.d[4 * kb + 1][0], o.d[4 * kb + 1][1], o.d[4 * kb + 2][0], o.d[4 * kb + 2][1], o.d[4 * kb + 3][0], o.d[4 * kb + 3][1]};
-}
-__device__ __forceinline__ Ob2 act16w(const f16v& a, h2 slope, bool use_max) {
-    Ob2 o;
-#pragma unroll
-    for (int d = 0; d < 8; ++d) {
-        const h2 c = __builtin_convertvector(f2w{a[2 * d], a[2 * d + 1]}, h2);
-        const h2 m = c * slope;
-        o.d[d] = use_max ? __builtin_elementwise_max(c, m) : __builtin_elementwise_min(c, m);
-    }
-    return o;
-}
-// The activation as 24 single instructions the iteration's schedule places one by one (sr_utd4.hip: "program positions" 0..23 -- convert 0,
-// convert 1, then per dword pair p = 0..2: multiply 2p, multiply 2p+1, convert 2p+2, max 2p, max 2p+1, convert 2p+3; then multiply 6, 7,
-// max 6, 7 -- whose chunks [0,2) [2,5) [5,8) .. [17,20) [20,24) end behind a convert: a packed-math instruction directly in front of an
-// MFMA costs an s_nop).  ZERO: the result is zeroed where `keep` is false (the conv's zero padding).
-struct ActW {
-    h2 c[8], m[8];
-};
-__device__ __forceinline__ constexpr int actw_chunk(int c) { return c <= 0 ? 0 : (c >= 8 ? 24 : 3 * c - 1); }
-template <bool ZERO>
-__device__ __forceinline__ void actw_st(int j, const f16v& a, ActW& t, Ob2& o, h2 slope, bool use_max, bool keep) {
-    int op, d;
-    if (j < 2) { op = 0; d = j; }
-    else if (j < 20) {
-        const int p = (j - 2) / 6, k = (j - 2) % 6;
-        op = (k == 2 || k == 5) ? 0 : (k < 2 ? 1 : 2);
-        d = k == 2 ? 2 * p + 2 : k == 5 ? 2 * p + 3 : ((k == 0 || k == 3) ? 2 * p : 2 * p + 1);
-    } else { op = j < 22 ? 1 : 2; d = 6 + (j & 1); }
-    if (op == 0) {
-        t.c[d] = __builtin_convertvector(f2w{a[2 * d], a[2 * d + 1]}, h2);
-        asm volatile("" : : "v"(t.c[d]));
-    } else if (op == 1) {
-        t.m[d] = t.c[d] * slope;
-        asm volatile("" : : "v"(t.m[d]));
-    } else {
-        h2 r = use_max ? __builtin_elementwise_max(t.c[d], t.m[d]) : __builtin_elementwise_min(t.c[d], t.m[d]);
-        if (ZERO) r = keep ? r : h2{(_Float16)0.0f, (_Float16)0.0f};
-        o.d[d] = r;
-        asm volatile("" : : "v"(o.d[d]));
-    }
-}
-__device__ __forceinline__ h2 shift1h(h2 v) {
-    return __builtin_bit_cast(h2, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x130, 0xF, 0xF, true));   // wave_shl:1
-}
-#define W2_FENCE() __builtin_amdgcn_sched_barrier(0)
-// byte offset of (pixel p, 16-byte piece) inside an LR row slot for THIS kernel's reads -- 32 consecutive pixels, one piece per half wave: the
-// piece XOR pixel bits 2-3 (lr_off's bits 1-2 serve 16-pixel x 4-piece reads and give this pattern two-way bank conflicts: 8 cycles per
-// ds_read_b128 instead of 4, tools/lds_bank_sim.py; PMC: 41 % of the LDS-active cycles were conflicts)
-__device__ __forceinline__ int lr_off32(int p, int chunk) { return p * 64 + ((chunk ^ ((p >> 2) & 3)) << 4); }
-
-// the tile moved down one position: lane n takes lane n + 1 (whole-wave shift; lane 31 / 63 -- position 32 -- take a neighbour's value,
-// read only by the discarded outputs 30, 31)
-__device__ __forceinline__ Ob2 shift1w(const Ob2& v) {
-    Ob2 o;
-#pragma unroll
-    for (int d = 0; d < 8; ++d) o.d[d] = __builtin_bit_cast(h2, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v.d[d]), 0x130, 0xF, 0xF, true));   // wave_shl:1
-    return o;
-}
 
 template <bool ALLMAX>
 __global__ void __launch_bounds__(256)
 k_utd_s2w(const _Float16* __restrict__ in, const unsigned char* __restrict__ blob, _Float16* __restrict__ out, int h, int w, int rows_per_seg) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* const lrr = smem;
-    unsigned char* const part = smem + W2_LR_BYTES + W2_LR_PAD;
+    unsigned char* const part = smem + S30_LR_BYTES + W2_LR_PAD;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n32 = lane & 31, kh = lane >> 5;
     const int c = wv & 1;                       // HR column parity this wave owns (its row parity wv >> 1 is in the packed weights)
-    const int x0 = blockIdx.x * W2_TX;
+    const int x0 = blockIdx.x * S30_TX;
     const int n = blockIdx.z;
     const int r0 = blockIdx.y * rows_per_seg;
     const int r1 = min(h, r0 + rows_per_seg);
@@ -158,15 +82,15 @@ k_utd_s2w(const _Float16* __restrict__ in, const unsigned char* __restrict__ blo
     // ---- LR loader: 34 columns x 4 chunks of 16 bytes per row; out-of-image pieces read zeros (out-of-range buffer offset)
     const __amdgpu_buffer_rsrc_t in_rsrc =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(in), 0, (int)((size_t)gridDim.z * h * w * NF * 2), 0x00020000);
-    const bool lr_loader = tid < W2_LRC * 4;
+    const bool lr_loader = tid < S30_LRC * 4;
     const int lr_px = tid >> 2, lr_ch = tid & 3, lr_col = x0 - 2 + lr_px;
     const bool lr_col_ok = lr_loader && lr_col >= 0 && lr_col < w;
     const int lr_st = lr_off32(lr_px, lr_ch);
-    auto fetch_lr = [&](int row) __attribute__((always_inline)) -> u4x {
+    auto fetch_lr = [&](int row) __attribute__((always_inline)) -> u4w {
         const unsigned off = (lr_col_ok && row >= 0 && row < h) ? (unsigned)(((((size_t)n * h + row) * w + lr_col) * NF + lr_ch * 8) * 2) : 0xFFFFFFFFu;
         return __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, off, 0, 0);
     };
-    auto lr_slot = [&](int row) __attribute__((always_inline)) { return ((row + 4) & 3) * W2_LR_SLOT; };   // (row >= -3)
+    auto lr_slot = [&](int row) __attribute__((always_inline)) { return ((row + 4) & 3) * S30_LR_SLOT; };   // (row >= -3)
     // LR operand of (dx, K block): staged column n + 2 - dx, 16-byte piece 2 kb + kh
     int lr_b[3][2];
 #pragma unroll
@@ -177,11 +101,11 @@ k_utd_s2w(const _Float16* __restrict__ in, const unsigned char* __restrict__ blo
     // ---- reduce role (as k_utd_s2): output pixel tid >> 3 (32 of them, 30 live), channels 4 (tid & 7) .. + 3
     const int rj = tid >> 3, rc4 = tid & 7;
     const f4 bdn = *reinterpret_cast<const f4*>(fpar + 64 + 4 * rc4);
-    const bool red_ok = (rj < W2_TX) && (x0 + rj < w);
+    const bool red_ok = (rj < S30_TX) && (x0 + rj < w);
     const __amdgpu_buffer_rsrc_t out_rsrc =
         __builtin_amdgcn_make_buffer_rsrc(out, 0, (int)((size_t)gridDim.z * h * w * NF * 2), 0x00020000);
-    const int part_wr = wv * W2_PART_W + n32 * PART_PX_PITCH + 16 * kh;   // + 32 q: channels 8 q + 4 kh .. + 3
-    const int part_rd = rj * PART_PX_PITCH + rc4 * 16;                    // + k W2_PART_W
+    const int part_wr = wv * S30_PART_W + n32 * PART_PX_PITCH + 16 * kh;   // + 32 q: channels 8 q + 4 kh .. + 3
+    const int part_rd = rj * PART_PX_PITCH + rc4 * 16;                    // + k S30_PART_W
     // (the same reduce as single instructions for the iteration's gaps: 0-3 p0 + p1, 4-7 + p2, 8-11 + p3, 12-15 + bias, 16-19 slope multiply,
     //  20-23 select, 24-25 converts, 26 store; the four partial tiles in pr[])
     struct RedW {
@@ -195,12 +119,12 @@ k_utd_s2w(const _Float16* __restrict__ in, const unsigned char* __restrict__ blo
         else if (j < 16) u.s[e] += bdn[e];
         else if (j < 20) u.t[e] = u.s[e] * a_dn;
         else if (j < 24) u.s[e] = u.s[e] >= 0.0f ? u.s[e] : u.t[e];
-        else if (j == 24) u.lo = __builtin_bit_cast(unsigned, __builtin_convertvector(f2w{u.s[0], u.s[1]}, h2));
-        else if (j == 25) u.hi = __builtin_bit_cast(unsigned, __builtin_convertvector(f2w{u.s[2], u.s[3]}, h2));
+        else if (j == 24) u.lo = __builtin_bit_cast(unsigned, __builtin_convertvector(f2v4{u.s[0], u.s[1]}, h2));
+        else if (j == 25) u.hi = __builtin_bit_cast(unsigned, __builtin_convertvector(f2v4{u.s[2], u.s[3]}, h2));
         else {
             unsigned ad = (unsigned)(((((size_t)n * h + i) * w + x0 + rj) * NF + 4 * rc4) * 2);
             asm volatile("" : "+v"(ad));
-            __builtin_amdgcn_raw_buffer_store_b64(u2x{u.lo, u.hi}, out_rsrc, (red_ok && ok) ? ad : 0xFFFFFFFFu, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b64(u2w{u.lo, u.hi}, out_rsrc, (red_ok && ok) ? ad : 0xFFFFFFFFu, 0, 0);
         }
         if (j < 16 || (j >= 20 && j < 24)) asm volatile("" : "+v"(u.s[e]));
         else if (j < 20) asm volatile("" : "+v"(u.t[e]));
@@ -210,23 +134,23 @@ k_utd_s2w(const _Float16* __restrict__ in, const unsigned char* __restrict__ blo
     auto reduce_store = [&](int i, const unsigned char* pbase, bool ok) __attribute__((always_inline)) {
         f4 s = *reinterpret_cast<const f4*>(pbase + part_rd);
 #pragma unroll
-        for (int k = 1; k < 4; ++k) s += *reinterpret_cast<const f4*>(pbase + part_rd + k * W2_PART_W);
+        for (int k = 1; k < 4; ++k) s += *reinterpret_cast<const f4*>(pbase + part_rd + k * S30_PART_W);
         s += bdn;
         float v[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = s[e] >= 0.0f ? s[e] : s[e] * a_dn;
-        const unsigned lo = __builtin_bit_cast(unsigned, __builtin_convertvector(f2w{v[0], v[1]}, h2));
-        const unsigned hi = __builtin_bit_cast(unsigned, __builtin_convertvector(f2w{v[2], v[3]}, h2));
+        const unsigned lo = __builtin_bit_cast(unsigned, __builtin_convertvector(f2v4{v[0], v[1]}, h2));
+        const unsigned hi = __builtin_bit_cast(unsigned, __builtin_convertvector(f2v4{v[2], v[3]}, h2));
         unsigned ad = (unsigned)(((((size_t)n * h + i) * w + x0 + rj) * NF + 4 * rc4) * 2);
         asm volatile("" : "+v"(ad));
-        __builtin_amdgcn_raw_buffer_store_b64(u2x{lo, hi}, out_rsrc, (red_ok && ok) ? ad : 0xFFFFFFFFu, 0, 0);   // (rows not output: dropped)
+        __builtin_amdgcn_raw_buffer_store_b64(u2w{lo, hi}, out_rsrc, (red_ok && ok) ? ad : 0xFFFFFFFFu, 0, 0);   // (rows not output: dropped)
     };
 
     // ---- prologue: LR rows r0-2, r0-1, r0 (the first pair, m = r0-1, reads them)
     if (lr_loader) {
-        *reinterpret_cast<u4x*>(lrr + lr_slot(r0 - 2) + lr_st) = fetch_lr(r0 - 2);
-        *reinterpret_cast<u4x*>(lrr + lr_slot(r0 - 1) + lr_st) = fetch_lr(r0 - 1);
-        *reinterpret_cast<u4x*>(lrr + lr_slot(r0) + lr_st) = fetch_lr(r0);
+        *reinterpret_cast<u4w*>(lrr + lr_slot(r0 - 2) + lr_st) = fetch_lr(r0 - 2);
+        *reinterpret_cast<u4w*>(lrr + lr_slot(r0 - 1) + lr_st) = fetch_lr(r0 - 1);
+        *reinterpret_cast<u4w*>(lrr + lr_slot(r0) + lr_st) = fetch_lr(r0);
     }
     __syncthreads();
 
@@ -263,7 +187,7 @@ k_utd_s2w(const _Float16* __restrict__ in, const unsigned char* __restrict__ blo
     auto iter = [&](int m, auto tauc, auto dodc) __attribute__((always_inline)) {
         constexpr int TAU = decltype(tauc)::value;
         constexpr bool DOD = decltype(dodc)::value;   // false: the drain iteration (no new pair)
-        u4x nxt;
+        u4w nxt;
         if (DOD) nxt = fetch_lr(m + 2);
         f16v& a0 = R[TAU % 3];
         f16v& a1 = R[(TAU + 1) % 3];
@@ -276,78 +200,78 @@ k_utd_s2w(const _Float16* __restrict__ in, const unsigned char* __restrict__ blo
             const int t = q >> 1, kb = q & 1, dy = t / 3, dx = t - 3 * dy;
             B[q] = *reinterpret_cast<const h8*>(lrr + slot_r[dy] + lr_b[dx][kb]);
         };
-        W2_FENCE();
-        Ob2 T0, T1, T2, u;
-        ActW tA, tB;
+        VSR_FENCE();
+        Ob T0, T1, T2, u;
+        ActT tA, tB;
         f16v d;
         f4 pr[4];
         RedW ru;
         const bool red_row_ok = m - 3 >= r0 && m - 3 < r1;
-        const unsigned char* const red_base = part + ((m - 1) & 1) * W2_PART_BUF;
+        const unsigned char* const red_base = part + ((m - 1) & 1) * S30_PART_BUF;
         // ---- lead-in: the first six LR operands requested; behind them the second activation of pair m-1 (needs no LDS: covers their latency)
         if (DOD) {
 #pragma unroll
             for (int q = 0; q < 6; ++q) breq(q);
         }
 #pragma unroll
-        for (int v = 0; v < 24; ++v) actw_st<true>(v, e_prev, tA, T0, a_dt2, dt_max, keep);
-        W2_FENCE();
+        for (int v = 0; v < 24; ++v) act_st<true>(v, e_prev, tA, T0, a_dt2, dt_max, keep);
+        VSR_FENCE();
         // ---- D(m): the two tile shifts in its gaps
 #pragma unroll
         for (int q = 0; q < 18; ++q) {
-            if (DOD) d = mfma32w(Aup[q >> 1][q & 1], B[q], q == 0 ? bup : d);
-            W2_FENCE();
+            if (DOD) d = mfma32(Aup[q >> 1][q & 1], B[q], q == 0 ? bup : d);
+            VSR_FENCE();
             if (DOD && q + 6 < 18) breq(q + 6);
-            if (q < 8) T1.d[q] = shift1h(T0.d[q]);
-            if (q >= 1 && q < 9) T2.d[q - 1] = shift1h(T1.d[q - 1]);
-            W2_FENCE();
+            if (q < 8) T1.d[q] = shift1d(T0.d[q]);
+            if (q >= 1 && q < 9) T2.d[q - 1] = shift1d(T1.d[q - 1]);
+            VSR_FENCE();
         }
         // ---- E(m-1): kernel rows r+4, r+2, r of pair m-1 -> rows m-2 (a0, finishes), m-1 (a1), m (a2, starts); kernel columns c + 2 s <-> tile moved s
 #pragma unroll
         for (int q = 0; q < 18; ++q) {
             const int s = q / 6, kb = (q / 3) & 1, k = q % 3;
-            const h8 b = opk2(s == 0 ? T0 : (s == 1 ? T1 : T2), kb);
-            if (k == 0) a0 = mfma32w(Adn[2][s][kb], b, a0);
-            else if (k == 1) a1 = mfma32w(Adn[1][s][kb], b, a1);
+            const h8 b = opk(s == 0 ? T0 : (s == 1 ? T1 : T2), kb);
+            if (k == 0) a0 = mfma32(Adn[2][s][kb], b, a0);
+            else if (k == 1) a1 = mfma32(Adn[1][s][kb], b, a1);
             else {
                 if (q == 2) {
                     f16v z;
 #pragma unroll
                     for (int r = 0; r < 16; ++r) z[r] = 0.0f;
-                    a2 = mfma32w(Adn[0][s][kb], b, z);
+                    a2 = mfma32(Adn[0][s][kb], b, z);
                 } else {
-                    a2 = mfma32w(Adn[0][s][kb], b, a2);
+                    a2 = mfma32(Adn[0][s][kb], b, a2);
                 }
             }
-            W2_FENCE();
+            VSR_FENCE();
             if (DOD && q >= 1 && q < 9) {   // (one gap behind D's last MFMA: its result is not there earlier)
 #pragma unroll
-                for (int v = actw_chunk(q - 1); v < actw_chunk(q); ++v) actw_st<false>(v, d, tB, u, a_up2, up_max, true);
+                for (int v = act_chunk_begin(q - 1); v < act_chunk_begin(q); ++v) act_st<false>(v, d, tB, u, a_up2, up_max, true);
             }
             // the reduce of row m-3: its four partial tiles requested in gap 5, 27 stages in gaps 9-17
             if (q == 5) {
 #pragma unroll
-                for (int k = 0; k < 4; ++k) pr[k] = *reinterpret_cast<const f4*>(red_base + part_rd + k * W2_PART_W);
+                for (int k = 0; k < 4; ++k) pr[k] = *reinterpret_cast<const f4*>(red_base + part_rd + k * S30_PART_W);
             }
             if (q >= 9) {
 #pragma unroll
                 for (int v = 3 * (q - 9); v < 3 * (q - 8); ++v) red_st(v, m - 3, red_row_ok, pr, ru);
             }
-            W2_FENCE();
+            VSR_FENCE();
         }
         // ---- C(m)
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
-            if (DOD) e_prev = mfma32w(adt[q], opk2(u, q), q == 0 ? bdt : e_prev);
-            W2_FENCE();
+            if (DOD) e_prev = mfma32(adt[q], opk(u, q), q == 0 ? bdt : e_prev);
+            VSR_FENCE();
             {   // output row m-2 has all its kernel rows: this wave's partial tile -> LDS (rows that are not output: harmless)
-                unsigned char* const pbase = part + (m & 1) * W2_PART_BUF;
+                unsigned char* const pbase = part + (m & 1) * S30_PART_BUF;
 #pragma unroll
                 for (int qq = 2 * q; qq < 2 * q + 2; ++qq)
                     *reinterpret_cast<f4*>(pbase + part_wr + 32 * qq) = f4{a0[4 * qq], a0[4 * qq + 1], a0[4 * qq + 2], a0[4 * qq + 3]};
             }
-            if (DOD && q == 1) *reinterpret_cast<u4x*>(lrr + (lr_loader ? lr_slot(m + 2) + lr_st : W2_LR_BYTES + 16 * (tid - W2_LRC * 4))) = nxt;   // (lanes without a piece: the pad)
-            W2_FENCE();
+            if (DOD && q == 1) *reinterpret_cast<u4w*>(lrr + (lr_loader ? lr_slot(m + 2) + lr_st : S30_LR_BYTES + 16 * (tid - S30_LRC * 4))) = nxt;   // (lanes without a piece: the pad)
+            VSR_FENCE();
         }
         __syncthreads();
     };
@@ -370,8 +294,8 @@ k_utd_s2w(const _Float16* __restrict__ in, const unsigned char* __restrict__ blo
     else if (kind == 1) iter(m, K1{}, NO{});
     else iter(m, K2{}, NO{});
     // rows r1-2 (tiles of iteration r1, buffer r1 & 1) and r1-1 (tiles of the drain iteration)
-    reduce_store(r1 - 2, part + (r1 & 1) * W2_PART_BUF, r1 - 2 >= r0);
-    reduce_store(r1 - 1, part + ((r1 + 1) & 1) * W2_PART_BUF, true);
+    reduce_store(r1 - 2, part + (r1 & 1) * S30_PART_BUF, r1 - 2 >= r0);
+    reduce_store(r1 - 1, part + ((r1 + 1) & 1) * S30_PART_BUF, true);
 }
 
 }  // namespace
@@ -383,7 +307,7 @@ extern "C" int vsr_sr_utd_s2w_f16(const void* in, const void* blob, void* out, i
     VSR_REQUIRE((reinterpret_cast<uintptr_t>(in) & 15) == 0 && (reinterpret_cast<uintptr_t>(blob) & 15) == 0 &&
                     (reinterpret_cast<uintptr_t>(out) & 15) == 0, "sr_utd_s2w: pointers must be 16-byte aligned");
     if ((size_t)N * h * w * NF * 2 >= (1ull << 32) - 16) return vsr::fail(VSR_E_UNSUPPORTED, "sr_utd_s2w: tensors beyond 4 GiB");
-    const unsigned strips = vsr::cdiv(w, W2_TX), segs = vsr::cdiv(h, rows_per_seg);
+    const unsigned strips = vsr::cdiv(w, S30_TX), segs = vsr::cdiv(h, rows_per_seg);
     VSR_REQUIRE(segs <= 65535, "sr_utd_s2w: too many row segments");
     typedef void (*kern_t)(const _Float16*, const unsigned char*, _Float16*, int, int, int);
     static const kern_t kerns[2] = {k_utd_s2w<false>, k_utd_s2w<true>};

@@ -49,20 +49,14 @@
 // Measured on an MI355X (tools/utd_s3_time.py): 8 x 720 x 1280 in 1.75 ms = 924 TFLOP/s at 219,136 FLOP per pixel and plane,
 // against 7.20 ms of the unfused launches.
 #pragma once
-#include "sr_f16_common.h"
+#include "sr_s3_taps.h"
+#include "sr_strip30.h"
 
 namespace {
 
-constexpr int S3_TX = 30;                    // LR output columns per strip (32 deconv positions = 2 MFMA pixel tiles)
-constexpr int S3_LRC = 34;                   // staged LR columns x0-2 .. x0+31
-constexpr int S3_LR_SLOT = S3_LRC * 64;
-constexpr int S3_LR_BYTES = 4 * S3_LR_SLOT;  // rows m-1, m, m+1 + the row being loaded
-constexpr int S3_PART_W = 32 * PART_PX_PITCH;
-constexpr int S3_PART_BUF = 4 * S3_PART_W;
 constexpr int S3_PAR_BYTES = 256 + 2048;     // b_up[32], b_dt[32] fp32 + the two 1x1 fragments
-constexpr int S3_LDS = S3_LR_BYTES + 2 * S3_PART_BUF + S3_PAR_BYTES;
-constexpr int S3_OROW = 2048;                           // POST: a finished output row as fp16 [32 px][64 B], 16-byte pieces swizzled (lr_off)
-constexpr int S3_LDS_POST = 2 * S3_OROW + 2048 + 256;   // two rows + the uptran 1x1's two fragments + its bias and slope
+constexpr int S3_LDS = S30_LR_BYTES + 2 * S30_PART_BUF + S3_PAR_BYTES;
+constexpr int S3_LDS_POST = 2 * S30_OROW + 2048 + 256;   // two rows + the uptran 1x1's two fragments + its bias and slope
 constexpr int S3_PRE_FRAGS = 10;                         // PRE: co (2 inputs x 2 tiles), ci (feat half, chained half), ut0: A fragments of 1 KiB
 constexpr int S3_LDS_PRE = S3_PRE_FRAGS * 1024 + 512;   // + b_co[32] b_ci[32] b_ut0[32] fp32 (the slopes are read from the blob)
 static_assert(S3_LDS + S3_LDS_POST + S3_LDS_PRE <= 64 * 1024, "dynamic LDS without the large-LDS attribute");
@@ -81,50 +75,6 @@ constexpr int S3_BLOB_POST_BYTES = S3_BLOB_POST + 2048 + 256;
 constexpr int S3_BLOB_PRE = S3_BLOB_POST_BYTES;
 constexpr int S3_BLOB_PRE_F32 = S3_BLOB_PRE + 12 * 1024;
 constexpr int S3_BLOB_PRE_BYTES = S3_BLOB_PRE_F32 + 512;
-
-// ---- the waves' phase sets and the slot order of their tap fragments (sr_pack.py:pack_utd_s3_blob restates these)
-constexpr int ph_cnt(int wv) { return wv == 3 ? 3 : 2; }
-constexpr int ph_r(int wv, int p) { return wv == 0 ? (p == 0 ? 1 : 0) : wv == 2 ? 1 : (p == 0 ? 0 : 2); }
-constexpr int ph_c(int wv, int p) { return wv == 0 ? (p == 0 ? 1 : 0) : wv == 1 ? 1 : wv == 2 ? (p == 0 ? 0 : 2) : (p == 1 ? 0 : 2); }
-// phase x (a row or a column phase) and offset d in {+1, 0, -1}: kernel index x + 2 - 3 d, live when it lies in 0 .. 6
-constexpr bool tap_ok(int x, int d) { return x + 2 - 3 * d >= 0 && x + 2 - 3 * d <= 6; }
-constexpr int tap_cnt(int x) { return x == 1 ? 3 : 2; }
-constexpr int tap_rank(int x, int d) { return 1 - d - (x == 0 ? 1 : 0); }   // position of d among the live offsets, +1 first
-constexpr int ph_base(int wv, int p) {
-    int s = 0;
-    for (int i = 0; i < p; ++i) s += tap_cnt(ph_r(wv, i)) * tap_cnt(ph_c(wv, i));
-    return s;
-}
-constexpr int tap_slot(int wv, int p, int dy, int dx) {
-    return ph_base(wv, p) + tap_rank(ph_r(wv, p), dy) * tap_cnt(ph_c(wv, p)) + tap_rank(ph_c(wv, p), dx);
-}
-static_assert(ph_base(0, 2) == 13 && ph_base(1, 2) == 12 && ph_base(2, 2) == 12 && ph_base(3, 3) == 12, "tap counts of the phase sets");
-
-template <int V>
-struct IntC { static constexpr int value = V; };
-
-typedef unsigned int u4v __attribute__((ext_vector_type(4)));
-
-// tile pair T (pixel tiles 0, 1: deconv positions n = 16 nt + lane&15) moved down SH lanes: B[nt] lane <- position n + SH
-template <int SH>
-__device__ __forceinline__ void shift_tiles(const h8 (&T)[2], h8 (&B)[2]) {
-    if (SH == 0) {
-        B[0] = T[0];
-        B[1] = T[1];
-        return;
-    }
-    const u4v v0 = __builtin_bit_cast(u4v, T[0]), v1 = __builtin_bit_cast(u4v, T[1]);
-    u4v b0, b1;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        // lanes 16-SH .. 15 of tile 0 take lanes 0 .. SH-1 of tile 1 (row_ror:16-SH), the others their right neighbour (row_shl:SH)
-        const unsigned ror = (unsigned)__builtin_amdgcn_mov_dpp((int)v1[q], 0x120 + (16 - SH), 0xF, 0xF, false);
-        b0[q] = (unsigned)__builtin_amdgcn_update_dpp((int)ror, (int)v0[q], 0x100 + SH, 0xF, 0xF, false);
-        b1[q] = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v1[q], 0x100 + SH, 0xF, 0xF, true);   // positions >= 32: zeros (discarded outputs)
-    }
-    B[0] = __builtin_bit_cast(h8, b0);
-    B[1] = __builtin_bit_cast(h8, b1);
-}
 
 // POST: the NEXT group's uptran slice (1x1 + PReLU on this stage's output) applied to every finished output row inside the launch and
 // written to `out2`, as k_utd_s2<.., POST> does (sr_utd_s2.hip).  The reduce leaves the row's fp16 values in LDS as well (orow, two
@@ -161,16 +111,16 @@ __device__ __forceinline__ void utd_s3_body(const _Float16* __restrict__ in, con
                                             const float* __restrict__ cmap = nullptr) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* const lrr = smem;
-    unsigned char* const part = smem + S3_LR_BYTES;
+    unsigned char* const part = smem + S30_LR_BYTES;
     [[maybe_unused]] unsigned char* const orow = smem + S3_LDS;   // (POST only: the launch allocates S3_LDS + S3_LDS_POST)
-    [[maybe_unused]] unsigned char* const postw = orow + 2 * S3_OROW;
+    [[maybe_unused]] unsigned char* const postw = orow + 2 * S30_OROW;
     [[maybe_unused]] unsigned char* const prew = smem + S3_LDS + (POST ? S3_LDS_POST : 0);   // (PRE only: + S3_LDS_PRE)
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, g = lane >> 4;
-    const int x0 = blockIdx.x * S3_TX;
+    const int x0 = blockIdx.x * S30_TX;
     const int n = blockIdx.z;
     const int r0 = blockIdx.y * rows_per_seg;
     const int r1 = min(h, r0 + rows_per_seg);
@@ -190,9 +140,9 @@ __device__ __forceinline__ void utd_s3_body(const _Float16* __restrict__ in, con
             asm volatile("" : "+a"(Adn[t][mt]));
         }
     const float* fpar = reinterpret_cast<const float*>(blob + S3_BLOB_F32);
-    float* const bias_s = reinterpret_cast<float*>(smem + S3_LR_BYTES + 2 * S3_PART_BUF);
+    float* const bias_s = reinterpret_cast<float*>(smem + S30_LR_BYTES + 2 * S30_PART_BUF);
     if (tid < 64) bias_s[tid] = fpar[tid];   // (visible after the prologue's barrier)
-    unsigned char* const adt_s = smem + S3_LR_BYTES + 2 * S3_PART_BUF + 256;
+    unsigned char* const adt_s = smem + S30_LR_BYTES + 2 * S30_PART_BUF + 256;
     if (tid < 128) *reinterpret_cast<u4v*>(adt_s + tid * 16) = *reinterpret_cast<const u4v*>(blob + S3_BLOB_DT + tid * 16);
     auto adt = [&](int mt) __attribute__((always_inline)) { return *reinterpret_cast<const h8*>(adt_s + (mt * 64 + lane) * 16); };
     // this lane's accumulator rows are channels {4g..4g+3} of tile mt
@@ -214,7 +164,7 @@ __device__ __forceinline__ void utd_s3_body(const _Float16* __restrict__ in, con
     // ---- LR loader: 34 columns x 4 chunks of 16 bytes per row; out-of-image pieces read zeros (out-of-range buffer offset)
     const __amdgpu_buffer_rsrc_t in_rsrc =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(in), 0, (int)((size_t)gridDim.z * h * w * NF * 2), 0x00020000);
-    const bool lr_loader = tid < S3_LRC * 4;
+    const bool lr_loader = tid < S30_LRC * 4;
     const int lr_px = tid >> 2, lr_ch = tid & 3, lr_col = x0 - 2 + lr_px;
     const bool lr_col_ok = lr_loader && lr_col >= 0 && lr_col < w;
     const int lr_st = lr_off(lr_px, lr_ch);
@@ -222,12 +172,12 @@ __device__ __forceinline__ void utd_s3_body(const _Float16* __restrict__ in, con
         const unsigned off = (lr_col_ok && row >= 0 && row < h) ? (unsigned)(((((size_t)n * h + row) * w + lr_col) * NF + lr_ch * 8) * 2) : 0xFFFFFFFFu;
         return __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, off, 0, 0);
     };
-    auto lr_slot = [&](int row) __attribute__((always_inline)) { return ((row + 4) & 3) * S3_LR_SLOT; };   // (row >= -3)
+    auto lr_slot = [&](int row) __attribute__((always_inline)) { return ((row + 4) & 3) * S30_LR_SLOT; };   // (row >= -3)
 
     // ---- PRE: the folded chain.  Waves 1-3, pixel tile wv - 1 of the staged columns; lane = MFMA operand lane (pixel l15, chunk g)
     [[maybe_unused]] const bool pre3 = PRE && pa != nullptr;
     [[maybe_unused]] const int pre_px = PRE ? 16 * (wv - 1) + l15 : 0, pre_col = PRE ? x0 - 2 + pre_px : 0;
-    [[maybe_unused]] const bool pre_lane = PRE && wv >= 1 && pre_px < S3_LRC;
+    [[maybe_unused]] const bool pre_lane = PRE && wv >= 1 && pre_px < S30_LRC;
     [[maybe_unused]] const bool pre_col_ok = pre_lane && pre_col >= 0 && pre_col < w;
     [[maybe_unused]] h2 a_co2 = {(_Float16)1.0f, (_Float16)1.0f}, a_ci2 = a_co2, a_ut2 = a_co2;
     [[maybe_unused]] bool co_max = true, ci_max = true, ut_max = true;
@@ -313,17 +263,17 @@ __device__ __forceinline__ void utd_s3_body(const _Float16* __restrict__ in, con
     // ---- reduce role: output pixel tid>>3 (32 of them, 30 live), channels 4*(tid&7) .. +3
     const int rj = tid >> 3, rc4 = tid & 7;
     const f4 bdn = *reinterpret_cast<const f4*>(fpar + 64 + 4 * rc4);
-    const bool red_ok = (rj < S3_TX) && (x0 + rj < w);
+    const bool red_ok = (rj < S30_TX) && (x0 + rj < w);
     const __amdgpu_buffer_rsrc_t out_rsrc =
         __builtin_amdgcn_make_buffer_rsrc(out, 0, (int)((size_t)gridDim.z * h * w * NF * 2), 0x00020000);
     typedef unsigned int u2v __attribute__((ext_vector_type(2)));
     typedef float f2v __attribute__((ext_vector_type(2)));
-    const int part_wr = wv * S3_PART_W + l15 * PART_PX_PITCH + 4 * g * 4;   // + 64 mt + 16 nt PART_PX_PITCH
-    const int part_rd = rj * PART_PX_PITCH + rc4 * 16;                       // + k S3_PART_W
+    const int part_wr = wv * S30_PART_W + l15 * PART_PX_PITCH + 4 * g * 4;   // + 64 mt + 16 nt PART_PX_PITCH
+    const int part_rd = rj * PART_PX_PITCH + rc4 * 16;                       // + k S30_PART_W
     auto reduce_store = [&](int i, const unsigned char* pbase) __attribute__((always_inline)) {
         f4 s = *reinterpret_cast<const f4*>(pbase + part_rd);
 #pragma unroll
-        for (int k = 1; k < 4; ++k) s += *reinterpret_cast<const f4*>(pbase + part_rd + k * S3_PART_W);
+        for (int k = 1; k < 4; ++k) s += *reinterpret_cast<const f4*>(pbase + part_rd + k * S30_PART_W);
         s += bdn;
         float v[4];
 #pragma unroll
@@ -332,16 +282,16 @@ __device__ __forceinline__ void utd_s3_body(const _Float16* __restrict__ in, con
         const unsigned hi = __builtin_bit_cast(unsigned, __builtin_convertvector(f2v{v[2], v[3]}, h2));
         const unsigned off = red_ok ? (unsigned)(((((size_t)n * h + i) * w + x0 + rj) * NF + 4 * rc4) * 2) : 0xFFFFFFFFu;
         __builtin_amdgcn_raw_buffer_store_b64(u2v{lo, hi}, out_rsrc, off, 0, 0);
-        if constexpr (POST) *reinterpret_cast<u2v*>(orow + (i & 1) * S3_OROW + lr_off(rj, rc4 >> 1) + (rc4 & 1) * 8) = u2v{lo, hi};
+        if constexpr (POST) *reinterpret_cast<u2v*>(orow + (i & 1) * S30_OROW + lr_off(rj, rc4 >> 1) + (rc4 & 1) * 8) = u2v{lo, hi};
     };
     // POST: the 1x1 on finished row i (its fp16 values lie in orow[i & 1] since the barrier that followed its reduce): this wave's quadrant;
     // dead pixels and rows outside [r0, r1) store to an out-of-range buffer offset (dropped)
     [[maybe_unused]] const __amdgpu_buffer_rsrc_t out2_rsrc =
         __builtin_amdgcn_make_buffer_rsrc(POST ? out2 : out, 0, (int)((size_t)gridDim.z * h * w * NF * 2), 0x00020000);
     [[maybe_unused]] const int pmt = wv >> 1, ppx = 16 * (wv & 1) + l15;
-    [[maybe_unused]] const bool post_px_ok = ppx < S3_TX && x0 + ppx < w;
+    [[maybe_unused]] const bool post_px_ok = ppx < S30_TX && x0 + ppx < w;
     [[maybe_unused]] auto post_row = [&](int i) __attribute__((always_inline)) {
-        const h8 b = *reinterpret_cast<const h8*>(orow + (i & 1) * S3_OROW + lr_off(ppx, g));
+        const h8 b = *reinterpret_cast<const h8*>(orow + (i & 1) * S30_OROW + lr_off(ppx, g));
         const h8 a = *reinterpret_cast<const h8*>(postw + (pmt * 64 + lane) * 16);
         const f4 e = mfma16(a, b, *reinterpret_cast<const f4*>(postw + 2048 + (16 * pmt + 4 * g) * 4));
         const h2 p0 = prelu_h2(__builtin_convertvector(f2v{e[0], e[1]}, h2), a_post2, post_max);
@@ -465,7 +415,7 @@ __device__ __forceinline__ void utd_s3_body(const _Float16* __restrict__ in, con
         }
         // ---- output row m-1 has all its kernel rows: partial tile of this wave -> LDS; rotate the accumulator sets
         const bool row_out = (m - 1 >= r0) && (m - 1 < r1);
-        unsigned char* const pbase = part + (m & 1) * S3_PART_BUF;
+        unsigned char* const pbase = part + (m & 1) * S30_PART_BUF;
         if (row_out) {
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt)
@@ -538,7 +488,7 @@ inline int s3_stage_args(const char* what, const S3Buf* bufs, int nbufs, int N, 
         VSR_REQUIRE((reinterpret_cast<uintptr_t>(bufs[i].p) & 15) == 0, "%s: pointers must be 16-byte aligned", what);
     if ((size_t)N * h * w * NF * 2 >= (1ull << 32) - 16) return vsr::fail(VSR_E_UNSUPPORTED, "%s: tensors beyond 4 GiB (split the planes)", what);
     if (rows_per_seg == 0) rows_per_seg = h;
-    const unsigned strips = vsr::cdiv(w, S3_TX), segs = vsr::cdiv(h, rows_per_seg);
+    const unsigned strips = vsr::cdiv(w, S30_TX), segs = vsr::cdiv(h, rows_per_seg);
     VSR_REQUIRE(segs <= 65535, "%s: too many row segments", what);
     for (int i = 0; i < nbufs; ++i)
         for (int j = i + 1; j < nbufs; ++j)

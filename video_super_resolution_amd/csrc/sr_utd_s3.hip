@@ -13,7 +13,7 @@ const char* vsr_s3_last_error(void) { return vsr::err_buf(); }
 size_t vsr_s3_query(int what) {
     switch (what) {
         case VSR_S3_Q_BLOB_BYTES: return S3_BLOB_BYTES;
-        case VSR_S3_Q_STRIP_WIDTH: return S3_TX;
+        case VSR_S3_Q_STRIP_WIDTH: return S30_TX;
         default: return 0;
     }
 }

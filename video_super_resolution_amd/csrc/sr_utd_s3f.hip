@@ -17,7 +17,7 @@ const char* vsr_s3f_last_error(void) { return vsr::err_buf(); }
 size_t vsr_s3f_query(int what) {
     switch (what) {
         case VSR_S3F_Q_BLOB_BYTES: return S3_BLOB_PRE_BYTES;
-        case VSR_S3F_Q_STRIP_WIDTH: return S3_TX;
+        case VSR_S3F_Q_STRIP_WIDTH: return S30_TX;
         default: return 0;
     }
 }

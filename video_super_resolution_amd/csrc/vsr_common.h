@@ -73,6 +73,27 @@ inline int current_device() {
 inline bool device_marked(unsigned long long mask) { return (mask >> current_device()) & 1ull; }
 inline void mark_device(unsigned long long& mask) { mask |= 1ull << current_device(); }
 
+// Raises the dynamic-LDS limit of kerns[0 .. n) to bytes_of(q) each, once per device: `mask` is the launcher's static, one bit per
+// device ordinal that is done.  Returns whether every attribute is set; the device is marked only then, so a refusal is asked again.
+template <class Kern, class BytesOf>
+inline bool raise_lds_limit(unsigned long long& mask, const Kern* kerns, int n, BytesOf bytes_of) {
+    if (device_marked(mask)) return true;
+    for (int q = 0; q < n; ++q)
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kerns[q]), hipFuncAttributeMaxDynamicSharedMemorySize, bytes_of(q)) != hipSuccess)
+            return false;
+    mark_device(mask);
+    return true;
+}
+template <class Kern>
+inline bool raise_lds_limit(unsigned long long& mask, const Kern* kerns, int n, int bytes) {
+    return raise_lds_limit(mask, kerns, n, [bytes](int) { return bytes; });
+}
+// One kernel, asked once per device whatever the answer: for the launchers that leave a refusal to the launch itself to report.
+template <class Kern>
+inline void raise_lds_limit_once(unsigned long long& mask, Kern kern, int bytes) {
+    if (!raise_lds_limit(mask, &kern, 1, bytes)) mark_device(mask);
+}
+
 }  // namespace vsr
 
 // Two libraries are built from these sources (Makefile): libvsr_hip.so -- the shipping kernels behind include/vsr_hip.h -- and
