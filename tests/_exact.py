@@ -138,7 +138,7 @@ def prelu_ref(v, slope):
 
 def leaky_tenth_f16(v):
     """LeakyReLU with the product's default slope 0.1, which is not dyadic: the reference restates the kernel's own operation
-    (csrc/conv_igemm.hip `fmaxf(x, 0) + nslope * fminf(x, 0)` / `t >= 0 ? t : t * p.slope`, csrc/conv_tile.hip:223, conv_patch.h:34;
+    (csrc/conv_igemm.hip `fmaxf(x, 0) + nslope * fminf(x, 0)` / `t >= 0 ? t : t * p.slope`, csrc/conv_tile.hip:187, conv_patch.h:36;
     csrc/flow_ops.hip k_corr_mfma `s > 0 ? s : 0.1f * s`): the exact sum (a float32 value by the budget), ONE float32 multiply by
     float32(0.1) on the negative side -- for a negative x the other summand is +0, so a fused multiply-add gives the same --
     and one round-to-nearest-even to fp16.  -> float64 tensor of fp16 values."""

@@ -6,6 +6,7 @@ import ctypes
 import json
 import os
 import re
+import subprocess
 
 import pytest
 
@@ -87,3 +88,80 @@ def test_plan_reports_the_entries_argument_errors():
         args[pos] = value
         assert lib.vsr_conv2d_plan(kind, *args, 1, ctypes.c_size_t(WS_BYTES)) == -1
         assert text in lib.vsr_last_error().decode()
+
+
+_KWALK_MAIN = r"""
+// The K-walk table of the gather / tile kernels (csrc/conv_kwalk.h, host part): the entry counts the kernels write and the launchers
+// reserve, and the largest index each kernel's loop reads, replayed from the loop bounds in the kernel text.
+#include <cassert>
+#include <cstdio>
+#include "conv_kwalk.h"
+using namespace vsrc;
+
+// k_conv_igemm_d<.., D>: en = tab[0], tab[1]; D - 1 requests before the loop, then whole groups of D steps, one request each; request
+// number j (1-based) ends with q = 2 j and reads tab[q], tab[q + 1].  n = nk - ks0 live steps (<= ks_per; <= 0: the loop does not run).
+static int last_read_gather(int n, int D) {
+    int requests = D - 1;
+    for (int ks = 0; ks < n; ks += D) requests += D;
+    return 2 * requests + 1;
+}
+// k_conv_igemm (first build): two requests before the loop, groups of two steps
+static int last_read_first(int n) {
+    int requests = 2;
+    for (int ks = 0; ks < n; ks += 2) requests += 2;
+    return 2 * requests + 1;
+}
+// k_conv_tile: stage(0) before the loop, stage(buf ^ 1) in every step but the last
+static int last_read_tile(int n) {
+    int requests = 1;
+    for (int ks = 0; ks < n; ++ks)
+        if (ks + 1 < n) ++requests;
+    return 2 * requests + 1;
+}
+
+int main() {
+    static_assert(kwalk_entries(7, kwalk_gather_lookahead(3)) == 2 * (7 + 5), "gather D = 3");
+    long checked = 0;
+    for (int ks_per = 1; ks_per <= 4096; ++ks_per) {
+        const int g3 = kwalk_entries(ks_per, kwalk_gather_lookahead(3)), g5 = kwalk_entries(ks_per, kwalk_gather_lookahead(5));
+        const int f = kwalk_entries(ks_per, KWALK_FIRST_LOOKAHEAD), t = kwalk_entries(ks_per, KWALK_TILE_LOOKAHEAD);
+        assert(g3 == 2 * (ks_per + 5));
+        assert(g5 == 2 * (ks_per + 9));
+        assert(f == 2 * (ks_per + 5));
+        assert(t == 2 * (ks_per + 2));
+        for (int n = 0; n <= ks_per; n += (ks_per > 64 && n > 8 && n + 9 < ks_per ? 7 : 1)) {   // every n near both ends, every 7th between
+            assert(last_read_gather(n, 3) < g3);
+            assert(last_read_gather(n, 5) < g5);
+            assert(last_read_first(n) < f);
+            assert(last_read_tile(n) < t);
+            ++checked;
+        }
+        // the gather bound is tight: a range that ends one step into a group of D reads the table's last entry
+        if (ks_per % 3 == 1) assert(last_read_gather(ks_per, 3) == g3 - 1);
+        if (ks_per % 5 == 1) assert(last_read_gather(ks_per, 5) == g5 - 1);
+        assert(last_read_tile(ks_per) == t - 3);
+    }
+    // the launchers' helper: pairs, steps and steps per split (conv: kh kw cin/32 pairs; stem: one per kernel row)
+    const KSteps a = k_steps(false, 3, 3, 256, 4), s = k_steps(true, 7, 7, 32, 1);
+    assert(a.nchunk == 8 && a.npair == 72 && a.nk_all == 36 && a.ks_per == 9);
+    assert(s.nchunk == 1 && s.npair == 7 && s.nk_all == 4 && s.ks_per == 4);
+    std::printf("kwalk ok %ld\n", checked);
+    return 0;
+}
+"""
+
+
+def test_kwalk_table_holds_every_entry_the_kernels_read(tmp_path):
+    """csrc/conv_kwalk.h's `kwalk_entries` (the count the gather / tile kernels write and their launchers reserve in LDS) gives the four
+    formulas the kernels had before the header existed, for 1..4096 steps per workgroup, and the largest index each kernel's loop reads
+    (its requests before the loop, its groups of D steps, the one-step read-ahead `tab[q + 1]`) stays below it.  A plain C++17 host
+    program, built with the address and undefined-behaviour sanitizers (host code only: nothing here is compiled for or run on a GPU)
+    and run on its own."""
+    csrc = os.path.join(os.path.dirname(os.path.abspath(L.__file__)), "csrc")
+    src, exe = tmp_path / "kwalk_table.cpp", tmp_path / "kwalk_table"
+    src.write_text(_KWALK_MAIN)
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")   # the compiler _lib.build() runs through csrc/Makefile
+    subprocess.run([hipcc, "-std=c++17", "-x", "c++", "-Wall", "-O1", "-g", "-Xarch_host", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", csrc,
+                    str(src), "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
+    assert out.startswith("kwalk ok ")

@@ -9,10 +9,12 @@
 //        and a pixel tile [128][32] (64-byte rows, chunk index XOR row bits 1-2:
 //        conflict-free ds_read_b128 for the 16x16x32 operand pattern, same scheme as the LR ring of k_utd)
 //   one barrier per K step: global loads of step s+1 are in flight while step s is multiplied
+// The K walk shared with conv_tile.hip (split-K range, table, pixel origin) is conv_kwalk.h; the patch kernels' vocabulary conv_patch.h.
 // Epilogue: + bias (fp32), none / ReLU / LeakyReLU, fp16 store into a channel slice [out_coff, out_coff+Cout) of a
 // tensor with out_ld channels (concatenations are written in place), with an output pixel stride/offset so the four
 // phases of a k4 s2 transposed convolution are four ordinary 2x2-tap launches.
 #include "conv_common.h"
+#include "conv_kwalk.h"
 #include "conv_patch.h"
 
 namespace {
@@ -23,6 +25,9 @@ using vsrc::f4;
 using vsrc::BM;
 using vsrc::ConvP;
 using vsrc::sw_off;
+using vsrc::u4;
+using vsrc::u2;
+using vsrc::dma16;
 using vsrc::patch_epilogue;
 using vsrc::patch_epilogue_act;
 using vsrc::patch_pixoff;
@@ -113,8 +118,6 @@ __global__ void __launch_bounds__(256) k_conv_igemm(const ConvP p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // operand ring [2][STAGE], then the K-walk table
     auto As = [&](int b, int hf) __attribute__((always_inline)) { return smem + b * STAGE + hf * (A_HALF + B_HALF); };
     auto Bs = [&](int b, int hf) __attribute__((always_inline)) { return smem + b * STAGE + hf * (A_HALF + B_HALF) + A_HALF; };
-    typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-    typedef unsigned int u2 __attribute__((ext_vector_type(2)));
     u4* const tab = reinterpret_cast<u4*>(smem + 2 * STAGE);
 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -125,36 +128,14 @@ __global__ void __launch_bounds__(256) k_conv_igemm(const ConvP p) {
     const int nchunk = STEM ? 1 : p.cin >> 5;
     const int npair = STEM ? p.kh : p.kh * p.kw * nchunk;     // (tap, chunk) pairs; STEM: one per kernel row
     const int nk_all = (npair + 1) >> 1;        // K steps of two pairs (the odd tail pair is zero-filled)
-    // split-K (small pixel counts with long K, e.g. the 1/32 and 1/64-resolution FlowNet layers): blockIdx.z owns a
-    // contiguous range of K steps and writes an fp32 partial tile; k_splitk_finish sums them in a fixed order
-    const int ph = p.nphase > 1 ? (int)(blockIdx.z & 3) : 0;
-    const int zsplit = p.nphase > 1 ? (int)(blockIdx.z >> 2) : (int)blockIdx.z;
-    const _Float16* const wpk = p.nphase > 1 ? p.wpk_ph[ph] : p.wpk;
-    const int pad_y = p.nphase > 1 ? p.pad_y_ph[ph] : p.pad_y, pad_x = p.nphase > 1 ? p.pad_x_ph[ph] : p.pad_x;
-    const int oy_off = p.nphase > 1 ? p.oy_off_ph[ph] : p.oy_off, ox_off = p.nphase > 1 ? p.ox_off_ph[ph] : p.ox_off;
-    const int ks_per = (nk_all + p.splits - 1) / p.splits;
-    const int ks0 = zsplit * ks_per;
-    const int nk = min(nk_all, ks0 + ks_per);
+    const vsrc::KRange kr = vsrc::k_range(p, blockIdx.z, nk_all);   // (split-K range and phase: conv_kwalk.h)
+    const int ph = kr.ph, zsplit = kr.zsplit, pad_y = kr.pad_y, pad_x = kr.pad_x, oy_off = kr.oy_off, ox_off = kr.ox_off;
+    const int ks_per = kr.ks_per, ks0 = kr.ks0, nk = kr.nk;
+    const _Float16* const wpk = kr.wpk;
 
-    const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<_Float16*>(wpk), 0, (int)((size_t)(STEM ? p.kh : p.kh * p.kw * nchunk) * p.cout_pad * 64), 0x00020000);
-    const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<_Float16*>(p.in), 0, (int)((size_t)p.N * p.H * p.W * p.in_ld * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t w_rsrc = vsrc::kwalk_w_rsrc(p, wpk, npair), in_rsrc = vsrc::kwalk_in_rsrc(p);
 
-    // ---- the K walk as a table in LDS (see k_conv_igemm_d)
-    {
-        const int pr0 = 2 * ks0, ntab = 2 * (ks_per + 5);
-        const unsigned wstep = (unsigned)p.cout_pad * 64u;
-        for (int i = tid; i < ntab; i += 256) {
-            const int pr = pr0 + i;
-            const bool live = pr < npair && pr < 2 * nk;
-            const int prc = live ? pr : 0;
-            const int tap = prc / nchunk, ch = prc - tap * nchunk;
-            const int ky = STEM ? tap : tap / p.kw, kx = STEM ? 0 : tap - ky * p.kw;
-            const unsigned delta = ((unsigned)(ky * p.W + kx) * (unsigned)p.in_ld + (unsigned)ch * 32u) * 2u;
-            tab[i] = live ? u4{delta, (unsigned)ky, (unsigned)kx, (unsigned)pr * wstep} : u4{0u, 1u << 29, 0u, 0x80000000u};
-        }
-    }
+    vsrc::build_kwalk<STEM>(p, tab, tid, ks0, nk, npair, nchunk, vsrc::kwalk_entries(ks_per, vsrc::KWALK_FIRST_LOOKAHEAD));   // (conv_kwalk.h)
 
     // ---- the two pixel pieces this thread stages per pair: piece q = tid + 256 r -> row q>>2, chunk piece q&3: four
     //      neighbouring lanes fetch the 64 contiguous bytes of one pixel's chunk (one L1 tag look-up per 64 bytes; in the MFMA
@@ -166,15 +147,8 @@ __global__ void __launch_bounds__(256) k_conv_igemm(const ConvP p) {
     bool xok0[2], xok1[2];
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
-        const long long m = m0 + brow[r];
-        const bool ok = m < M;
-        const unsigned mm = ok ? (unsigned)m : 0u, HoWo = (unsigned)(p.Ho * p.Wo);   // (M < 2^31: checked by the launchers; 32-bit divisions)
-        const int n = (int)(mm / HoWo);
-        const int rem = (int)(mm - (unsigned)n * HoWo);
-        const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
-        piy0[r] = ok ? oy * p.stride - pad_y : -(1 << 28);
-        pix0[r] = ox * p.stride_x - pad_x + (STEM ? 2 * bchunk : 0);
-        pbase[r] = (unsigned)(((((long long)n * p.H + piy0[r]) * p.W + pix0[r]) * p.in_ld + (STEM ? 0 : p.in_coff + bchunk * 8)) * 2);
+        const vsrc::PixOrigin o = vsrc::pixel_origin<STEM>(p, m0 + brow[r], M, pad_y, pad_x, bchunk);
+        piy0[r] = o.piy0; pix0[r] = o.pix0; pbase[r] = o.pbase;
         xok0[r] = (unsigned)pix0[r] < (unsigned)p.W;
         xok1[r] = (unsigned)(pix0[r] + 1) < (unsigned)p.W;
     }
@@ -182,7 +156,9 @@ __global__ void __launch_bounds__(256) k_conv_igemm(const ConvP p) {
 #pragma unroll
     for (int ap = 0; ap < AP; ++ap) wlane[ap] = tid + 256 * ap < A_PIECES ? (unsigned)(co0 * 64 + (tid + 256 * ap) * 16) : 0x40000000u;
 
-    // Global -> register staging, two K steps deep, every load unconditional (out-of-range offsets where a piece does not exist)
+    // Global -> register staging, two K steps deep, every load unconditional (out-of-range offsets where a piece does not exist).
+    // (gload / lstore / wlane repeat k_conv_igemm_d's text with one set index: as shared functions they changed the K step's
+    // register allocation in both kernels, LAB_NOTES.md "Trunk conv kernels".)
     u4 ra[2][2][AP], rb[2][2][2];
     __syncthreads();   // the table
     int q = 0;
@@ -289,8 +265,6 @@ __global__ void __launch_bounds__(256) k_conv_igemm_d(const ConvP p) {
     constexpr int AP = (A_PIECES + 255) / 256;  // ... per thread (2 for the 128-channel tile)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // weight ring [2][STAGE], then the K-walk table
     auto As = [&](int b, int hf) __attribute__((always_inline)) { return smem + b * STAGE + hf * A_HALF; };
-    typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-    typedef unsigned int u2 __attribute__((ext_vector_type(2)));
     u4* const tab = reinterpret_cast<u4*>(smem + 2 * STAGE);
 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -301,42 +275,14 @@ __global__ void __launch_bounds__(256) k_conv_igemm_d(const ConvP p) {
     const int nchunk = STEM ? 1 : p.cin >> 5;
     const int npair = STEM ? p.kh : p.kh * p.kw * nchunk;     // (tap, chunk) pairs; STEM: one per kernel row
     const int nk_all = (npair + 1) >> 1;        // K steps of two pairs (the odd tail pair is zero-filled)
-    // split-K (small pixel counts with long K, e.g. the 1/32 and 1/64-resolution FlowNet layers): blockIdx.z owns a
-    // contiguous range of K steps and writes an fp32 partial tile; k_splitk_finish sums them in a fixed order
-    const int ph = p.nphase > 1 ? (int)(blockIdx.z & 3) : 0;
-    const int zsplit = p.nphase > 1 ? (int)(blockIdx.z >> 2) : (int)blockIdx.z;
-    const _Float16* const wpk = p.nphase > 1 ? p.wpk_ph[ph] : p.wpk;
-    const int pad_y = p.nphase > 1 ? p.pad_y_ph[ph] : p.pad_y, pad_x = p.nphase > 1 ? p.pad_x_ph[ph] : p.pad_x;
-    const int oy_off = p.nphase > 1 ? p.oy_off_ph[ph] : p.oy_off, ox_off = p.nphase > 1 ? p.ox_off_ph[ph] : p.ox_off;
-    const int ks_per = (nk_all + p.splits - 1) / p.splits;
-    const int ks0 = zsplit * ks_per;
-    const int nk = min(nk_all, ks0 + ks_per);
+    const vsrc::KRange kr = vsrc::k_range(p, blockIdx.z, nk_all);   // (split-K range and phase: conv_kwalk.h)
+    const int ph = kr.ph, zsplit = kr.zsplit, pad_y = kr.pad_y, pad_x = kr.pad_x, oy_off = kr.oy_off, ox_off = kr.ox_off;
+    const int ks_per = kr.ks_per, ks0 = kr.ks0, nk = kr.nk;
+    const _Float16* const wpk = kr.wpk;
 
-    const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<_Float16*>(wpk), 0, (int)((size_t)(STEM ? p.kh : p.kh * p.kw * nchunk) * p.cout_pad * 64), 0x00020000);
-    const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<_Float16*>(p.in), 0, (int)((size_t)p.N * p.H * p.W * p.in_ld * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t w_rsrc = vsrc::kwalk_w_rsrc(p, wpk, npair), in_rsrc = vsrc::kwalk_in_rsrc(p);
 
-    // ---- the K walk as a table in LDS, built once per workgroup: entry i = pair 2 ks0 + i = (tap (ky, kx), chunk ch) as
-    //      {input byte offset of the tap and chunk relative to tap (0,0) chunk 0, ky, kx, byte offset of the pair's weight slab};
-    //      a pair past the kernel or past this split's range has ky = 2^29 (fails every row test) and a weight offset past the
-    //      slabs, so the loop requests it like any other and the hardware returns zeros.  The loop itself then holds no integer
-    //      division, no tap walk and no range logic: per piece one add and two unsigned compares on broadcast table values.
-    //      (Measured, tools/gather_steps.py: with the addresses computed per step from (pair / nchunk, tap / kw, ...) a K step of
-    //      an otherwise EMPTY loop -- loads and MFMAs switched off -- cost 500-620 cycles per workgroup, half of the step.)
-    {
-        const int pr0 = 2 * ks0, ntab = 2 * (ks_per + 2 * D - 1);   // range + rounding to D-step groups + D-1 steps of prefetch + one of table read-ahead
-        const unsigned wstep = (unsigned)p.cout_pad * 64u;
-        for (int i = tid; i < ntab; i += 256) {
-            const int pr = pr0 + i;
-            const bool live = pr < npair && pr < 2 * nk;
-            const int prc = live ? pr : 0;
-            const int tap = prc / nchunk, ch = prc - tap * nchunk;
-            const int ky = STEM ? tap : tap / p.kw, kx = STEM ? 0 : tap - ky * p.kw;
-            const unsigned delta = ((unsigned)(ky * p.W + kx) * (unsigned)p.in_ld + (unsigned)ch * 32u) * 2u;
-            tab[i] = live ? u4{delta, (unsigned)ky, (unsigned)kx, (unsigned)pr * wstep} : u4{0u, 1u << 29, 0u, 0x80000000u};
-        }
-    }
+    vsrc::build_kwalk<STEM>(p, tab, tid, ks0, nk, npair, nchunk, vsrc::kwalk_entries(ks_per, vsrc::kwalk_gather_lookahead(D)));   // (conv_kwalk.h)
 
     // ---- this lane's two pixels (tile r: row 32 wv + 16 r + l15 of the workgroup's 128) and its channel piece g: a 32-bit byte
     //      offset of (pixel, tap (0,0), chunk 0, piece g) -- wrapped modulo 2^32 where the padding makes it negative; adding the
@@ -347,15 +293,8 @@ __global__ void __launch_bounds__(256) k_conv_igemm_d(const ConvP p) {
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
         const int row = 32 * wv + 16 * r + l15;
-        const long long m = m0 + row;
-        const bool ok = m < M;
-        const unsigned mm = ok ? (unsigned)m : 0u, HoWo = (unsigned)(p.Ho * p.Wo);   // (M < 2^31: checked by the launchers; 32-bit divisions)
-        const int n = (int)(mm / HoWo);
-        const int rem = (int)(mm - (unsigned)n * HoWo);
-        const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
-        piy0[r] = ok ? oy * p.stride - pad_y : -(1 << 28);   // (a pixel past M fails every row test)
-        pix0[r] = ox * p.stride_x - pad_x + (STEM ? 2 * g : 0);
-        pbase[r] = (unsigned)(((((long long)n * p.H + piy0[r]) * p.W + pix0[r]) * p.in_ld + (STEM ? 0 : p.in_coff + g * 8)) * 2);
+        const vsrc::PixOrigin o = vsrc::pixel_origin<STEM>(p, m0 + row, M, pad_y, pad_x, g);
+        piy0[r] = o.piy0; pix0[r] = o.pix0; pbase[r] = o.pbase;
         xok0[r] = (unsigned)pix0[r] < (unsigned)p.W;
         xok1[r] = (unsigned)(pix0[r] + 1) < (unsigned)p.W;
     }
@@ -624,9 +563,6 @@ __global__ void __launch_bounds__(512) k_conv1x1_stream(const ConvP p) {
 //        [32 px][256 B] (same permutation), are read back lane-linearly and leave as 4 x 256 contiguous bytes per instruction.
 // A wave synchronises with nobody after the weights are staged (its slots are its own; LDS executes a wave's accesses in order).
 // Same products in the same order per accumulator as k_conv1x1_stream: bit-identical.
-__device__ __forceinline__ void c1t_dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned char* lds, unsigned off) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds, 16, off, 0, 0, 0);
-}
 #if VSR_X   // the transposing 1x1 build (measured: does not pay): cross-check library only
 constexpr int C1T_SLOT = 32 * 256;   // one wave's [32 px][256 B] image
 __global__ void __launch_bounds__(256) k_conv1x1_t(const ConvP p) {
@@ -646,7 +582,6 @@ __global__ void __launch_bounds__(256) k_conv1x1_t(const ConvP p) {
     const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<_Float16*>(p.in), 0, (int)((size_t)M * p.in_ld * 2), 0x00020000);
     const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, (int)((size_t)M * p.out_ld * 2), 0x00020000);
-    typedef unsigned int u4 __attribute__((ext_vector_type(4)));
     // DMA piece k (0..7) of a block: pixels 4 k .. 4 k + 3 of the wave's 32; lane L -> pixel 4 k + (L >> 4), slot L & 15
     const int dq = lane >> 4, ds = lane & 15;
     auto fetch = [&](long long blk, int slot) __attribute__((always_inline)) {
@@ -656,7 +591,7 @@ __global__ void __launch_bounds__(256) k_conv1x1_t(const ConvP p) {
             const int pl = 4 * k + dq;
             const long long m = m0 + pl;
             const unsigned off = m < M ? (unsigned)(((size_t)m * p.in_ld + p.in_coff) * 2 + ((ds ^ (pl & 15)) << 4)) : 0xFFFFFFFFu;
-            c1t_dma16(in_rsrc, slots + slot * C1T_SLOT + 1024 * k, off);
+            dma16(in_rsrc, slots + slot * C1T_SLOT + 1024 * k, off);
         }
     };
     const float nslope = p.act == 1 ? 0.0f : (p.act == 2 ? p.slope : 1.0f);
@@ -772,12 +707,9 @@ __global__ void __launch_bounds__(256) k_conv_patch(const ConvP p) {
     unsigned char* const patch = psm;                      // [PH][PW] pixels of 64 B (chunk XOR pixel-column bits 1-2)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int l15 = lane & 15, g = lane >> 4;
-    const int tiles_x = (p.Wo + PT_W - 1) / PT_W;
-    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
-    const int n = blockIdx.y;
+    const vsrc::PatchTile t0 = vsrc::patch_tile<PT_H, PT_W>(p, p.Wo);
+    const int n = t0.n, oy0 = t0.oy0, ox0 = t0.ox0, iy0 = t0.iy0, ix0 = t0.ix0;
     const int co0 = blockIdx.z * 16 * MT;
-    const int oy0 = ty * PT_H, ox0 = tx * PT_W;
-    const int iy0 = oy0 - p.pad_y, ix0 = ox0 - p.pad_x;
     const int nchunk = p.cin >> 5;
 
     f4 acc[MT][4];
@@ -835,52 +767,41 @@ __global__ void __launch_bounds__(256) k_conv_patch_rows(const ConvP p) {
     unsigned char* const patch = psm;                      // [PH][PW] pixels of 64 B (chunk XOR pixel-column bits 1-2)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int l15 = lane & 15, g = lane >> 4;
-    const int tiles_x = (p.Wo + PT_W - 1) / PT_W;
-    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
-    const int n = blockIdx.y;
-    const int oy0 = ty * PT_H, ox0 = tx * PT_W;
-    const int iy0 = oy0 - p.pad_y, ix0 = ox0 - p.pad_x;
+    const vsrc::PatchTile t0 = vsrc::patch_tile<PT_H, PT_W>(p, p.Wo);
+    const int n = t0.n, oy0 = t0.oy0, ox0 = t0.ox0, iy0 = t0.iy0, ix0 = t0.ix0;
     const int nchunk = p.cin >> 5;
     const int ry0 = 4 * (wv >> 1), cx0 = 16 * (wv & 1);    // this wave's 4 x 16 pixels of the 8 x 32 tile
 
-    f4 acc[4];
+    f4 acc[4][1];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) acc[r] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int r = 0; r < 4; ++r) acc[r][0] = f4{0.0f, 0.0f, 0.0f, 0.0f};
     auto wfrag = [&](int ky, int kx, int ch) __attribute__((always_inline)) {
         return *reinterpret_cast<const h8*>(p.wpk + ((size_t)((ky * p.kw + kx) * nchunk + ch) * 16 + l15) * 32 + 8 * g);
     };
-    auto column = [&](int kx, const h8 (&af)[KH]) __attribute__((always_inline)) {
+    auto column = [&](int kx, const h8 (&af)[KH][1]) __attribute__((always_inline)) {
         const int px = cx0 + l15 + kx;
         const unsigned char* src = patch + (ry0 * PW + px) * 64 + ((g ^ ((px >> 1) & 3)) << 4);
-#pragma unroll
-        for (int pr = 0; pr < KH + 3; ++pr) {
-            const h8 bf = *reinterpret_cast<const h8*>(src + pr * PW * 64);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int ky = pr - r;
-                if (ky >= 0 && ky < KH) acc[r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[ky], bf, acc[r], 0, 0, 0);
-            }
-        }
+        vsrc::walk_tap_column<KH, 4, 1>(src, PW, af, acc, [](int) {});
     };
     for (int ch = 0; ch < nchunk; ++ch) {
         __syncthreads();
         stage_patch(p, patch, n, ch, iy0, ix0, PH, PW, tid);
-        h8 a0[KH], a1[KH];
+        h8 a0[KH][1], a1[KH][1];
 #pragma unroll
-        for (int ky = 0; ky < KH; ++ky) a0[ky] = wfrag(ky, 0, ch);
+        for (int ky = 0; ky < KH; ++ky) a0[ky][0] = wfrag(ky, 0, ch);
         __syncthreads();
         for (int kx = 0; kx < p.kw; kx += 2) {   // two tap columns per trip: the weight sets swap roles without copies
             const int k1 = kx + 1 < p.kw ? kx + 1 : kx, k2 = kx + 2 < p.kw ? kx + 2 : kx;
 #pragma unroll
-            for (int ky = 0; ky < KH; ++ky) a1[ky] = wfrag(ky, k1, ch);
+            for (int ky = 0; ky < KH; ++ky) a1[ky][0] = wfrag(ky, k1, ch);
             column(kx, a0);
 #pragma unroll
-            for (int ky = 0; ky < KH; ++ky) a0[ky] = wfrag(ky, k2, ch);
+            for (int ky = 0; ky < KH; ++ky) a0[ky][0] = wfrag(ky, k2, ch);
             if (kx + 1 < p.kw) column(kx + 1, a1);
         }
     }
     __syncthreads();
-    patch_epilogue<1, 4>(p, psm + wv * (4 * 16 * 32), 0, lane, [&](int r, int) { return acc[r]; },
+    patch_epilogue<1, 4>(p, psm + wv * (4 * 16 * 32), 0, lane, [&](int r, int) { return acc[r][0]; },
                          [&](int r, int li) { return patch_pixoff(p, n, oy0 + ry0 + r, ox0 + cx0 + li); });
 }
 
@@ -897,11 +818,9 @@ __global__ void __launch_bounds__(256) k_deconv4s2_patch(const ConvP p) {
     unsigned char* const patch = psm;                      // [PH][PW] pixels of 64 B (chunk XOR pixel-column bits 1-2)
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, g = lane >> 4;
-    const int tiles_x = (p.W + PT_W - 1) / PT_W;
-    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
-    const int n = blockIdx.y;
+    const vsrc::PatchTile t0 = vsrc::patch_tile<PT_H, PT_W>(p, p.W);   // (tiles of the INPUT map)
+    const int n = t0.n, oy0 = t0.oy0, ox0 = t0.ox0;
     const int co0 = blockIdx.z * 16;
-    const int oy0 = ty * PT_H, ox0 = tx * PT_W;
     const int nchunk = p.cin >> 5;
     const int ry0 = 4 * (wv >> 1), cx0 = 16 * (wv & 1);    // this wave's 4 x 16 input pixels of the 8 x 32 tile
 
@@ -947,13 +866,11 @@ __global__ void __launch_bounds__(256) k_deconv4s2_patch(const ConvP p) {
         }
     }
     __syncthreads();   // every wave is done with the patch: its memory carries the output tiles now
-    const int rows_ok = p.H - (oy0 + ry0), cols_ok = p.W - (ox0 + cx0);
 #pragma unroll
-    for (int ph = 0; ph < 4; ++ph) {
-        const long long wbase = (((long long)n * p.outH + 2 * (oy0 + ry0) + (ph >> 1)) * p.outW + 2 * (ox0 + cx0) + (ph & 1)) * p.out_ld;
-        const int rstride = 2 * p.outW * p.out_ld, cstride = 2 * p.out_ld;
+    for (int ph = 0; ph < 4; ++ph) {   // phase (py, px) = (ph >> 1, ph & 1): output pixel (2 y + py, 2 x + px)
+        const vsrc::WaveOut wo = vsrc::wave_out(p.outH, p.outW, p.out_ld, n, oy0 + ry0, ox0 + cx0, 2, ph >> 1, 2, ph & 1, p.H, p.W);
         patch_epilogue<1, 4>(p, psm + wv * (4 * 16 * 32), co0, lane, [&](int r, int) { return acc[ph][r]; },
-                             [&](int r, int li) { return r < rows_ok && li < cols_ok ? wbase + r * rstride + li * cstride : -1ll; });
+                             [&](int r, int li) { return r < wo.rows_ok && li < wo.cols_ok ? wo.wbase + r * wo.rstride + li * wo.cstride : -1ll; });
     }
 }
 
@@ -974,12 +891,9 @@ __global__ void __launch_bounds__(256) k_conv_patch_r8(const ConvP p) {
     unsigned char* const patch = psm;                      // [PH][PW] pixels of 64 B (chunk XOR pixel-column bits 1-2)
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);   // (wave-uniform: scalar arithmetic downstream)
     const int l15 = lane & 15, g = lane >> 4;
-    const int tiles_x = (p.Wo + P8_W - 1) / P8_W;
-    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
-    const int n = blockIdx.y;
+    const vsrc::PatchTile t0 = vsrc::patch_tile<P8_H, P8_W>(p, p.Wo);
+    const int n = t0.n, oy0 = t0.oy0, ox0 = t0.ox0, iy0 = t0.iy0, ix0 = t0.ix0;
     const int co0 = blockIdx.z * 16 * MT;
-    const int oy0 = ty * P8_H, ox0 = tx * P8_W;
-    const int iy0 = oy0 - p.pad_y, ix0 = ox0 - p.pad_x;
     const int nchunk = p.cin >> 5;
     const int ry0 = P8_R * (wv >> 1), cx0 = 16 * (wv & 1);
 
@@ -997,7 +911,7 @@ __global__ void __launch_bounds__(256) k_conv_patch_r8(const ConvP p) {
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) A[ky][mt] = wfrag(ky, 0, 0, mt);
     // pieces of the patch this thread stages: descriptors kept across chunks where the layer has several and the kernel is square
-    constexpr int NPC = ((P8_H + KH - 1) * (P8_W + KH - 1) * 4 + 255) / 256;
+    constexpr int NPC = vsrc::P8Geom<KH, MT>::NPC;
     constexpr bool CACHE = KH <= 7;
     unsigned poff[CACHE ? NPC : 1];
     int pdst[CACHE ? NPC : 1];
@@ -1033,12 +947,9 @@ __global__ void __launch_bounds__(256) k_conv_patch_r8(const ConvP p) {
         }
     }
     __syncthreads();
-    // output offsets: the wave's first pixel once (64-bit, scalar), then row / column strides
-    const long long wbase = (((long long)n * p.outH + (oy0 + ry0) * p.oy_mul + p.oy_off) * p.outW + (ox0 + cx0) * p.ox_mul + p.ox_off) * p.out_ld;
-    const int rstride = p.oy_mul * p.outW * p.out_ld, cstride = p.ox_mul * p.out_ld;
-    const int rows_ok = p.Ho - (oy0 + ry0), cols_ok = p.Wo - (ox0 + cx0);
+    const vsrc::WaveOut wo = vsrc::wave_out(p, n, oy0 + ry0, ox0 + cx0);
     patch_epilogue<MT, P8_R>(p, psm + wv * (P8_R * 16 * 32 * MT), co0, lane, [&](int r, int mt) { return acc[r][mt]; },
-                             [&](int r, int li) { return r < rows_ok && li < cols_ok ? wbase + r * rstride + li * cstride : -1ll; });
+                             [&](int r, int li) { return r < wo.rows_ok && li < wo.cols_ok ? wo.wbase + r * wo.rstride + li * wo.cstride : -1ll; });
 }
 
 // k_conv_patch_r8 with the chunk's WEIGHT BLOCK staged in LDS once per workgroup.  In k_conv_patch_r8 every wave fetches every
@@ -1050,27 +961,22 @@ __global__ void __launch_bounds__(256) k_conv_patch_r8(const ConvP p) {
 // (tap, chunk) is contiguous), the four waves read their column's fragments from there, and with no weight traffic per wave a
 // workgroup can own 64 out-channels (MT = 4: the patch is staged once for twice the MFMAs; round 2's MT = 4 build kept 12
 // fragments in registers per column, needed 266, and lost).  Same loop nest per accumulator as k_conv_patch_r8: bit-identical.
-__device__ __forceinline__ void lw_dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned char* lds, unsigned off) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds, 16, off, 0, 0, 0);
-}
 template <int KH, int MT>
 __global__ void __launch_bounds__(256, 2) k_conv_patch_lw(const ConvP p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char psm[];
+    typedef vsrc::P8Geom<KH, MT> G;                   // (conv_patch.h)
     const int KW = KH;
-    const int PH = P8_H + KH - 1, PW = P8_W + KW - 1;
-    constexpr int PATCH_BYTES = (P8_H + KH - 1) * (P8_W + KH - 1) * 64;
-    constexpr int WROWS = 16 * MT;                    // weight rows (out-channels) of this workgroup
-    constexpr int WTAP = WROWS * 64;                  // one tap's block [16 MT][32] fp16
+    const int PH = G::PH, PW = G::PW;
+    constexpr int PATCH_BYTES = G::PATCH_BYTES, NPC = G::NPC;
+    constexpr int WROWS = G::WROWS;                   // weight rows (out-channels) of this workgroup
+    constexpr int WTAP = G::WTAP;                     // one tap's block [16 MT][32] fp16
     unsigned char* const patch = psm;                 // [PH][PW] pixels of 64 B (chunk XOR pixel-column bits 1-2)
     unsigned char* const wts = psm + PATCH_BYTES;     // [KH*KW][16 MT] rows of 64 B, 16-byte pieces XOR row bits 1-2 (sw_off)
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, g = lane >> 4;
-    const int tiles_x = (p.Wo + P8_W - 1) / P8_W;
-    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
-    const int n = blockIdx.y;
+    const vsrc::PatchTile t0 = vsrc::patch_tile<P8_H, P8_W>(p, p.Wo);
+    const int n = t0.n, oy0 = t0.oy0, ox0 = t0.ox0, iy0 = t0.iy0, ix0 = t0.ix0;
     const int co0 = blockIdx.z * WROWS;
-    const int oy0 = ty * P8_H, ox0 = tx * P8_W;
-    const int iy0 = oy0 - p.pad_y, ix0 = ox0 - p.pad_x;
     const int nchunk = p.cin >> 5;
     const int ry0 = P8_R * (wv >> 1), cx0 = 16 * (wv & 1);
 
@@ -1079,7 +985,6 @@ __global__ void __launch_bounds__(256, 2) k_conv_patch_lw(const ConvP p) {
     for (int r = 0; r < P8_R; ++r)
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) acc[r][mt] = f4{0.0f, 0.0f, 0.0f, 0.0f};
-    constexpr int NPC = ((P8_H + KH - 1) * (P8_W + KH - 1) * 4 + 255) / 256;
     unsigned poff[NPC];
     int pdst[NPC];
     patch_pieces(p, iy0, ix0, PH, PW, tid, poff, pdst);
@@ -1095,7 +1000,7 @@ __global__ void __launch_bounds__(256, 2) k_conv_patch_lw(const ConvP p) {
             const int tap = q / MT, blk = q - tap * MT;
             const int row = 16 * blk + wrow_l;
             const unsigned off = (unsigned)(((size_t)(tap * nchunk + ch) * p.cout_pad + co0 + row) * 64 + ((wslot ^ ((row >> 1) & 3)) << 4));
-            lw_dma16(w_rsrc, wts + tap * WTAP + 1024 * blk, off);
+            dma16(w_rsrc, wts + tap * WTAP + 1024 * blk, off);
         }
         stage_patch_cached(p, patch, n, ch, iy0, poff, pdst);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1109,25 +1014,13 @@ __global__ void __launch_bounds__(256, 2) k_conv_patch_lw(const ConvP p) {
                     A[ky][mt] = *reinterpret_cast<const h8*>(wts + (ky * KW + kx) * WTAP + sw_off(16 * mt + l15, g));
             const int px = cx0 + l15 + kx;
             const unsigned char* src = patch + (ry0 * PW + px) * 64 + ((g ^ ((px >> 1) & 3)) << 4);
-#pragma unroll
-            for (int pr = 0; pr < KH + P8_R - 1; ++pr) {
-                const h8 bf = *reinterpret_cast<const h8*>(src + pr * PW * 64);
-#pragma unroll
-                for (int r = 0; r < P8_R; ++r) {
-                    const int ky = pr - r;
-                    if (ky < 0 || ky >= KH) continue;
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) acc[r][mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[ky][mt], bf, acc[r][mt], 0, 0, 0);
-                }
-            }
+            vsrc::walk_tap_column<KH, P8_R, MT>(src, PW, A, acc, [](int) {});
         }
     }
     __syncthreads();
-    const long long wbase = (((long long)n * p.outH + (oy0 + ry0) * p.oy_mul + p.oy_off) * p.outW + (ox0 + cx0) * p.ox_mul + p.ox_off) * p.out_ld;
-    const int rstride = p.oy_mul * p.outW * p.out_ld, cstride = p.ox_mul * p.out_ld;
-    const int rows_ok = p.Ho - (oy0 + ry0), cols_ok = p.Wo - (ox0 + cx0);
+    const vsrc::WaveOut wo = vsrc::wave_out(p, n, oy0 + ry0, ox0 + cx0);
     patch_epilogue<MT, P8_R>(p, psm + wv * (P8_R * 16 * 32 * MT), co0, lane, [&](int r, int mt) { return acc[r][mt]; },
-                             [&](int r, int li) { return r < rows_ok && li < cols_ok ? wbase + r * rstride + li * cstride : -1ll; });
+                             [&](int r, int li) { return r < wo.rows_ok && li < wo.cols_ok ? wo.wbase + r * wo.rstride + li * wo.cstride : -1ll; });
 }
 
 // The hourglass stem (7x7, 3 -> 128, stride 1, at full resolution): 531 MB of output per 4-frame batch against 0.12
@@ -1290,221 +1183,6 @@ __global__ void __launch_bounds__(256) k_splitk_finish(const ConvP p) {
 }  // namespace
 
 
-// ---- NHWC fp16 glue of the hourglass (pytorch_DIW_scratch.py: MaxPool2d / AvgPool2d 2x2, UpsamplingNearest2d(2),
-//      coolAddTensors = nearest-resize + add): 16 bytes (8 channels) per thread, channel-slice aware on the input side.
-typedef _Float16 h8v __attribute__((ext_vector_type(8)));
-
-// mode 0: 2x2 max pool, 1: 2x2 average pool (both floor: out H/2 x W/2), 2: 2x2 max pool with ceil_mode (out ceil(H/2) x
-// ceil(W/2); the last window of an odd side holds one row / column).  in [N,H,W,in_ld] slice [in_coff, +C) -> out [N,Ho,Wo,C]
-__global__ void __launch_bounds__(256) k_pool2(const _Float16* __restrict__ in, int in_ld, int in_coff, _Float16* __restrict__ out,
-                                               int N, int H, int W, int C, int mode) {
-    // blockIdx.y = output row (n * Ho + oy), blockIdx.x walks (ox, 8-channel piece): 32-bit index math only
-    const int Ho = mode == 2 ? (H + 1) >> 1 : H >> 1, Wo = mode == 2 ? (W + 1) >> 1 : W >> 1;
-    const unsigned c8n = (unsigned)C >> 3;
-    const unsigned q = blockIdx.x * 256 + threadIdx.x;
-    if (q >= (unsigned)Wo * c8n) return;
-    const unsigned ox = q / c8n, c8 = q - ox * c8n;
-    const unsigned row = blockIdx.y, n = row / (unsigned)Ho, oy = row - n * (unsigned)Ho;
-    const int dy = 2 * (int)oy + 1 < H ? 1 : 0, dx = 2 * (int)ox + 1 < W ? 1 : 0;   // (ceil mode: a clamped window re-reads its own row / column)
-    const _Float16* p00 = in + (((size_t)n * H + 2 * oy) * W + 2 * ox) * in_ld + in_coff + 8 * c8;
-    const h8v a = *reinterpret_cast<const h8v*>(p00), b = *reinterpret_cast<const h8v*>(p00 + (size_t)dx * in_ld);
-    const h8v c = *reinterpret_cast<const h8v*>(p00 + (size_t)dy * W * in_ld), d = *reinterpret_cast<const h8v*>(p00 + ((size_t)dy * W + dx) * in_ld);
-    h8v o;
-    if (mode != 1) {
-        o = __builtin_elementwise_max(__builtin_elementwise_max(a, b), __builtin_elementwise_max(c, d));
-    } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (_Float16)(((float)a[e] + (float)b[e] + (float)c[e] + (float)d[e]) * 0.25f);
-    }
-    *reinterpret_cast<h8v*>(out + ((size_t)row * Wo + ox) * C + 8 * c8) = o;
-}
-
-// [N,C,H,W] fp32 -> [N,H,W,cp] fp16 with the channels >= C written as zeros (round to nearest even, like Tensor.half()):
-// the entry conversion of every trunk input in one pass instead of a zero fill plus a strided copy.  Thread = (pixel,
-// 4-channel piece): plane reads are coalesced along x, a pixel's pieces are written by adjacent lanes.
-__global__ void __launch_bounds__(256) k_nchw_to_nhwc_h(const float* __restrict__ in, _Float16* __restrict__ out, int N, int C, int HW, int cp) {
-    const int c4n = cp >> 2;
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)N * HW * c4n) return;
-    const int c4 = (int)(idx % c4n);
-    const long long px = idx / c4n;          // n * HW + p
-    const int n = (int)(px / HW);
-    const int pp = (int)(px - (long long)n * HW);
-    h4 v;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int c = 4 * c4 + j;
-        v[j] = c < C ? (_Float16)in[((size_t)n * C + c) * HW + pp] : (_Float16)0.0f;
-    }
-    *reinterpret_cast<h4*>(out + (size_t)px * cp + 4 * c4) = v;
-}
-
-// out[n,y,x,:] = a[n, y*Ha/H, x*Wa/W, slice a] (nearest, as F.interpolate(size)) + b[n,y,x, slice b]; b == null: resize only.
-
-// The same pass with either operand given as up to four channel SEGMENTS of equal width (separate tensors / slices): the 16-channel
-// branches of an inception block write dense [N,H,W,16] maps instead of 32-byte slices of a 512-byte pixel row (partial-line
-// writes: 3x3 64 -> 16 at 4 x 540 x 960 168 -> 118 us, 64 -> 1 139 -> 99, tools/thin_out_ab.py) and meet again here, where the
-// block's 64-channel result is read for the level's sum.
-// (ATen nearest: src = min(floor(dst * (in / out)), in - 1) with a float scale; up2: `a` stands for UpsamplingNearest2d(2)(a), never
-//  materialised -- the resize indexes the doubled map and halves the index; b_up2: `b` likewise, of exactly the output's size.
-//  blockIdx.y = image row, blockIdx.x walks (x, 8-channel piece) of that row: 32-bit index math only.)
-struct SegOp {
-    const _Float16* ptr[4];
-    int ld[4], coff[4];
-    int seg_c;     // channels per segment (a multiple of 8); one segment: = C
-};
-__global__ void __launch_bounds__(256) k_resize_add_segs(const SegOp a, int Ha, int Wa, const SegOp b, int has_b, _Float16* __restrict__ out, int N, int H,
-                                                         int W, int C, int up2, int b_up2) {
-    const unsigned c8n = (unsigned)C >> 3;
-    const unsigned q = blockIdx.x * 256 + threadIdx.x;
-    if (q >= (unsigned)W * c8n) return;
-    const unsigned x = q / c8n, c8 = q - x * c8n;
-    const unsigned row = blockIdx.y, n = row / (unsigned)H, y = row - n * (unsigned)H;
-    const int Hs = Ha << up2, Ws = Wa << up2;
-    const int ya = min((int)floorf((float)y * ((float)Hs / (float)H)), Hs - 1) >> up2;
-    const int xa = min((int)floorf((float)x * ((float)Ws / (float)W)), Ws - 1) >> up2;
-    const int ch = 8 * (int)c8;
-    const int sa = ch / a.seg_c, ca = ch - sa * a.seg_c;
-    const _Float16* ap = sa == 0 ? a.ptr[0] : sa == 1 ? a.ptr[1] : sa == 2 ? a.ptr[2] : a.ptr[3];
-    const int ald = sa == 0 ? a.ld[0] : sa == 1 ? a.ld[1] : sa == 2 ? a.ld[2] : a.ld[3];
-    const int aco = sa == 0 ? a.coff[0] : sa == 1 ? a.coff[1] : sa == 2 ? a.coff[2] : a.coff[3];
-    h8v v = *reinterpret_cast<const h8v*>(ap + (((size_t)n * Ha + ya) * Wa + xa) * ald + aco + ca);
-    if (has_b) {
-        const int sb = ch / b.seg_c, cb = ch - sb * b.seg_c;
-        const _Float16* bp = sb == 0 ? b.ptr[0] : sb == 1 ? b.ptr[1] : sb == 2 ? b.ptr[2] : b.ptr[3];
-        const int bld = sb == 0 ? b.ld[0] : sb == 1 ? b.ld[1] : sb == 2 ? b.ld[2] : b.ld[3];
-        const int bco = sb == 0 ? b.coff[0] : sb == 1 ? b.coff[1] : sb == 2 ? b.coff[2] : b.coff[3];
-        v += *reinterpret_cast<const h8v*>(bp + (((size_t)n * (H >> b_up2) + (y >> b_up2)) * (W >> b_up2) + (x >> b_up2)) * bld + bco + cb);
-    }
-    *reinterpret_cast<h8v*>(out + ((size_t)row * W + x) * C + ch) = v;
-}
-
-// ---- OSVOS head (reference networks/vgg_osvos.py: side_prep -> upscale ConvTranspose2d(16,16,k=2s,stride=s) -> centre
-//      crop -> cat -> fuse 1x1 (64 -> 1)).  Nothing non-linear sits between the transposed convolutions and the fuse,
-//      so the fuse row is folded into each branch's kernel on the host (weff[b][ky][kx][ci] = sum_co fuse[16b+co] *
-//      up_b[ci][co][ky][kx]) and one pass writes the logit: per output pixel 4 branches x 2x2 source pixels x 16
-//      channels, fp32 accumulate.  Replaces 4 transposed convolutions on 16-channel full-resolution maps, 4 crops, a
-//      concat and a convolution.
-struct OsvosP {
-    const _Float16* side[4];   // [N, hs, ws, ld] fp16, channels 0..15 live
-    const _Float16* weff[4];   // [2s][2s][16] fp16
-    int hs[4], ws[4], stride[4], oy[4], ox[4];   // crop offsets: output (y,x) = upsampled (y + oy, x + ox)
-    int ld;
-    float bias;
-    float* out;                // [N, h, w] fp32
-    int N, h, w, nb;
-};
-__global__ void __launch_bounds__(256) k_osvos_fuse(const OsvosP p) {
-    const long long total = (long long)p.N * p.h * p.w;
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    const int x = (int)(i % p.w);
-    const int y = (int)((i / p.w) % p.h);
-    const int n = (int)(i / ((long long)p.w * p.h));
-    float acc = p.bias;
-    for (int b = 0; b < p.nb; ++b) {
-        const int s = p.stride[b], Y = y + p.oy[b], X = x + p.ox[b];
-        const int iy1 = Y / s, ix1 = X / s;          // source pixel reached with tap (Y - iy1 s, X - ix1 s) in [0, s)
-        const int ky1 = Y - iy1 * s, kx1 = X - ix1 * s;
-#pragma unroll
-        for (int dy = 0; dy < 2; ++dy) {
-            const int iy = iy1 - dy, ky = ky1 + dy * s;
-            if (iy < 0 || iy >= p.hs[b]) continue;
-#pragma unroll
-            for (int dx = 0; dx < 2; ++dx) {
-                const int ix = ix1 - dx, kx = kx1 + dx * s;
-                if (ix < 0 || ix >= p.ws[b]) continue;
-                const h8* sp = reinterpret_cast<const h8*>(p.side[b] + (((size_t)n * p.hs[b] + iy) * p.ws[b] + ix) * p.ld);
-                const h8* wp = reinterpret_cast<const h8*>(p.weff[b] + ((size_t)ky * 2 * s + kx) * 16);
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    const h8 a = sp[q], wv = wp[q];
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) acc += (float)a[e] * (float)wv[e];
-                }
-            }
-        }
-    }
-    p.out[i] = acc;
-}
-
-// ---- FlowNetC cost volume on MFMA, NHWC fp16 in, straight into the concat buffer (reference FlowNetC.py: Correlation(pad 20,
-//      kernel 1, max_disp 20, stride1 1, stride2 2) + LeakyReLU(0.1); correlation_cuda_kernel.cu:74-147).
-//      out[b][y][x][coff + (tj*21 + ti)] = lrelu( 1/C * sum_c a[b][y][x][c] * bb[b][y + 2(tj-10)][x + 2(ti-10)][c] ).
-//      Workgroup = 32 pixels of one row; wave w takes the vertical displacements tj = w, w+4, ...  For one tj the full
-//      product G = A^T B of the 32 pixels against the 72-column window of row y2 is 80 MFMAs (M = pixels, N = window
-//      columns, K = C = 256) -- 3.4x more products than the band the volume keeps, but ~10 us of MFMA time for the whole
-//      map against 350 us of LDS-bound scalar FMAs in k_correlation; the band (column - pixel even, 0..40) is picked out
-//      of the accumulator tiles into an LDS image [32][441] and written as contiguous 882-byte pixel vectors.
-constexpr int CORR_D = 21, CORR_OC = CORR_D * CORR_D;
-__global__ void __launch_bounds__(256) k_corr_mfma(const _Float16* __restrict__ a, const _Float16* __restrict__ bb,
-                                                   _Float16* __restrict__ out, int out_ld, int out_coff, int H, int W, int C) {
-    __shared__ _Float16 stage[32 * CORR_OC];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int l15 = lane & 15, g = lane >> 4;
-    const int x0 = blockIdx.x * 32, y = blockIdx.y, b = blockIdx.z;
-    const int nks = C >> 5;   // 8 for C = 256
-    const size_t img = (size_t)b * H * W;
-    h8 Af[2][8];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-        const int px = x0 + 16 * mt + l15;
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) {
-            h8 v;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = (_Float16)0.0f;
-            if (px < W && ks < nks) v = *reinterpret_cast<const h8*>(a + (img + (size_t)y * W + px) * C + 32 * ks + 8 * g);
-            Af[mt][ks] = v;
-        }
-    }
-    const float inv = 1.0f / (float)C;
-    for (int tj = wv; tj < CORR_D; tj += 4) {
-        const int y2 = y + 2 * (tj - 10);
-        f4 acc[2][5];
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 5; ++nt) acc[mt][nt] = f4{0.0f, 0.0f, 0.0f, 0.0f};
-        if (y2 >= 0 && y2 < H) {   // wave-uniform; a row outside the image contributes zeros (the padding)
-#pragma unroll
-            for (int nt = 0; nt < 5; ++nt) {
-                const int col = x0 - 20 + 16 * nt + l15;
-                const bool ok = col >= 0 && col < W;
-                const _Float16* src = bb + (img + (size_t)y2 * W + (ok ? col : 0)) * C + 8 * g;
-#pragma unroll
-                for (int ks = 0; ks < 8; ++ks) {
-                    h8 v;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = (_Float16)0.0f;
-                    if (ok && ks < nks) v = *reinterpret_cast<const h8*>(src + 32 * ks);
-#pragma unroll
-                    for (int mt = 0; mt < 2; ++mt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Af[mt][ks], v, acc[mt][nt], 0, 0, 0);
-                }
-            }
-        }
-        // band: window column cl = 16 nt + l15, pixel pl = 16 mt + 4 g + r; cl - pl = 2 ti
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 5; ++nt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int pl = 16 * mt + 4 * g + r, d = 16 * nt + l15 - pl;
-                    if (d >= 0 && d <= 40 && (d & 1) == 0) {
-                        float v = acc[mt][nt][r] * inv;
-                        v = v >= 0.0f ? v : 0.1f * v;
-                        stage[pl * CORR_OC + tj * CORR_D + (d >> 1)] = (_Float16)v;
-                    }
-                }
-    }
-    __syncthreads();
-    for (int idx = tid; idx < 32 * CORR_OC; idx += 256) {
-        const int pl = idx / CORR_OC, tc = idx - pl * CORR_OC;
-        if (x0 + pl < W) out[(img + (size_t)y * W + x0 + pl) * out_ld + out_coff + tc] = stage[idx];
-    }
-}
-
 // k_conv_igemm_d<.., 5>: five register sets, four K steps in flight, for launches of at most one workgroup per CU (0 never -- the
 // default --, 1 that rule, 2 always; vsr_conv2d_tuning(8000 + n)).  Measured (tools/trunks_time.py, one box): FlowNet2 3.06 / 3.09 /
 // 3.16 ms, hourglass x4 4.76 / 4.66 / 4.70, OSVOS 1.186 / 1.177 / 1.230 for n = 0 / 1 / 2 -- inside the run-to-run spread: the
@@ -1513,12 +1191,12 @@ VSR_TUNABLE g_gather_deep = 0;
 // k_conv_igemm_d's dynamic LDS: the double-buffered weight ring + the K-walk table of one workgroup's range of steps
 template <int BN, bool STEM>
 static int launch_gather(const ConvP& p, dim3 grid, hipStream_t stream) {
-    const int nchunk = STEM ? 1 : p.cin >> 5, npair = STEM ? p.kh : p.kh * p.kw * nchunk;
-    const int nk_all = (npair + 1) >> 1, ks_per = (nk_all + p.splits - 1) / p.splits;
+    const vsrc::KSteps k = vsrc::k_steps(STEM, p.kh, p.kw, p.cin, p.splits);
+    const int npair = k.npair, ks_per = k.ks_per;
     // five register sets (four K steps in flight) where the launch leaves one workgroup on a CU: nothing else hides the
     // memory latency there and the registers are free (g_gather_deep: 0 never, 1 that rule, 2 always)
     const bool deep = g_gather_deep == 2 || (g_gather_deep == 1 && (long long)grid.x * grid.y * grid.z <= 256 && ks_per >= 8);
-    const size_t lds = (size_t)BN * 256 + (size_t)2 * (ks_per + (deep ? 9 : 5)) * 16;
+    const size_t lds = (size_t)BN * 256 + (size_t)vsrc::kwalk_entries(ks_per, vsrc::kwalk_gather_lookahead(deep ? 5 : 3)) * 16;
     if (lds > 64 * 1024) return vsr::fail(VSR_E_ARG, "conv2d: %d K steps per workgroup exceed the kernel's walk table (split K further)", ks_per);
     if ((unsigned long long)npair * p.cout_pad * 64 >= (1ull << 30)) return vsr::fail(VSR_E_ARG, "conv2d: packed weights beyond 1 GiB");
 #if VSR_X
@@ -1531,9 +1209,9 @@ static int launch_gather(const ConvP& p, dim3 grid, hipStream_t stream) {
 #if VSR_X
 template <int BN, bool STEM>
 static int launch_gather_lds(const ConvP& p, dim3 grid, hipStream_t stream) {
-    const int nchunk = STEM ? 1 : p.cin >> 5, npair = STEM ? p.kh : p.kh * p.kw * nchunk;
-    const int nk_all = (npair + 1) >> 1, ks_per = (nk_all + p.splits - 1) / p.splits;
-    const size_t lds = (size_t)4 * (BN * 64 + BM * 64) + (size_t)2 * (ks_per + 5) * 16;
+    const vsrc::KSteps k = vsrc::k_steps(STEM, p.kh, p.kw, p.cin, p.splits);
+    const int npair = k.npair, ks_per = k.ks_per;
+    const size_t lds = (size_t)4 * (BN * 64 + BM * 64) + (size_t)vsrc::kwalk_entries(ks_per, vsrc::KWALK_FIRST_LOOKAHEAD) * 16;
     if (lds > 64 * 1024) return vsr::fail(VSR_E_ARG, "conv2d: %d K steps per workgroup exceed the kernel's walk table (split K further)", ks_per);
     if ((unsigned long long)npair * p.cout_pad * 64 >= (1ull << 30)) return vsr::fail(VSR_E_ARG, "conv2d: packed weights beyond 1 GiB");
     hipLaunchKernelGGL((k_conv_igemm<BN, STEM>), grid, dim3(256), lds, stream, p);
@@ -1865,8 +1543,9 @@ static int launch_route(const ConvP& p, const ConvRoute& r, hipStream_t st) {
                                   {{k_conv_patch_r8<7, 2>, 0}, {k_conv_patch_r8<7, 1>, 0}}, {{k_conv_patch_r8<11, 2>, 0}, {k_conv_patch_r8<11, 1>, 0}}};
         const bool is_lw = r.kind == Kind::patch_lw;
         BigLds& e = is_lw ? lw[r.mt == 4 ? 0 : 1 + kh_slot(kh)] : r8[kh_slot(kh)][2 - r.mt];
-        const int lds_patch = is_lw ? (P8_H + kh - 1) * (P8_W + kh - 1) * 64 + kh * kh * 16 * r.mt * 64 : (P8_H + kh - 1) * (P8_W + p.kw - 1) * 64;
-        const int lds_out = 4 * P8_R * 16 * 32 * r.mt, lds = lds_patch > lds_out ? lds_patch : lds_out;
+        static const int lw_lds[4] = {vsrc::P8Geom<3, 4>::LW_LDS, vsrc::P8Geom<3, 2>::LW_LDS, vsrc::P8Geom<5, 2>::LW_LDS, vsrc::P8Geom<7, 2>::LW_LDS};
+        const int r8_patch = (P8_H + kh - 1) * (P8_W + p.kw - 1) * 64, r8_out = 4 * P8_R * 16 * 32 * r.mt;
+        const int lds = is_lw ? lw_lds[r.mt == 4 ? 0 : 1 + kh_slot(kh)] : r8_patch > r8_out ? r8_patch : r8_out;
         if (lds > 64 * 1024) raise_lds(e);
         hipLaunchKernelGGL(e.k, dim3(vsr::cdiv(p.Ho, P8_H) * vsr::cdiv(p.Wo, P8_W), p.N, p.cout_pad / (16 * r.mt)), dim3(256), lds, st, p);
         break;
@@ -2047,83 +1726,6 @@ int vsr_conv2d_tuning(int patch_mode) {
     return old;
 }
 #endif  // VSR_X
-
-int vsr_pool2x2_nhwc_f16(const void* in, int in_ld, int in_coff, void* out, int N, int H, int W, int C, int mode,
-                         vsr_stream_t stream) {
-    VSR_REQUIRE(in && out, "pool2x2: null pointer");
-    VSR_REQUIRE(N > 0 && H >= 2 && W >= 2 && C > 0 && (C & 7) == 0 && (in_ld & 7) == 0 && (in_coff & 7) == 0 && in_coff + C <= in_ld &&
-                    (mode >= 0 && mode <= 2), "pool2x2: bad arguments");
-    const int Ho = mode == 2 ? (H + 1) >> 1 : H >> 1, Wo = mode == 2 ? (W + 1) >> 1 : W >> 1;
-    VSR_REQUIRE((long long)N * Ho <= 65535 && (long long)Wo * (C >> 3) < (1ll << 31), "pool2x2: more than 65535 output rows");
-    hipLaunchKernelGGL(k_pool2, dim3(vsr::cdiv((long long)Wo * (C >> 3), 256), (unsigned)(N * Ho)), dim3(256), 0, vsr::S(stream),
-                       (const _Float16*)in, in_ld, in_coff, (_Float16*)out, N, H, W, C, mode);
-    return vsr::launched("pool2x2");
-}
-
-int vsr_nchw_f32_to_nhwc_f16(const float* in, void* out, int N, int C, int H, int W, int cp, vsr_stream_t stream) {
-    VSR_REQUIRE(in && out, "nchw_to_nhwc: null pointer");
-    VSR_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0 && cp >= C && (cp & 3) == 0, "nchw_to_nhwc: bad shape");
-    const long long total = (long long)N * H * W * (cp >> 2);
-    hipLaunchKernelGGL(k_nchw_to_nhwc_h, dim3(vsr::cdiv(total, 256)), dim3(256), 0, vsr::S(stream), in, (_Float16*)out, N, C, H * W, cp);
-    return vsr::launched("nchw_f32_to_nhwc_f16");
-}
-
-int vsr_resize_add_segs_nhwc_f16(const void* const* a_ptrs, const int* a_lds, const int* a_coffs, int a_nseg, int Ha, int Wa, int up2,
-                                 const void* const* b_ptrs, const int* b_lds, const int* b_coffs, int b_nseg, int b_up2, void* out, int N, int H,
-                                 int W, int C, vsr_stream_t stream) {
-    VSR_REQUIRE(a_ptrs && a_lds && a_coffs && out && a_nseg >= 1 && a_nseg <= 4 && b_nseg >= 0 && b_nseg <= 4, "resize_add_segs: bad segment lists");
-    VSR_REQUIRE(b_nseg == 0 || (b_ptrs && b_lds && b_coffs), "resize_add_segs: addend segments");
-    VSR_REQUIRE((up2 == 0 || up2 == 1) && (b_up2 == 0 || (b_up2 == 1 && b_nseg > 0 && (H & 1) == 0 && (W & 1) == 0)),
-                "resize_add_segs: up2 flags (an upsampled addend needs an even output size)");
-    VSR_REQUIRE(N > 0 && H > 0 && W > 0 && Ha > 0 && Wa > 0 && C > 0 && (C & 7) == 0 && C % a_nseg == 0 && ((C / a_nseg) & 7) == 0 &&
-                    (b_nseg == 0 || (C % b_nseg == 0 && ((C / b_nseg) & 7) == 0)), "resize_add_segs: channels per segment must be a multiple of 8");
-    VSR_REQUIRE((long long)N * H <= 65535 && (long long)W * (C >> 3) < (1ll << 31), "resize_add_segs: more than 65535 image rows");
-    SegOp a, b;
-    for (int i = 0; i < 4; ++i) { a.ptr[i] = b.ptr[i] = nullptr; a.ld[i] = b.ld[i] = 8; a.coff[i] = b.coff[i] = 0; }
-    a.seg_c = C / a_nseg;
-    b.seg_c = b_nseg ? C / b_nseg : C;
-    for (int i = 0; i < a_nseg; ++i) {
-        VSR_REQUIRE(a_ptrs[i] && (a_lds[i] & 7) == 0 && (a_coffs[i] & 7) == 0 && a_coffs[i] + a.seg_c <= a_lds[i], "resize_add_segs: segment %d of a", i);
-        a.ptr[i] = (const _Float16*)a_ptrs[i]; a.ld[i] = a_lds[i]; a.coff[i] = a_coffs[i];
-    }
-    for (int i = 0; i < b_nseg; ++i) {
-        VSR_REQUIRE(b_ptrs[i] && (b_lds[i] & 7) == 0 && (b_coffs[i] & 7) == 0 && b_coffs[i] + b.seg_c <= b_lds[i], "resize_add_segs: segment %d of b", i);
-        b.ptr[i] = (const _Float16*)b_ptrs[i]; b.ld[i] = b_lds[i]; b.coff[i] = b_coffs[i];
-    }
-    hipLaunchKernelGGL(k_resize_add_segs, dim3(vsr::cdiv((long long)W * (C >> 3), 256), (unsigned)(N * H)), dim3(256), 0, vsr::S(stream), a, Ha, Wa, b,
-                       b_nseg > 0 ? 1 : 0, (_Float16*)out, N, H, W, C, up2, b_up2);
-    return vsr::launched("resize_add_segs");
-}
-
-int vsr_osvos_fuse_f16(const void* const* side, const int* hs, const int* ws, int ld, const void* const* weff, const int* strides,
-                       int nbranch, float bias, float* out, int N, int h, int w, vsr_stream_t stream) {
-    VSR_REQUIRE(side && hs && ws && weff && strides && out, "osvos_fuse: null pointer");
-    VSR_REQUIRE(nbranch >= 1 && nbranch <= 4 && N > 0 && h > 0 && w > 0 && ld >= 16 && (ld & 7) == 0, "osvos_fuse: bad arguments");
-    OsvosP p;
-    for (int b = 0; b < 4; ++b) {
-        p.side[b] = nullptr; p.weff[b] = nullptr; p.hs[b] = p.ws[b] = p.stride[b] = 1; p.oy[b] = p.ox[b] = 0;
-        if (b >= nbranch) continue;
-        VSR_REQUIRE(side[b] && weff[b] && strides[b] >= 1 && hs[b] > 0 && ws[b] > 0, "osvos_fuse: branch %d", b);
-        const int uh = (hs[b] + 1) * strides[b], uw = (ws[b] + 1) * strides[b];   // (hs - 1) s + 2 s
-        VSR_REQUIRE(uh >= h && uw >= w, "osvos_fuse: branch %d upsamples to %dx%d < %dx%d", b, uh, uw, h, w);
-        p.side[b] = (const _Float16*)side[b]; p.weff[b] = (const _Float16*)weff[b];
-        p.hs[b] = hs[b]; p.ws[b] = ws[b]; p.stride[b] = strides[b];
-        p.oy[b] = (uh - h) / 2; p.ox[b] = (uw - w) / 2;   // centre crop (vgg_osvos.py center_crop)
-    }
-    p.ld = ld; p.bias = bias; p.out = out; p.N = N; p.h = h; p.w = w; p.nb = nbranch;
-    hipLaunchKernelGGL(k_osvos_fuse, dim3(vsr::cdiv((long long)N * h * w, 256)), dim3(256), 0, vsr::S(stream), p);
-    return vsr::launched("osvos_fuse");
-}
-
-int vsr_flownetc_corr_nhwc_f16(const void* feat_a, const void* feat_b, void* out, int out_ld, int out_coff, int B, int H, int W, int C,
-                               vsr_stream_t stream) {
-    VSR_REQUIRE(feat_a && feat_b && out, "flownetc_corr: null pointer");
-    VSR_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && (C & 31) == 0 && C <= 256, "flownetc_corr: C must be a multiple of 32 up to 256");
-    VSR_REQUIRE(out_coff >= 0 && out_coff + CORR_OC <= out_ld && B <= 65535 && H <= 65535, "flownetc_corr: output slice / grid");
-    hipLaunchKernelGGL(k_corr_mfma, dim3(vsr::cdiv(W, 32), H, B), dim3(256), 0, vsr::S(stream), (const _Float16*)feat_a,
-                       (const _Float16*)feat_b, (_Float16*)out, out_ld, out_coff, H, W, C);
-    return vsr::launched("flownetc_corr");
-}
 
 int vsr_conv2d_route_batch(int num, int den) {
     VSR_REQUIRE(num >= 0 && den >= 0 && num <= 65535 && den <= 65535, "conv2d_route_batch: %d / %d", num, den);

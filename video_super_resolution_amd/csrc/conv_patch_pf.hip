@@ -26,23 +26,11 @@ using vsrc::P8_R;
 using vsrc::P8_W;
 using vsrc::sw_off;
 
-typedef unsigned int u4v __attribute__((ext_vector_type(4)));
-
-template <int KH, int MT>
-struct PfGeom {
-    static constexpr int PH = P8_H + KH - 1, PW = P8_W + KH - 1;
-    static constexpr int PATCH_BYTES = PH * PW * 64;
-    static constexpr int WROWS = 16 * MT, WTAP = WROWS * 64, WBYTES = KH * KH * WTAP;
-    static constexpr int NPC = (PH * PW * 4 + 255) / 256;      // 16-byte patch pieces per thread
-    static constexpr int NWC = (WBYTES / 16 + 255) / 256;      // 16-byte weight pieces per thread
-    static constexpr int OUT_BYTES = 4 * P8_R * 16 * 32 * MT;  // epilogue: 4 wave slices
-    static constexpr int LDS = (PATCH_BYTES > OUT_BYTES ? PATCH_BYTES : OUT_BYTES) + WBYTES;
-    static constexpr int WOFF = LDS - WBYTES;                  // weight block behind the patch / epilogue region
-};
+typedef vsrc::u4 u4v;
 
 template <int KH, int MT, int WPS>
 __global__ void __launch_bounds__(256, WPS) k_conv_patch_pf(const ConvP p, int tiles_x, int tiles_y, int nwork) {
-    typedef PfGeom<KH, MT> G;
+    typedef vsrc::P8Geom<KH, MT> G;   // (conv_patch.h; this kernel's LDS: G::LDS, weight block at G::WOFF)
     constexpr int PH = G::PH, PW = G::PW, NPC = G::NPC, NWC = G::NWC, WTAP = G::WTAP;
     extern __shared__ __attribute__((aligned(16))) unsigned char psm[];
     unsigned char* const patch = psm;
@@ -89,17 +77,10 @@ __global__ void __launch_bounds__(256, WPS) k_conv_patch_pf(const ConvP p, int t
         it.by = iy0 > 0 ? iy0 : 0;
         return it;
     };
-    auto in_rsrc = [&](const Item& it) {
-        const size_t rem_bytes = (size_t)(p.H - it.by) * p.W * p.in_ld * 2;
-        return __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(p.in) + ((size_t)it.n * p.H + it.by) * p.W * p.in_ld, 0,
-                                                 (int)(rem_bytes < 0x7FFFFFF0ull ? rem_bytes : 0x7FFFFFF0ull), 0x00020000);
-    };
     auto issue = [&](const Item& it, int ch) __attribute__((always_inline)) {
-        const __amdgpu_buffer_rsrc_t rs = in_rsrc(it);
-        const unsigned coff = (unsigned)ch * 64u;
+        const __amdgpu_buffer_rsrc_t rs = vsrc::patch_rsrc_at(p, it.n, it.by);
 #pragma unroll
-        for (int k = 0; k < NPC; ++k)
-            pf[k] = __builtin_amdgcn_raw_buffer_load_b128(rs, poff[k] == 0xFFFFFFFFu ? 0xFFFFFFFFu : poff[k] + coff, 0, 0);
+        for (int k = 0; k < NPC; ++k) pf[k] = __builtin_amdgcn_raw_buffer_load_b128(rs, vsrc::cached_piece_off(poff[k], ch), 0, 0);
         const unsigned woff = (unsigned)(((size_t)ch * p.cout_pad + it.co0) * 64);
 #pragma unroll
         for (int j = 0; j < NWC; ++j)
@@ -162,11 +143,9 @@ __global__ void __launch_bounds__(256, WPS) k_conv_patch_pf(const ConvP p, int t
         if (!last_chunk) { ++ch; continue; }
         __syncthreads();          // the patch memory carries the output tile now
         {
-            const long long wbase = (((long long)cur.n * p.outH + (cur.oy0 + ry0) * p.oy_mul + p.oy_off) * p.outW + (cur.ox0 + cx0) * p.ox_mul + p.ox_off) * p.out_ld;
-            const int rstride = p.oy_mul * p.outW * p.out_ld, cstride = p.ox_mul * p.out_ld;
-            const int rows_ok = p.Ho - (cur.oy0 + ry0), cols_ok = p.Wo - (cur.ox0 + cx0);
+            const vsrc::WaveOut wo = vsrc::wave_out(p, cur.n, cur.oy0 + ry0, cur.ox0 + cx0);
             vsrc::patch_epilogue<MT, P8_R>(p, psm + wv * (P8_R * 16 * 32 * MT), cur.co0, lane, [&](int r, int mt) { return acc[r][mt]; },
-                                           [&](int r, int li) { return r < rows_ok && li < cols_ok ? wbase + r * rstride + li * cstride : -1ll; });
+                                           [&](int r, int li) { return r < wo.rows_ok && li < wo.cols_ok ? wo.wbase + r * wo.rstride + li * wo.cstride : -1ll; });
         }
         if (!have_next) break;
 #pragma unroll
@@ -179,7 +158,7 @@ __global__ void __launch_bounds__(256, WPS) k_conv_patch_pf(const ConvP p, int t
 
 template <int KH, int MT, int WPS>
 int launch_pf(const ConvP& p, int N, hipStream_t stream) {
-    typedef PfGeom<KH, MT> G;
+    typedef vsrc::P8Geom<KH, MT> G;
     static unsigned long long raised = 0;
     if (G::LDS > 64 * 1024) vsr::raise_lds_limit_once(raised, &k_conv_patch_pf<KH, MT, WPS>, 160 * 1024);
     const int tiles_x = (int)vsr::cdiv(p.Wo, P8_W), tiles_y = (int)vsr::cdiv(p.Ho, P8_H);

@@ -21,6 +21,7 @@
 // Same products as the gather kernel in another summation order (fp32 accumulate): parity is tested against the stock
 // operator at the gather kernel's bar and against the gather kernel itself (tests/test_gpu_conv.py).
 #include "conv_common.h"
+#include "conv_kwalk.h"
 
 namespace {
 
@@ -29,19 +30,11 @@ using vsrc::f4;
 using vsrc::h4;
 using vsrc::h8;
 using vsrc::sw_off;
-typedef unsigned int u4 __attribute__((ext_vector_type(4)));
+using vsrc::u4;
+using vsrc::dma16;
 
 constexpr int TM = 128;                       // pixels per workgroup
 constexpr int B_HALF = TM * 64;               // pixel tile of one (tap, 32-channel chunk) pair
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-// One LDS-DMA piece: lane L's 16 bytes at buffer offset `off` (zeros when out of range) -> LDS bytes [16 L, 16 L + 16) of the
-// 1-KiB piece at `lds` (wave-uniform).  (A plain function: inside the kernel TEMPLATE the builtin fails the host pass's
-// instantiation of the kernel stub, silently -- the launch then links against an undefined symbol.)
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned char* lds, unsigned off) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)lds, 16, off, 0, 0, 0);
-}
 
 template <int BN>
 __global__ void __launch_bounds__(256, 2) k_conv_tile(const ConvP p, int gx, int gy, int nwg) {
@@ -68,36 +61,14 @@ __global__ void __launch_bounds__(256, 2) k_conv_tile(const ConvP p, int gx, int
     const int nchunk = p.cin >> 5;
     const int npair = p.kh * p.kw * nchunk;
     const int nk_all = (npair + 1) >> 1;
-    const int ph = p.nphase > 1 ? (bz & 3) : 0;
-    const int zsplit = p.nphase > 1 ? (bz >> 2) : bz;
-    const _Float16* const wpk = p.nphase > 1 ? p.wpk_ph[ph] : p.wpk;
-    const int pad_y = p.nphase > 1 ? p.pad_y_ph[ph] : p.pad_y, pad_x = p.nphase > 1 ? p.pad_x_ph[ph] : p.pad_x;
-    const int oy_off = p.nphase > 1 ? p.oy_off_ph[ph] : p.oy_off, ox_off = p.nphase > 1 ? p.ox_off_ph[ph] : p.ox_off;
-    const int ks_per = (nk_all + p.splits - 1) / p.splits;
-    const int ks0 = zsplit * ks_per;
-    const int nk = min(nk_all, ks0 + ks_per);
+    const vsrc::KRange kr = vsrc::k_range(p, bz, nk_all);
+    const int ph = kr.ph, zsplit = kr.zsplit, pad_y = kr.pad_y, pad_x = kr.pad_x, oy_off = kr.oy_off, ox_off = kr.ox_off;
+    const int ks_per = kr.ks_per, ks0 = kr.ks0, nk = kr.nk;
+    const _Float16* const wpk = kr.wpk;
 
-    const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<_Float16*>(wpk), 0, (int)((size_t)npair * p.cout_pad * 64), 0x00020000);
-    const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<_Float16*>(p.in), 0, (int)((size_t)p.N * p.H * p.W * p.in_ld * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t w_rsrc = vsrc::kwalk_w_rsrc(p, wpk, npair), in_rsrc = vsrc::kwalk_in_rsrc(p);
 
-    // ---- K-walk table: entry i = pair 2 ks0 + i as {input byte offset of (tap, chunk) relative to tap (0,0) chunk 0, ky, kx,
-    //      byte offset of the pair's weight slab}; pairs past the kernel / this split's range fail every bounds test and point
-    //      past the slabs (zeros)
-    {
-        const int pr0 = 2 * ks0, ntab = 2 * (ks_per + 2);
-        const unsigned wstep = (unsigned)p.cout_pad * 64u;
-        for (int i = tid; i < ntab; i += 256) {
-            const int pr = pr0 + i;
-            const bool live = pr < npair && pr < 2 * nk;
-            const int prc = live ? pr : 0;
-            const int tap = prc / nchunk, ch = prc - tap * nchunk;
-            const int ky = tap / p.kw, kx = tap - ky * p.kw;
-            const unsigned delta = ((unsigned)(ky * p.W + kx) * (unsigned)p.in_ld + (unsigned)ch * 32u) * 2u;
-            tab[i] = live ? u4{delta, (unsigned)ky, (unsigned)kx, (unsigned)pr * wstep} : u4{0u, 1u << 29, 0u, 0x80000000u};
-        }
-    }
+    vsrc::build_kwalk<false>(p, tab, tid, ks0, nk, npair, nchunk, vsrc::kwalk_entries(ks_per, vsrc::KWALK_TILE_LOOKAHEAD));
 
     // ---- what this lane fetches: in every 1-KiB DMA piece lane L fills LDS bytes [16 L, 16 L + 16) of the piece, i.e. row
     //      L >> 2, physical slot L & 3 of a 16-row group; under the read swizzle that slot holds channel chunk
@@ -109,15 +80,8 @@ __global__ void __launch_bounds__(256, 2) k_conv_tile(const ConvP p, int gx, int
     for (int q = 0; q < 2; ++q) {            // pixel rows 32 wv + 16 q + rg of the tile
         const int row = 32 * wv + 16 * q + rg;
         const int chunk = slot ^ ((row >> 1) & 3);
-        const long long m = m0 + row;
-        const bool ok = m < M;
-        const unsigned mm = ok ? (unsigned)m : 0u, HoWo = (unsigned)(p.Ho * p.Wo);
-        const int n = (int)(mm / HoWo);
-        const int rem = (int)(mm - (unsigned)n * HoWo);
-        const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
-        piy0[q] = ok ? oy * p.stride - pad_y : -(1 << 28);
-        pix0[q] = ox * p.stride_x - pad_x;
-        pbase[q] = (unsigned)(((((long long)n * p.H + piy0[q]) * p.W + pix0[q]) * p.in_ld + p.in_coff + chunk * 8) * 2);
+        const vsrc::PixOrigin o = vsrc::pixel_origin<false>(p, m0 + row, M, pad_y, pad_x, chunk);
+        piy0[q] = o.piy0; pix0[q] = o.pix0; pbase[q] = o.pbase;
     }
     unsigned wlane[AQ];
 #pragma unroll
@@ -240,8 +204,9 @@ int launch_bn(const ConvP& p, hipStream_t stream) {
     const int gz = (p.nphase > 1 ? 4 : 1) * p.splits;
     const long long nwg = (long long)gx * gy * gz;
     if (nwg >= (1ll << 30)) return vsr::fail(VSR_E_ARG, "conv2d/tile: %lld workgroups", nwg);
-    const int npair = p.kh * p.kw * (p.cin >> 5), nk_all = (npair + 1) >> 1, ks_per = (nk_all + p.splits - 1) / p.splits;
-    const size_t lds = (size_t)4 * (BN * 64 + B_HALF) + (size_t)2 * (ks_per + 2) * 16;
+    const vsrc::KSteps k = vsrc::k_steps(false, p.kh, p.kw, p.cin, p.splits);
+    const int npair = k.npair, ks_per = k.ks_per;
+    const size_t lds = (size_t)4 * (BN * 64 + B_HALF) + (size_t)vsrc::kwalk_entries(ks_per, vsrc::KWALK_TILE_LOOKAHEAD) * 16;
     if (lds > 160 * 1024) return vsr::fail(VSR_E_ARG, "conv2d/tile: %d K steps per workgroup exceed the walk table (split K further)", ks_per);
     if ((unsigned long long)npair * p.cout_pad * 64 >= (1ull << 30)) return vsr::fail(VSR_E_ARG, "conv2d/tile: packed weights beyond 1 GiB");
     static unsigned long long raised = 0;

@@ -551,7 +551,7 @@ def osvos_fold(upscale_weights, fuse_weight):
     """upscale (ConvTranspose2d 16->16, k = 2s, stride s) -> centre crop -> cat -> fuse 1x1 is linear: fold the fuse row into each
     branch's transposed-conv kernel.  upscale_weights: [16 (in), 16 (out), k, k] per branch; fuse_weight: 16 entries per branch in
     cat order (any shape).  -> [weff_b] fp16 [k][k][16 (in)], weff_b[ky][kx][ci] = sum_co fuse[16 b + co] * up_b[ci][co][ky][kx]
-    (csrc/conv_igemm.hip k_osvos_fuse)."""
+    (csrc/conv_glue.hip k_osvos_fuse)."""
     fw = fuse_weight.detach().float().reshape(-1)
     return [torch.einsum("iokl,o->kli", w.detach().float(), fw[16 * b:16 * b + 16]).contiguous().half()
             for b, w in enumerate(upscale_weights)]
