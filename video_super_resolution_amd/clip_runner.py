@@ -1,7 +1,8 @@
 """`ClipRunner`: a 4:2:0 clip streamed through the model on top of `frames`: every source frame uploaded once from pinned memory on a
 copy stream, converted once into a three-slot LR ring, the window formed on the device, the HR frame written out as 4:2:0 and copied
 back on a second copy stream.  What a run scores (`score=`, `baseline=`, `temporal=`) is a list of series, each a range of rows of one
-float64 tensor of sums (`sums_layout`); `driver` imports `ClipRunner`, so `driver.ClipRunner` resolves as before.
+float64 tensor of sums (`sums_layout`); with `scene="sad"` scene cuts are found and the window composed under them on the device, in
+tensors of their own; `driver` imports `ClipRunner`, so `driver.ClipRunner` resolves as before.
 """
 from __future__ import annotations
 
@@ -11,8 +12,8 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 import torch
 
-from .frames import (METRIC_CHANNELS, FrameResizer, ewarp, frame_metrics, psnr_ssim, truth_flows, warp_error, yuv_coefficients,
-                     yuv_frame_bytes, yuv_ingest, yuv_write)
+from .frames import (METRIC_CHANNELS, FrameResizer, _scene_thresholds, ewarp, frame_metrics, psnr_ssim, scene_flags, scene_sums,
+                     scene_window, truth_flows, warp_error, yuv_coefficients, yuv_frame_bytes, yuv_ingest, yuv_write)
 
 # series of `sums_layout` -> the keys of `ClipRunner.metrics` its host step (`psnr_ssim` for a frame series, `ewarp` for a pair series)
 # fills; the occlusion mask depends on the flows alone, so the estimate's pairs give the one `valid_share`
@@ -79,16 +80,30 @@ class ClipRunner:
     T - 3 rows each that travel in the one copy at the end:
     `metrics` gains `ewarp`, `ewarp_truth`, `valid_share` (the occlusion mask depends on the flows alone: one share for all) and, with a
     baseline, `ewarp_baseline`, each [T-3] (empty for T = 3).  No upload, download or host wait is added; with `temporal=None` the
-    launches are the ones described above."""
+    launches are the ones described above.
+
+    `scene="sad"`: scene cuts found and handled on the device (include/vsr_hip_scene.h).  After source frame i >= 1 has been converted
+    into its ring slot, `scene_sums` of the ring's frames i - 1 and i goes into row i - 1 of a [T-1,2] float64 tensor and `scene_flags`
+    of that row, with the row above as the pair before, into element i - 1 of a [T-1] int32 tensor.  The window of frames i - 2 .. i
+    = (a, b, c) is then `scene_window`'s under the flags of the pairs (a, b) and (b, c): a cut between a and b gives (b, b, c) and
+    restarts the recurrence from b, a cut between b and c gives (a, b, b): for a clip A ++ B with one cut the outputs are those of a run
+    over A ++ [A[-1]] followed by those of a fresh run over [B[0]] ++ B.  The host never reads a flag: no host wait is added, no byte
+    more is uploaded, and the two small tensors (views of one buffer) come back in one copy at the end of `run()`: `cuts` (bool [T-1],
+    entry i - 1 is the pair (i - 1, i)) and `scene_m` (float64 [T-1], the mean absolute luma difference).  `scene_thresholds`:
+    (t_abs, ratio), default `frames.SCENE_THRESHOLDS`: this project's choice, not validated on real video.  With `temporal="warp"` the
+    rows of `ewarp`, `ewarp_truth` and `ewarp_baseline` whose flows cross a cut (row r where `cuts[r + 1]`) are NaN: a warping error
+    across a cut measures nothing; `valid_share` stays as computed.  With `scene=None` the launches are the ones described above and
+    `cuts` and `scene_m` are None."""
 
     DECIMATE = ("nearest", "bicubic")
     BASELINE = (None, "bicubic")
     TEMPORAL = (None, "warp")
+    SCENE = (None, "sad")
 
     def __init__(self, model, shape: Tuple[int, int], fmt_in: str, fmt_out: str, scale_down: int = 1, overlap: bool = True,
                  matrix: str = "bt709", full_range: bool = False, siting: str = "left", score: Optional[str] = None,
                  shave: Optional[int] = None, decimate: str = "nearest", baseline: Optional[str] = None, temporal: Optional[str] = None,
-                 occ=None):
+                 occ=None, scene: Optional[str] = None, scene_thresholds=None):
         if decimate not in self.DECIMATE:
             raise ValueError(f"decimate must be 'nearest' or 'bicubic', got {decimate!r}")
         if baseline not in self.BASELINE:
@@ -101,7 +116,13 @@ class ClipRunner:
             raise ValueError(f"temporal={temporal!r} is scored beside the estimate: it needs score='rgb' or 'y'")
         if occ is not None and temporal is None:
             raise ValueError("occ is given but no temporal score is asked for (temporal=None)")
+        if scene not in self.SCENE:
+            raise ValueError(f"scene must be None or 'sad', got {scene!r}")
+        if scene_thresholds is not None and scene is None:
+            raise ValueError("scene_thresholds is given but no scene detection is asked for (scene=None)")
         self.decimate, self.baseline, self.temporal, self.occ = decimate, baseline, temporal, occ
+        self.scene, self.scene_thresholds = scene, (_scene_thresholds(scene_thresholds) if scene is not None else None)
+        self.cuts = self.scene_m = None   # of the last run(): bool [T-1], float64 [T-1] with scene="sad"
         self.model, self.fmt_in, self.fmt_out, self.overlap, self.siting = model, fmt_in, fmt_out, bool(overlap), siting
         H, W = int(shape[0]), int(shape[1])
         self.shape = (H, W)
@@ -161,7 +182,7 @@ class ClipRunner:
             raise ValueError(f"expected uint8 [T >= 3, {self.in_bytes}], got {frames.dtype} {frames.shape}")
         T = frames.shape[0]
         self.h2d_bytes = self.d2h_bytes = self.frames_in = self.frames_out = 0
-        self.metrics = None
+        self.metrics = self.cuts = self.scene_m = None
         with torch.cuda.device(self.device), torch.no_grad():
             st = self._begin(T)
             for i in range(T):
@@ -173,6 +194,8 @@ class ClipRunner:
                     self._score(st, i - 2)
                 self._write_out(st, i - 2)
             self._drain(st)
+            if st.scene_buf is not None:
+                self._collect_scene(st, T)
             if st.layout is not None:
                 self.metrics = self._collect(st)
         return st.out
@@ -183,7 +206,14 @@ class ClipRunner:
         rows = sum(n for _, n, _ in layout.values()) if layout is not None else 0
         main = torch.cuda.current_stream(self.device)
         s_in, s_out = (self._s_in, self._s_out) if self.overlap else (main, main)
+        # scene="sad": the sums [T-1,2] float64 and the flags [T-1] int32, views of one buffer so that one copy brings both back
+        scene_buf = scene_rows = scene_flag = None
+        if self.scene is not None:
+            scene_buf = torch.empty(20 * (T - 1), dtype=torch.uint8, device=self.device)
+            scene_rows = scene_buf[:16 * (T - 1)].view(torch.float64).view(T - 1, 2)
+            scene_flag = scene_buf[16 * (T - 1):].view(torch.int32)
         return SimpleNamespace(
+            scene_buf=scene_buf, scene_sums=scene_rows, scene_flags=scene_flag,
             out=np.empty((T - 2, self.out_bytes), dtype=np.uint8), layout=layout,
             sums=None if layout is None else torch.empty((rows, 4), dtype=torch.float64, device=self.device),
             main=main, s_in=s_in, s_out=s_out, est=None, prev_est=None,
@@ -214,11 +244,22 @@ class ClipRunner:
             self._down(self._full, quantise=True, out=self._ring[i % 3])
         st.converted[a] = torch.cuda.Event()
         st.converted[a].record(st.main)
+        if st.scene_buf is not None and i >= 1:   # the pair (i - 1, i): its sums, then its flag against the pair before
+            row = st.scene_sums[i - 1:i]
+            scene_sums(self._ring[(i - 1) % 3], self._ring[i % 3], out=row)
+            scene_flags(row, st.scene_sums[i - 2] if i >= 2 else None, self.scene_thresholds, out=st.scene_flags[i - 1:i])
 
     def _forward(self, st, i: int) -> None:
         """The window of source frames i - 2 .. i through the model, the estimate fed back (as `run_item`)."""
-        x = torch.stack([self._ring[(i - 2) % 3], self._ring[(i - 1) % 3], self._ring[i % 3]])
-        st.est, _ = self.model(x, None, None, st.est, train=False)
+        if st.scene_buf is None:
+            x = torch.stack([self._ring[(i - 2) % 3], self._ring[(i - 1) % 3], self._ring[i % 3]])
+            st.est, _ = self.model(x, None, None, st.est, train=False)
+            return
+        # the window and the fed-back estimate under the flags of the pairs (i - 2, i - 1) and (i - 1, i), chosen on the device; the
+        # first window passes no estimate, as above: if its first pair is a cut, the model's "plane 7 = frame 0" picks the middle frame
+        x, est = scene_window(self._ring[(i - 2) % 3], self._ring[(i - 1) % 3], self._ring[i % 3], st.est,
+                              st.scene_flags[i - 2:i - 1], st.scene_flags[i - 1:i])
+        st.est, _ = self.model(x, None, None, est, train=False)
 
     def _score(self, st, j: int) -> None:
         """Output frame `j` against source frame j + 1, and the pair (j - 1, j); every launch writes its row of `st.sums`."""
@@ -287,5 +328,14 @@ class ClipRunner:
         metrics = {}
         for name, (row0, rows, kind) in st.layout.items():
             values = (psnr_ssim if kind == "frame" else ewarp)(host[row0:row0 + rows])
+            if kind == "pair" and self.cuts is not None:   # row r is scored along the flows between source frames r + 1 and r + 2
+                values[0][self.cuts[1:1 + rows]] = np.nan
             metrics.update((k, v) for k, v in zip(METRIC_KEYS[name], values) if k is not None)
         return metrics
+
+    def _collect_scene(self, st, T: int) -> None:
+        """`cuts` and `scene_m` from the run's scene buffer: one copy (it waits for the current stream)."""
+        host = st.scene_buf.cpu().numpy()
+        sums = host[:16 * (T - 1)].view(np.float64).reshape(T - 1, 2)
+        self.cuts = host[16 * (T - 1):].view(np.int32) != 0
+        self.scene_m = sums[:, 0] / sums[:, 1]

@@ -36,9 +36,10 @@ import torch
 
 from . import _lib as L
 from .clip_runner import ClipRunner, sums_layout  # noqa: F401
-from .frames import (METRIC_CHANNELS, METRIC_WHAT, RESIZE_KERNELS, RESIZE_MAX_TAPS, WARP_OCC, YUV_FORMATS, YUV_SITINGS,  # noqa: F401
-                     FrameResizer, ewarp, frame_metrics, frames_to_yuv, ingest_item_yuv, psnr_ssim, read_clip_yuv, resize_frames,
-                     resize_tables, ssim_window, truth_flows, warp_error, yuv_coefficients, yuv_frame_bytes, yuv_ingest, yuv_write)
+from .frames import (METRIC_CHANNELS, METRIC_WHAT, RESIZE_KERNELS, RESIZE_MAX_TAPS, SCENE_THRESHOLDS, WARP_OCC, YUV_FORMATS,  # noqa: F401
+                     YUV_SITINGS, FrameResizer, ewarp, frame_metrics, frames_to_yuv, ingest_item_yuv, psnr_ssim, read_clip_yuv,
+                     resize_frames, resize_tables, scene_cuts, scene_flags, scene_sums, scene_window, ssim_window, truth_flows, warp_error,
+                     yuv_coefficients, yuv_frame_bytes, yuv_ingest, yuv_write)
 
 
 # ------------------------------------------------------------------------------------------------ dataset
@@ -234,13 +235,16 @@ def run_c1(lr: int = 128, frames: int = 3, scale: int = 4, precision: str = "fp3
 
 
 def run_c1_yuv(pix_fmt: str, lr: int = 128, frames: int = 3, scale: int = 4, precision: str = "fp32", score: Optional[str] = None,
-               decimate: str = "nearest", baseline: Optional[str] = None, temporal: Optional[str] = None):
+               decimate: str = "nearest", baseline: Optional[str] = None, temporal: Optional[str] = None, scene: Optional[str] = None,
+               scene_thresholds=None, cut_at: Optional[int] = None):
     """Config C1 with a 4:2:0 boundary: the synthetic clip as `pix_fmt` frames on the host, streamed through `ClipRunner`
     (decimated by `scale`, super-resolved by `scale`).  -> (result line, output frames uint8 [T-2, frame_bytes] on the host).
     `score`: "rgb" | "y": the line also carries the per-frame PSNR / SSIM against the synthetic HR clip.  `decimate` / `baseline`: as
     `ClipRunner`'s; with a baseline the line carries its mean PSNR / SSIM beside the estimate's and `psnr_gain`, their difference in dB; with
     `temporal` the clip means of E_warp of the estimate, of the truth frames (and of the baseline) and of the valid share (E_warp over the
-    pairs that have valid pixels; null where there is none, or no pair: a clip of three frames)."""
+    pairs that have valid pixels; null where there is none, or no pair: a clip of three frames).  `cut_at` = K: the clip's frames from K
+    on come from a second seed, a scene cut between the frames K - 1 and K.  `scene` / `scene_thresholds`: as `ClipRunner`'s; the line
+    then carries `cuts`, the indices i of the pairs (i, i + 1) found to be cuts, and `scene_m`, the mean absolute luma difference per pair."""
     import time
     from . import VSR
     from .weights import fill_module_
@@ -250,9 +254,13 @@ def run_c1_yuv(pix_fmt: str, lr: int = 128, frames: int = 3, scale: int = 4, pre
     model = fill_module_(VSR(upscale_factor=S).eval(), seed=0).to(dev)
     model.precision = model.model.precision = precision
     video = synthetic_video(frames, S * lr, S * lr)
+    if cut_at is not None:
+        if not 0 < cut_at < frames:
+            raise ValueError(f"cut_at must lie inside the clip of {frames} frames, got {cut_at}")
+        video[cut_at:] = synthetic_video(frames, S * lr, S * lr, seed=4321)[cut_at:]
     clip = frames_to_yuv(torch.from_numpy(video).to(dev).float(), pix_fmt).cpu().numpy()
     runner = ClipRunner(model, (S * lr, S * lr), pix_fmt, pix_fmt, scale_down=S, score=score, decimate=decimate, baseline=baseline,
-                        temporal=temporal)
+                        temporal=temporal, scene=scene, scene_thresholds=scene_thresholds)
     runner.run(clip)                                                      # warm-up (packing, allocator)
     t0 = time.perf_counter()
     out = runner.run(clip)
@@ -277,6 +285,11 @@ def run_c1_yuv(pix_fmt: str, lr: int = 128, frames: int = 3, scale: int = 4, pre
         line.update(temporal=temporal, ewarp=mean(m["ewarp"]), ewarp_truth=mean(m["ewarp_truth"]), valid_share=mean(m["valid_share"]))
         if baseline is not None:
             line.update(ewarp_baseline=mean(m["ewarp_baseline"]))
+    if cut_at is not None:
+        line.update(cut_at=cut_at)
+    if scene is not None:
+        line.update(scene=scene, scene_thresholds=list(runner.scene_thresholds), cuts=[int(i) for i in np.flatnonzero(runner.cuts)],
+                    scene_m=[round(float(v), 4) for v in runner.scene_m])
     return line, out
 
 
@@ -324,6 +337,14 @@ def main(argv=None):
                     help="with --score: also score the bicubic enlargement of the LR frame; the line carries both means and psnr_gain")
     ap.add_argument("--temporal", default=None, choices=["warp"],
                     help="with --score: also the flow-warped error between consecutive output frames (E_warp); the line carries the clip means")
+    ap.add_argument("--scene", default=None, choices=["sad"],
+                    help="with --pix-fmt: find scene cuts on the device (mean absolute luma difference of consecutive LR frames) and keep the "
+                         "other scene out of the window and of the fed-back estimate; the line carries the cuts found")
+    ap.add_argument("--scene-thresholds", type=float, nargs=2, default=None, metavar=("T_ABS", "RATIO"),
+                    help="with --scene: a pair is a cut where its mean difference reaches T_ABS (0..255 luma scale) and RATIO times the "
+                         "previous pair's (default 15 2; not validated on real video)")
+    ap.add_argument("--cut-at", type=int, default=None, metavar="K",
+                    help="with --pix-fmt: the synthetic clip's frames from K on come from a second seed (a scene cut before frame K)")
     ap.add_argument("--train-steps", type=int, default=None, metavar="K",
                     help="after the no-grad windows: K train steps on the last window (optim.Adam); the line carries the loss per step")
     ap.add_argument("--max-grad-norm", type=float, default=None, metavar="X",
@@ -341,6 +362,12 @@ def main(argv=None):
         ap.error("--baseline needs --score (it is scored beside the estimate)")
     if args.temporal is not None and args.score is None:
         ap.error("--temporal needs --score (it is scored beside the estimate)")
+    if args.scene is not None and args.pix_fmt is None:
+        ap.error("--scene needs --pix-fmt (the streamed clip runner watches its frames)")
+    if args.scene_thresholds is not None and args.scene is None:
+        ap.error("--scene-thresholds needs --scene")
+    if args.cut_at is not None and (args.pix_fmt is None or not 0 < args.cut_at < args.frames):
+        ap.error("--cut-at needs --pix-fmt and a frame index inside the clip (0 < K < --frames)")
     if args.max_grad_norm is not None and args.train_steps is None:
         ap.error("--max-grad-norm needs --train-steps")
     if args.train_steps is not None:
@@ -350,7 +377,7 @@ def main(argv=None):
                                loss_path=args.loss_path or "reference")
     elif args.pix_fmt is not None:
         line, _ = run_c1_yuv(args.pix_fmt, args.lr, args.frames, args.scale, args.precision, args.score, args.decimate, args.baseline,
-                             args.temporal)
+                             args.temporal, args.scene, args.scene_thresholds, args.cut_at)
     else:
         line, _, _, _ = run_c1(args.lr, args.frames, args.scale, args.precision)
     print(json.dumps(line))

@@ -1,4 +1,4 @@
-"""Frames in, out, resampled and scored on the device: the Python side of four side libraries, one section each.
+"""Frames in, out, resampled, scored and watched for scene cuts on the device: the Python side of five side libraries, one section each.
 
     read_clip_yuv / ingest_item_yuv / frames_to_yuv     ingest, and write-out for what decoders emit: packed Y'CbCr 4:2:0 frames
                             (yuv420p, nv12, yuv420p10le, p010le), converted on the device (include/vsr_hip_yuv.h); the matrix
@@ -11,8 +11,11 @@
     truth_flows / warp_error / ewarp   the temporal warping error on the device (include/vsr_hip_warp.h): forward and backward FlowNet2
                             flows between ground-truth frames, frame t + 1 warped back onto frame t and the squared difference summed
                             over the pixels that are not occluded, in float64, and the host step that forms E_warp from the sums
+    scene_sums / scene_flags / scene_window / scene_cuts   scene cuts on the device (include/vsr_hip_scene.h): the absolute luma difference
+                            of consecutive LR frames summed per pair, the cut rule on the sums as device flags, the 3-frame window and
+                            the fed-back estimate composed under two flags, and the host step that applies the same rule to the sums
 
-`clip_runner.ClipRunner` streams a clip through all four; `driver` imports every public name here, so `driver.frame_metrics` and the rest
+`clip_runner.ClipRunner` streams a clip through all five; `driver` imports every public name here, so `driver.frame_metrics` and the rest
 resolve as before.  Transfer functions and 4:2:2 / 4:4:4 stay out.
 """
 from __future__ import annotations
@@ -446,3 +449,110 @@ def ewarp(sums) -> Tuple[np.ndarray, np.ndarray]:
     on = s[:, 2] > 0
     e[on] = s[on, 0] / s[on, 1] / 255.0 ** 2
     return e, s[:, 2] / s[:, 3]
+
+
+# ------------------------------------------------------------------------------------------------ scene cuts
+SCENE_THRESHOLDS = (15.0, 2.0)   # {t_abs on the 0..255 luma scale, ratio against the pair before}: this project's choice, not validated on real video
+
+
+def _scene_thresholds(thresholds) -> Tuple[float, float]:
+    """(t_abs, ratio) as two floats, default `SCENE_THRESHOLDS`; both finite and not negative (what vsr_scene_decide accepts)."""
+    t = np.asarray(SCENE_THRESHOLDS if thresholds is None else thresholds, dtype=np.float64).reshape(-1)
+    if t.size != 2 or not np.isfinite(t).all() or (t < 0).any():
+        raise ValueError(f"scene thresholds are (t_abs, ratio), both finite and not negative, got {thresholds!r}")
+    return float(t[0]), float(t[1])
+
+
+@L.on_device
+def scene_sums(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None, luma4=None) -> torch.Tensor:
+    """float32 RGB frames `a`, `b` ([h,w,3] or [P,h,w,3], 0..255) -> the device tensor [P,2] float64 of {sad, n} per pair
+    (vsr_scene_pair_sums, include/vsr_hip_scene.h): the absolute difference of the two frames' 8-bit luma codes summed over the pixels,
+    and their count.  Nothing is synchronised; `scene_flags` is the device step on the sums, `scene_cuts` the host step.  `luma4`: four
+    float32 {a0, a1, a2, o}, default the BT.601 luma of `frame_metrics`; `out`: write the sums there ([P,2] float64, rows of a larger
+    tensor will do)."""
+    import ctypes
+    fa, fb = _frame_pair(a, b, "P")
+    P, h, w = int(fa.shape[0]), int(fa.shape[1]), int(fa.shape[2])
+    luma4 = _luma4("y", "bt601", False) if luma4 is None else np.ascontiguousarray(np.asarray(luma4, dtype=np.float32).reshape(4))
+    M = L.load_scene()
+    pa, pb = L.dptr(fa), L.dptr(fb)   # (raises on CPU tensors and on anything but float32)
+    if fb.device != fa.device:
+        raise ValueError("the two tensors live on different devices")
+    if out is None:
+        out = torch.empty((P, 2), dtype=torch.float64, device=fa.device)
+    elif tuple(out.shape) != (P, 2) or out.device != fa.device:
+        raise ValueError(f"out must be float64 {(P, 2)} on {fa.device}, got {tuple(out.shape)} on {out.device}")
+    ws = torch.empty(int(M.vsr_scene_ws_bytes(P, h, w)), dtype=torch.uint8, device=fa.device)
+    L.check(M.vsr_scene_pair_sums(pa, pb, P, h, w, luma4.ctypes.data_as(ctypes.c_void_p), L.dptr(out, torch.float64), L.dptr(ws, torch.uint8),
+                                  L.stream()), "scene_pair_sums", lib=M)
+    return out
+
+
+@L.on_device
+def scene_flags(sums: torch.Tensor, prev: Optional[torch.Tensor] = None, thresholds=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The cut rule on the device (vsr_scene_decide): `sums` [P,2] float64 as `scene_sums` writes them -> int32 [P], 1 where pair p is a
+    cut: m_p = sad_p / n_p, flag_p = m_p >= t_abs and m_p >= ratio * m_{p-1}; for p = 0 the pair before is `prev` (two float64 {sad, n} on
+    the device, e.g. the row above in a larger tensor), m = 0 without it.  `thresholds`: (t_abs, ratio), default `SCENE_THRESHOLDS`; `out`:
+    write the flags there (int32 [P], elements of a larger tensor will do).  Nothing is synchronised."""
+    if sums.dim() != 2 or sums.shape[1] != 2:
+        raise ValueError(f"expected float64 sums [P,2], got {tuple(sums.shape)}")
+    P = int(sums.shape[0])
+    t_abs, ratio = _scene_thresholds(thresholds)
+    if prev is not None and (prev.numel() != 2 or prev.device != sums.device):
+        raise ValueError(f"prev must be two float64 values on {sums.device}, got {tuple(prev.shape)} on {prev.device}")
+    M = L.load_scene()
+    ps = L.dptr(sums, torch.float64)
+    if out is None:
+        out = torch.empty((P,), dtype=torch.int32, device=sums.device)
+    elif tuple(out.shape) != (P,) or out.device != sums.device:
+        raise ValueError(f"out must be int32 {(P,)} on {sums.device}, got {tuple(out.shape)} on {out.device}")
+    L.check(M.vsr_scene_decide(ps, P, L.optr(prev, torch.float64), t_abs, ratio, L.dptr(out, torch.int32), L.stream()), "scene_decide", lib=M)
+    return out
+
+
+@L.on_device
+def scene_window(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor, prev_est: Optional[torch.Tensor] = None,
+                 flag_ab: Optional[torch.Tensor] = None, flag_bc: Optional[torch.Tensor] = None):
+    """The window of three consecutive LR frames `a`, `b`, `c` (float32 [h,w,3]) and the fed-back estimate under two device flags
+    (vsr_scene_window; one int32 element each, None: not set) -> (x [3,h,w,3], est [1,h,w,3] | None): x = (flag_ab ? b : a, b,
+    flag_bc ? b : c); est = b where flag_ab is set, else `prev_est` ([1,H,W,3] or [H,W,3], H = S h, W = S w) at its pixels (y S, x S):
+    the nearest resize VSR.forward performs; None without `prev_est` (the first window of a run).  Bit copies throughout.  Both results are
+    freshly allocated on every call: `VSR.temporal_cache` keys on storage identity and version, which a raw-pointer write into reused
+    storage would not change.  Nothing is synchronised."""
+    if a.dim() != 3 or a.shape[-1] != 3 or tuple(b.shape) != tuple(a.shape) or tuple(c.shape) != tuple(a.shape):
+        raise ValueError(f"expected three float32 frames of one shape [h,w,3], got {tuple(a.shape)}, {tuple(b.shape)} and {tuple(c.shape)}")
+    h, w = int(a.shape[0]), int(a.shape[1])
+    H = W = 0
+    if prev_est is not None:
+        if prev_est.dim() not in (3, 4) or prev_est.shape[-1] != 3 or (prev_est.dim() == 4 and prev_est.shape[0] != 1):
+            raise ValueError(f"prev_est must be float32 [1,H,W,3] or [H,W,3], got {tuple(prev_est.shape)}")
+        prev_est = prev_est.detach().to(torch.float32).contiguous()   # (the model's output is a permuted view: the copy VSR.forward makes)
+        H, W = int(prev_est.shape[-3]), int(prev_est.shape[-2])
+        if H % h or W % w or H // h != W // w:
+            raise ValueError(f"prev_est of {H} x {W} is no integer multiple (one factor both ways) of the frames of {h} x {w}")
+    for name, f in (("flag_ab", flag_ab), ("flag_bc", flag_bc)):
+        if f is not None and f.numel() != 1:
+            raise ValueError(f"{name} must be one int32 element on the device, got {tuple(f.shape)}")
+    M = L.load_scene()
+    pa, pb, pc = L.dptr(a.detach()), L.dptr(b.detach()), L.dptr(c.detach())   # (raises on CPU tensors, other dtypes and strided views)
+    if any(t is not None and t.device != a.device for t in (b, c, prev_est, flag_ab, flag_bc)):
+        raise ValueError("the frames, the estimate and the flags live on different devices")
+    x = torch.empty((3, h, w, 3), dtype=torch.float32, device=a.device)
+    est = torch.empty((1, h, w, 3), dtype=torch.float32, device=a.device) if prev_est is not None else None
+    L.check(M.vsr_scene_window(pa, pb, pc, L.optr(prev_est), H, W, L.optr(flag_ab, torch.int32), L.optr(flag_bc, torch.int32), L.dptr(x),
+                               L.optr(est), h, w, L.stream()), "scene_window", lib=M)
+    return x, est
+
+
+def scene_cuts(sums, thresholds=None) -> Tuple[np.ndarray, np.ndarray]:
+    """The host step after `scene_sums`: sums [P,2] of CONSECUTIVE pairs (a tensor, copied to the host here, or an array) -> (cuts bool
+    [P], m float64 [P]), the rule of `scene_flags` with no pair before the first: m = sad / n, cut_p = m_p >= t_abs and
+    m_p >= ratio * m_{p-1} (m_{-1} = 0)."""
+    t_abs, ratio = _scene_thresholds(thresholds)
+    s = sums.detach().cpu().numpy() if isinstance(sums, torch.Tensor) else np.asarray(sums)
+    s = np.asarray(s, dtype=np.float64).reshape(-1, 2)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        m = s[:, 0] / s[:, 1]
+        m_prev = np.concatenate([[0.0], m[:-1]])
+        cuts = (m >= t_abs) & (m >= ratio * m_prev)
+    return cuts, m
