@@ -1,0 +1,96 @@
+"""Cases of the one-launch inception block (tests/test_gpu_hg_inception.py) that need no GPU: the block signatures, the exact and the
+Gaussian operands, and their float64 references.  tests/test_hgi_cases_helper.py checks on the CPU that every exact case stays inside
+the reference's own budget."""
+import functools
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+import _exact as X
+from video_super_resolution_amd.depth import _A, _B, _C, _D, _E, _F, _G
+
+SIGS = {"A": _A, "B": _B, "C": _C, "D": _D, "E": _E, "F": _F, "G": _G}
+# 1x1, 3x5, 7x9: smaller than the 11x11 kernel; 9x17: one 8 x 16 tile plus ragged edges; 17x33: several ragged tiles
+SIZES = [(1, 1), (3, 5), (7, 9), (9, 17), (17, 33)]
+BIG_SIZES = [(33, 60), (67, 120)]
+NREF = 3
+
+
+def parts(node):
+    _, cin, o0, *rest = node
+    return cin, o0, rest
+
+
+# ---------------------------------------------------------------------------------------------------------------- exact
+@functools.lru_cache(maxsize=None)
+def exact_weights(name):
+    """Sparse integer weights: about 6 non-zero taps per 1x1 row and 60 per k x k row keep every mid value and every output a small
+    integer (an fp16 value; the references check it) while every tap of every 32-channel chunk carries weight in some row; biases are
+    non-zero integers."""
+    cin, o0, rest = parts(SIGS[name])
+    rs = np.random.RandomState(sum(map(ord, name)))
+
+    def bias(n):
+        return torch.from_numpy((rs.randint(1, 3, size=n) * (rs.randint(0, 2, size=n) * 2 - 1)).astype(np.float64))
+
+    w0 = X.sparse_weights(rs, (o0, cin, 1, 1), density=6.0 / cin)
+    branches = []
+    for mid, k, out in rest:
+        branches.append((X.sparse_weights(rs, (mid, cin, 1, 1), density=6.0 / cin), bias(mid),
+                         X.sparse_weights(rs, (out, mid, k, k), density=60.0 / (mid * k * k)), bias(out)))
+    return (w0, bias(o0)), branches
+
+
+def exact_input(name, hw):
+    """[NREF,cin,H,W] integers in -3..3, float64."""
+    return X.ints(np.random.RandomState(hw[0] * 100 + hw[1]), (NREF, parts(SIGS[name])[0]) + tuple(hw))
+
+
+def exact_ref(wts, x):
+    """float64: cat(relu(1x1) | relu(k x k(relu(1x1))) x 3), every sum inside the float32 budget, every mid and output an fp16 value."""
+    (w0, b0), branches = wts
+    outs = [F.relu(X.conv_ref(x, w0, b0, what="plain 1x1", store=torch.float16))]
+    for j, (w1, b1, wk, bk) in enumerate(branches):
+        mid = F.relu(X.conv_ref(x, w1, b1, what=f"branch {j} 1x1", store=torch.float16))
+        k = wk.shape[-1]
+        outs.append(F.relu(X.conv_ref(mid, wk, bk, padding=(k - 1) // 2, what=f"branch {j} {k}x{k}", store=torch.float16)))
+        if float((mid != 0).double().mean()) <= 0.1:
+            raise X.BudgetError(f"branch {j}: degenerate mid map")
+    y = torch.cat(outs, 1)
+    if float((y != 0).double().mean()) <= 0.1:
+        raise X.BudgetError("degenerate output")
+    return y
+
+
+# ---------------------------------------------------------------------------------------------------------------- Gaussian
+@functools.lru_cache(maxsize=None)
+def gauss_weights(name):
+    cin, o0, rest = parts(SIGS[name])
+    g = torch.Generator().manual_seed(sum(map(ord, name)) + 7)
+
+    def w(co, ci, k):
+        return torch.randn((co, ci, k, k), generator=g, dtype=torch.float64) * (2.0 / (ci * k * k)) ** 0.5
+
+    def b(n):
+        return torch.randn(n, generator=g, dtype=torch.float64) * 0.25
+
+    return (w(o0, cin, 1), b(o0)), [(w(mid, cin, 1), b(mid), w(out, mid, k), b(out)) for mid, k, out in rest]
+
+
+def gauss_ref(wts, x16):
+    """float64 with the kernels' operands: weights rounded to fp16, biases to float32, the mid maps rounded to fp16 after ReLU."""
+    X._threads()
+    (w0, b0), branches = wts
+
+    def h(w):
+        return w.to(torch.float16).double()
+
+    def f(b):
+        return b.to(torch.float32).double()
+
+    outs = [F.relu(F.conv2d(x16, h(w0), f(b0)))]
+    for w1, b1, wk, bk in branches:
+        mid = F.relu(F.conv2d(x16, h(w1), f(b1))).to(torch.float16).double()
+        outs.append(F.relu(F.conv2d(mid, h(wk), f(bk), padding=(wk.shape[-1] - 1) // 2)))
+    return torch.cat(outs, 1)

@@ -101,8 +101,57 @@ class _Inception:
             conv(buf, out=buf, out_coff=ooff, in_coff=moff)
         return buf, self.M, self.ctot
 
+    # The whole block in ONE launch on the small maps of the inner levels (csrc/conv_hg_inception.hip, libvsr_hip_hgi.so): the mid
+    # maps stay in LDS, the result is a dense [N,H,W,ctot] map.  VSR_HG_INCEPTION=0: the four launches everywhere.
+    fused_small = os.environ.get("VSR_HG_INCEPTION", "1") != "0"
+    # (mid, (k1, k2, k3), cout, o0) the library has a kernel for: depth.py's _A / _E, _B / _C, _D, _F, _G
+    FUSED_SIGS = {(32, (3, 5, 7), 32, 32), (32, (3, 5, 7), 64, 64), (64, (3, 7, 11), 64, 64), (64, (3, 7, 11), 32, 32), (64, (3, 5, 7), 32, 32)}
+    # Where the one launch beat the launches it replaces at BOTH N = 1 and N = 4 by more than the rounds' spread
+    # (profiles/hg_inception_time.txt; LAB_NOTES.md, "Hourglass inception blocks in one launch"): every signature up to 67 x 120; above
+    # that, up to 135 x 240, _B alone -- there the patch kernels of the four-launch path run at twice the one launch's rate at N = 4
+    FUSED_SMALL_PIXELS = 67 * 120
+    FUSED_MAX_PIXELS = 135 * 240
+    FUSED_SIGS_TO_MAX = {(128, 32, (3, 5, 7), 64, 64)}
+
+    @staticmethod
+    def fused_rule(sig, H, W):
+        """Pure rule of (block signature, H, W): does the one-launch kernel take this block?  sig = (cin, mid, (k1, k2, k3), cout, o0)
+        with one mid and one cout for the three k x k branches, as `signature()` gives it; never a function of N."""
+        cin, mid, ks, cout, o0 = sig
+        if cin not in (128, 256) or (mid, ks, cout, o0) not in _Inception.FUSED_SIGS or H <= 0 or W <= 0:
+            return False
+        return H * W <= _Inception.FUSED_SMALL_PIXELS or (H * W <= _Inception.FUSED_MAX_PIXELS and tuple(sig) in _Inception.FUSED_SIGS_TO_MAX)
+
+    def signature(self):
+        """(cin, mid, (k1, k2, k3), cout, o0), or None when the branches differ in mid or cout width."""
+        mids = {conv.cin_pad for conv, _, _ in self.kconvs}
+        outs = {conv.cout for conv, _, _ in self.kconvs}
+        if len(mids) != 1 or len(outs) != 1 or self.M != 3 * min(mids):
+            return None
+        return self.cin, min(mids), tuple(conv.kh for conv, _, _ in self.kconvs), min(outs), self.o0
+
+    def fused(self, x, in_coff):
+        """The block in one launch -> (dense map [N,H,W,ctot], 0, ctot)."""
+        N, H, W, in_ld = x.shape
+        cin, mid, ks, cout, o0 = self.signature()
+        out = torch.empty((N, H, W, self.ctot), dtype=torch.float16, device=x.device)
+        lib = L.load_hgi()
+        args = []
+        for conv, _, _ in self.kconvs:
+            args += [L.dptr(conv.w, torch.float16), L.dptr(conv.b), conv.kh]
+        L.check(lib.vsr_hgi_inception_f16(L.dptr(x, torch.float16), in_ld, in_coff, cin, L.dptr(self.first.w, torch.float16), L.dptr(self.first.b),
+                                          self.first.cout_pad, mid, o0, *args, cout, L.dptr(out, torch.float16), self.ctot, N, H, W, L.stream()),
+                "hgi_inception", lib=lib)
+        if L.ROUTES.enabled:
+            L.ROUTES.note_as(f"inception N{N} {H}x{W} c{cin}->{self.ctot} mid{mid}", "hg_inception<%d,%d,%d>" % ks)
+        return out, 0, self.ctot
+
     def __call__(self, x, in_coff):
         N, H, W, _ = x.shape
+        if self.fused_small:
+            sig = self.signature()
+            if sig is not None and self.ctot % 32 == 0 and self.fused_rule(sig, H, W):
+                return self.fused(x, in_coff)
         buf = torch.empty((N, H, W, self.width), dtype=torch.float16, device=x.device)
         if self.width != self.M + self.ctot:
             buf[..., self.M + self.ctot:] = 0
