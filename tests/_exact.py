@@ -20,7 +20,10 @@ This module holds
 The sign of a zero is not compared (`-0.0 == +0.0`): `0 * negative` in a PReLU with slope 0 is -0.0 in one formulation and +0.0 in
 another, and no consumer can tell.  Everything else is compared as bits.
 
-What these cases cannot see: rounding behaviour (the Gaussian-operand tests keep covering it) and overflow to infinity.
+What these cases cannot see is rounding and overflow to infinity: no stored value ever needs either.  The ROUNDING cases at the end of
+this module (`round_f16`, `act_round_ref`, `prelu_f16_ref`, `check_rounds`, the `*_round_ref` references; tests/_round_cases.py,
+tests/test_gpu_rounding.py) keep the float32 budget, make the sums 13 to 15 bits wide and require the one round-to-nearest-even
+fp16 value of each, again bit for bit.
 """
 import numpy as np
 import torch
@@ -109,11 +112,36 @@ def check_live(t, what, min_nonzero=0.5, min_distinct=200, both_signs=True):
 
 
 # ---------------------------------------------------------------------------------------------------------------- references
-def conv_ref(x, w, b=None, stride=1, padding=0, what="conv", store=None):
-    """float64 conv2d of exact operands (all float64 tensors), its float32 budget checked; `store`: a dtype the result must fit."""
+def local_granularity(x, w, stride=1, padding=0):
+    """Per OUTPUT of conv2d(x, w): the granule of the finest input element that a non-zero weight of that output reads (1.0 where all of
+    them are integers or the output reads nothing), times granularity(w).  A map whose small values carry fine granules beside large
+    coarse ones (a rounded map behind a slope such as fp16(0.2)) has a global granularity far below what any one sum needs."""
+    nz = (w != 0).to(torch.float64)
+    g = torch.ones_like(F.conv2d(x, nz, None, stride=stride, padding=padding))
+    step = 1.0
+    for _ in range(40):
+        need = torch.remainder(x, step) != 0          # elements finer than `step`
+        if not bool(need.any()):
+            break
+        step /= 2
+        g = torch.where(F.conv2d(need.to(torch.float64), nz, None, stride=stride, padding=padding) > 0, torch.full_like(g, step), g)
+    return g * granularity(w)
+
+
+def conv_ref(x, w, b=None, stride=1, padding=0, what="conv", store=None, local=False):
+    """float64 conv2d of exact operands (all float64 tensors), its float32 budget checked; `store`: a dtype the result must fit.
+    `local`: the budget per output on `local_granularity` instead of the granularity of the whole map."""
     _threads()
     y = F.conv2d(x, w, b, stride=stride, padding=padding)
     a = F.conv2d(x.abs(), w.abs(), None if b is None else b.abs(), stride=stride, padding=padding)
+    if local:
+        g = local_granularity(x, w, stride, padding)
+        g = g if b is None else torch.minimum(g, torch.full_like(g, granularity(b)))
+        bad = a >= (2.0 ** 24) * g
+        if bool(bad.any()):
+            c = _coord(bad)
+            raise BudgetError(f"{what}: sum |x||w| + |b| = {float(a[c])} at {c} is not below 2^24 * {float(g[c])}: partial sums may round in float32")
+        return y if store is None else check_storable(y, store, what)
     check_sum_budget(a, granularity(x) * granularity(w) if b is None else min(granularity(x) * granularity(w), granularity(b)), what)
     if store is not None:
         check_storable(y, store, what)
@@ -141,10 +169,8 @@ def leaky_tenth_f16(v):
     (csrc/conv_igemm.hip `fmaxf(x, 0) + nslope * fminf(x, 0)` / `t >= 0 ? t : t * p.slope`, csrc/conv_tile.hip:187, conv_patch.h:36;
     csrc/flow_ops.hip k_corr_mfma `s > 0 ? s : 0.1f * s`): the exact sum (a float32 value by the budget), ONE float32 multiply by
     float32(0.1) on the negative side -- for a negative x the other summand is +0, so a fused multiply-add gives the same --
-    and one round-to-nearest-even to fp16.  -> float64 tensor of fp16 values."""
-    x = check_storable(v, torch.float32, "leaky 0.1 input").to(torch.float32)
-    y = torch.where(x >= 0, x, x * torch.tensor(0.1, dtype=torch.float32))
-    return y.to(torch.float16).to(torch.float64)
+    and one round-to-nearest-even to fp16 (`act_round_ref` with slope 0.1).  -> float64 tensor of fp16 values."""
+    return act_round_ref(v, 2, 0.1)
 
 
 def leaky_tenth_f32(v):
@@ -169,9 +195,10 @@ def act_ref(v, act, slope=0.1, store=torch.float16):
 def stage_ref(a, up_w, up_b, up_a, dt_w, dt_b, dt_a, dn_w, dn_b, dn_a, S, live=True, min_distinct=200):
     """One FeedbackBlock stage in float64: ConvTranspose2d(k S+4, s S, p 2) -> PReLU -> the live 32-column slice of the downtran 1x1
     -> PReLU -> Conv2d(k S+4, s S, p 2) -> PReLU.  a [N,32,h,w]; up_w [32,32,k,k] (in, out); dt_w [32,32] (out, in: the slice);
-    dn_w [32,32,k,k] (out, in).  The fused kernels convert each sum to fp16 FIRST and apply PReLU on packed fp16 values with an fp16
-    slope (csrc/sr_f16_common.h), so each of the three sums and each of the three PReLU results is checked to be an fp16 value, and
-    the slopes too.  -> dict(hr, t, out) of float64 maps."""
+    dn_w [32,32,k,k] (out, in).  The fused kernels convert the two inner sums to fp16 FIRST and apply PReLU on packed fp16 values with an
+    fp16 slope (csrc/sr_f16_common.h); the output sum takes its PReLU in float32 and is converted behind it.  In the exact regime both
+    orders agree: each of the three sums and each of the three PReLU results is checked to be an fp16 value, and the slopes too
+    (`stage_round_ref` tells the orders apart).  -> dict(hr, t, out) of float64 maps."""
     for s in (up_a, dt_a, dn_a):
         check_storable(torch.tensor([float(s)], dtype=torch.float64), torch.float16, "PReLU slope")
     k = S + 4
@@ -470,6 +497,258 @@ def nearest_differs_from_rational(n_in, n_out):
     """True where the float32 operator's source differs from floor(dst * n_in / n_out) in integers, at one destination or more."""
     exact = (torch.arange(n_out, dtype=torch.int64) * n_in) // n_out
     return bool((nearest_sources(n_in, n_out) != exact).any())
+
+
+# ---------------------------------------------------------------------------------------------------------------- rounding cases
+# The float32 budget above, WITHOUT the requirement that stored values are fp16 values: the float32 sum is still exact in any order,
+# and what a kernel stores is the one round-to-nearest-even of it.  One right answer per element, no tolerance.
+def _f16_parts(t, what="value"):
+    """|t| = (q + rem / 2^s) * 2^qexp with integers q, 0 <= rem < 2^s, where 2^qexp is the fp16 spacing at |t| (2^(e-11) for a
+    normal result, 2^-24 below 2^-14: gradual underflow).  t: float64 tensor of finite float32 values (checked), so that the
+    significand M = |t| / 2^(e-24) is an integer below 2^24.  -> (q, rem, half = 2^(s-1), qexp), int64 tensors."""
+    t = torch.as_tensor(t, dtype=torch.float64)
+    if not bool(torch.isfinite(t).all()):
+        raise BudgetError(f"{what}: not finite at {_coord(~torch.isfinite(t))}")
+    check_storable(t, torch.float32, what)
+    mant, e = torch.frexp(t.abs())                      # |t| = mant * 2^e, mant in [0.5, 1) (0, 0 for zero)
+    m = mant * 2.0 ** 24
+    mi = m.to(torch.int64)
+    if bool((mi.to(torch.float64) != m).any()):
+        raise BudgetError(f"{what}: {float(t[_coord(mi.to(torch.float64) != m)])!r} has more than 24 significant bits")
+    e = e.to(torch.int64)
+    qexp = torch.clamp(e - 11, min=-24)
+    s = torch.clamp(qexp - (e - 24), max=40)            # 13 for a normal result; beyond 25 everything is remainder below the half
+    q = mi >> s
+    rem = mi - (q << s)
+    half = torch.ones_like(s) << (s - 1)
+    return q, rem, half, qexp
+
+
+def _round_parts(t, up_rule, overflow, what):
+    q, rem, half, qexp = _f16_parts(t, what)
+    n = q + up_rule(q, rem, half).to(torch.int64)
+    r = n.to(torch.float64) * torch.pow(torch.full_like(n, 2.0, dtype=torch.float64), qexp.to(torch.float64))
+    r = torch.where(r >= 65536.0, torch.full_like(r, overflow), r)
+    return torch.where(torch.as_tensor(t, dtype=torch.float64) < 0, -r, r)
+
+
+def round_f16(t, what="round_f16 input"):
+    """The fp16 value nearest to each element, ties to the even significand (IEEE 754 roundTiesToEven), as float64: in integer
+    arithmetic on the 24-bit significand (frexp, shift, half-to-even on the remainder), independent of any library cast.
+    Magnitudes of 65520 and above give +-inf; below 2^-14 the spacing stays 2^-24 (gradual underflow).  t: float64 tensor whose
+    elements are finite float32 values (checked)."""
+    return _round_parts(t, lambda q, rem, half: (rem > half) | ((rem == half) & ((q & 1) == 1)), float("inf"), what)
+
+
+def round_f16_alt(t, mode):
+    """A WRONG fp16 rounding, to prove that a case tells it from `round_f16` -- never a reference.  "rtz": truncation (what a
+    v_cvt_pkrtz-style conversion does; a finite overflow stays 65504); "away": ties away from zero."""
+    if mode == "rtz":
+        return torch.clamp(_round_parts(t, lambda q, rem, half: torch.zeros_like(q, dtype=torch.bool), 65504.0, "round_f16_alt input"), -65504.0, 65504.0)
+    if mode == "away":
+        return _round_parts(t, lambda q, rem, half: rem >= half, float("inf"), "round_f16_alt input")
+    raise ValueError(mode)
+
+
+def rounding_profile(pre):
+    """Masks over `pre` (float64 tensor of float32 values): `inexact` (not an fp16 value), `tie` (exactly between two fp16 values),
+    `tie_up` / `tie_down` (the tie goes to the neighbour of larger / smaller magnitude under nearest-even)."""
+    q, rem, half, _ = _f16_parts(pre, "pre-rounding value")
+    tie = rem == half
+    return dict(inexact=rem != 0, tie=tie, tie_up=tie & ((q & 1) == 1), tie_down=tie & ((q & 1) == 0))
+
+
+def check_rounds(pre, what, pool=None, min_inexact=0.25, min_ties=0.05, min_each=16):
+    """The liveness condition of a rounding case, on the values about to be rounded to fp16: at least 25 % are not fp16 values, at
+    least 5 % are exact ties, at least 16 ties resolve upward in magnitude and at least 16 downward, and no magnitude reaches 65520
+    (overflow has its own cases).  A map below 512 elements cannot meet the counts alone: it is appended to `pool` (a list) instead,
+    and the test calls `check_rounds_pool(pool, what)` once over all of its cases.  Conditions on the INPUTS, not tolerances."""
+    pre = torch.as_tensor(pre, dtype=torch.float64)
+    if bool((pre.abs() >= 65520.0).any()):
+        raise BudgetError(f"{what}: |{float(pre[_coord(pre.abs() >= 65520.0)])}| at {_coord(pre.abs() >= 65520.0)} overflows fp16")
+    if pool is not None:
+        pool.append(pre.reshape(-1))
+    if pre.numel() < 512:
+        if pool is None:
+            raise BudgetError(f"{what}: {pre.numel()} elements are too few for the rounding counts; pool the cases of the test")
+        return pre
+    p = rounding_profile(pre)
+    n = pre.numel()
+    fi, ft, nu, nd = int(p["inexact"].sum()) / n, int(p["tie"].sum()) / n, int(p["tie_up"].sum()), int(p["tie_down"].sum())
+    if fi < min_inexact or ft < min_ties or nu < min_each or nd < min_each:
+        raise BudgetError(f"{what}: {fi:.1%} of the values need rounding (minimum {min_inexact:.0%}), {ft:.1%} are ties (minimum {min_ties:.0%}), "
+                          f"{nu} ties go up and {nd} down (minimum {min_each} each)")
+    return pre
+
+
+def check_rounds_pool(pool, what):
+    """`check_rounds` over the small maps a test collected; the pool as a whole has to reach 512 elements."""
+    allv = torch.cat(pool) if pool else torch.zeros(0, dtype=torch.float64)
+    if allv.numel() < 512:
+        raise BudgetError(f"{what}: the pooled cases hold {allv.numel()} elements, fewer than 512")
+    return check_rounds(allv, what)
+
+
+def act_f32(pre, act, slope=0.1):
+    """The trunk activation as ONE float32 operation on a float32 value (act: 0 none, 1 ReLU, 2 Leaky: x >= 0 ? x : x * float32(slope)),
+    not yet rounded to fp16.  -> float64 tensor of float32 values."""
+    x = check_storable(torch.as_tensor(pre, dtype=torch.float64), torch.float32, "activation input").to(torch.float32)
+    if act == 0:
+        y = x
+    elif act == 1:
+        y = torch.clamp(x, min=0.0)
+    else:
+        y = torch.where(x >= 0, x, x * torch.tensor(float(slope), dtype=torch.float32))
+    return y.to(torch.float64)
+
+
+def act_round_ref(pre, act, slope=0.1):
+    """The trunk kernels' epilogue order: the activation in float32 on the exact sum, THEN one round-to-nearest-even to fp16.
+    act: 0 none, 1 ReLU, 2 LeakyReLU(slope) as igemm.ACT_*.  The activation restates csrc/conv_igemm.hip `fmaxf(x, 0) + nslope *
+    fminf(x, 0)` / `t >= 0 ? t : t * p.slope`, csrc/conv_tile.hip:187 and conv_patch.h:36: on the negative side ONE float32 multiply
+    by float32(slope), rounded to float32 (exact for a dyadic slope and a short sum, one rounding for 0.1), before the fp16 rounding.
+    A contracted fma(nslope, min(x, 0), max(x, 0)) gives the same value, because one of the two addends is zero.
+    pre: float64 tensor of float32 values (checked).  -> float64 tensor of fp16 values (+-inf from 65520)."""
+    return round_f16(act_f32(pre, act, slope), "activation output")
+
+
+def prelu_f16_ref(v16, slope, build="max"):
+    """The SR kernels' PReLU on packed fp16 (csrc/sr_f16_common.h prelu_h2 / act_stage): the slope (any float32 parameter) rounded to
+    fp16 by the packer, m = v * a rounded ONCE to fp16 (the exact product of two 11-bit significands has 22 bits: a float32 value),
+    then `max(v, m)` in the builds for slopes <= 1 ("max"), `min(v, m)` for a slope above 1 ("min"), `v < 0 ? m : v` in the select
+    builds ("select").  v16: float64 tensor of finite fp16 values (checked).  The sign of a zero is not compared, as elsewhere."""
+    v16 = check_storable(torch.as_tensor(v16, dtype=torch.float64), torch.float16, "PReLU input")
+    s32 = torch.tensor([float(slope)], dtype=torch.float32).to(torch.float64)
+    a = float(round_f16(s32, "PReLU slope"))
+    m = round_f16(v16 * a, "PReLU product")
+    if build == "max":
+        return torch.maximum(v16, m)
+    if build == "min":
+        return torch.minimum(v16, m)
+    if build == "select":
+        return torch.where(v16 < 0, m, v16)
+    raise ValueError(build)
+
+
+def store_f16(pre, slope, build, name=None):
+    """What an SR kernel stores for a float32 sum: one rounding to fp16, then the packed-fp16 PReLU.  The `*_round_ref` references take a
+    replacement (`store=`) so that tests/test_exact_helper.py can evaluate a case under a DEFECT and count what it moves; `name` tells the
+    replacement which storage point it is at."""
+    return prelu_f16_ref(round_f16(pre), slope, build)
+
+
+def store_f32act(pre, slope, build, name=None):
+    """What a fused stage stores for its OUTPUT sum (csrc/sr_utd4.hip red_stage, sr_utd_s2.hip reduce_store and their siblings: "slope
+    multiply, max / select, 2 converts"): the PReLU in float32 with the float32 slope on the float32 sum, then ONE rounding to fp16 --
+    `act_round_ref`.  The max form fmaxf(s, s a) and the select form s >= 0 ? s : s a give the same value for a <= 1."""
+    return act_round_ref(pre, 2, slope)
+
+
+def stage_round_ref(a, up_w, up_b, up_a, dt_w, dt_b, dt_a, dn_w, dn_b, dn_a, S, live=("up", "dt", "dn"), weights_f16=True, store=store_f16,
+                    store_out=store_f32act):
+    """`stage_ref` with rounding.  The two sums that stay inside the kernel (deconvolution, downtran 1x1) are rounded ONCE to fp16
+    (`round_f16`) and their PReLU runs on the fp16 value with the fp16 slope and one fp16 rounding of the product (`prelu_f16_ref`); the
+    OUTPUT sum takes its PReLU in float32 with the float32 slope and is rounded once behind it (`store_f32act`: the kernels' reduce
+    stages).  The next layer reads those rounded values -- its float32
+    budget checked on their actual granularity.  `live`: which of the three sums must meet `check_rounds` (none for a map of a few pixels).  -> dict(hr, t, out) plus
+    the pre-rounding sums (hr0, t0, o0)."""
+    b = "max" if all(float(s) <= 1.0 for s in (up_a, dt_a, dn_a)) else "select"      # (one flag per launch: csrc/sr_utd*.hip slopes_le_one)
+    check_storable(a, torch.float16, "stage input")
+    for w_ in (up_w, dt_w, dn_w) if weights_f16 else ():
+        check_storable(w_, torch.float16, "stage weight (fp16 fragments)")
+    hr0 = deconv_ref(a, up_w, up_b, stride=S, padding=2, what="stage deconvolution")
+    hr = store(hr0, up_a, b, "up")
+    t0 = conv_ref(hr, dt_w.reshape(32, 32, 1, 1), dt_b, what="stage downtran 1x1")
+    t = store(t0, dt_a, b, "dt")
+    o0 = conv_ref(t, dn_w, dn_b, stride=S, padding=2, what="stage strided convolution")
+    out = store_out(o0, dn_a, b, "dn")
+    for name, s0 in (("up", hr0), ("dt", t0), ("dn", o0)):
+        if name in live:
+            check_rounds(s0, f"stage {name} sum")
+            check_live(s0, f"stage {name} sum", min_distinct=4)
+    return dict(hr=hr, t=t, out=out, hr0=hr0, t0=t0, o0=o0)
+
+
+def tail_round_ref(hid, out_w, out_b, out_a, cv_w, cv_b, S, live=True, local=False, store=store_f16):
+    """`tail_ref` with rounding: the deconvolution sum rounds once to fp16, the fp16 PReLU (any float32 slope), then conv_out (float32
+    output, no fp16 store) reads the rounded map inside its float32 budget (`local`: per output, see `conv_ref`)."""
+    assert out_w.shape[-1] == S + 4 and tuple(cv_w.shape) == (3, 32, 3, 3)
+    check_storable(hid, torch.float16, "tail input")
+    check_storable(out_w, torch.float16, "tail weight (fp16 fragments)")
+    check_storable(cv_w, torch.float16, "conv_out weight (fp16 fragments)")
+    hr0 = deconv_ref(hid, out_w, out_b, stride=S, padding=2, what="tail deconvolution")
+    if live:
+        check_rounds(hr0, "tail deconvolution sum")
+        check_live(hr0, "tail deconvolution sum", min_distinct=4)
+    hr = store(hr0, out_a, "max" if float(out_a) <= 1.0 else "select", "out")
+    raw = conv_ref(hr, cv_w, cv_b, padding=1, what="conv_out", store=torch.float32, local=local)
+    if live:
+        check_live(raw, "conv_out sum", min_distinct=50)
+    return dict(hr=hr, hr0=hr0, raw=raw, dec=raw[..., ::S, ::S].contiguous())
+
+
+def fold_round_ref(lr_a, lr_b, cmap, co_w, co_b, co_a, live=True, store=store_f16):
+    """`fold_ref` with rounding: 1x1 over two LR maps + bias + the float32 constant map, ONE rounding to fp16, the fp16 PReLU.
+    -> (hid, the pre-rounding sum)."""
+    check_storable(cmap, torch.float32, "constant map")
+    x = torch.cat((lr_a, lr_b), 1)
+    check_storable(x, torch.float16, "compress_out input")
+    check_storable(co_w, torch.float16, "compress_out weight (fp16 fragments)")
+    s0 = conv_ref(x, co_w.reshape(32, 64, 1, 1), co_b, what="compress_out")
+    a = F.conv2d(x.abs(), co_w.abs().reshape(32, 64, 1, 1), co_b.abs()) + cmap.abs().unsqueeze(0)
+    check_sum_budget(a, min(granularity(x) * granularity(co_w), granularity(co_b), granularity(cmap)), "compress_out + constant map")
+    s0 = s0 + cmap.unsqueeze(0)
+    if live:
+        check_rounds(s0, "compress_out sum")
+    return store(s0, co_a, "max" if float(co_a) <= 1.0 else "select", "co"), s0
+
+
+def chain_round_ref(stages, pool=None, live=True, store=store_f16):
+    """`chain_ref` with rounding: every stage's float32 sum rounds once to fp16, PReLU on fp16 values (csrc/sr_f16.hip k_chain1x1_h
+    takes the max form for a slope <= 1 and the min form above).  -> (outputs, pre-rounding sums)."""
+    _threads()
+    outs, pres, last = [], [], None
+    for s, st in enumerate(stages):
+        terms = list(st["ins"]) + ([(last, st["prev"])] if st.get("prev") is not None else [])
+        if not terms or (st.get("prev") is not None and last is None):
+            raise ValueError(f"stage {s} has no input")
+        acc = st["bias"].view(1, 32, 1).clone()
+        mag = st["bias"].abs().view(1, 32, 1).clone()
+        gran = granularity(st["bias"])
+        if st.get("cmap") is not None:
+            check_storable(st["cmap"], torch.float32, f"stage {s} constant map")
+            acc, mag, gran = acc + st["cmap"].unsqueeze(0), mag + st["cmap"].abs().unsqueeze(0), min(gran, granularity(st["cmap"]))
+        for x, w in terms:
+            check_storable(w, torch.float16, f"stage {s} weight (fp16 fragments)")
+            check_storable(x, torch.float16, f"stage {s} input")
+            acc = acc + torch.einsum("oc,ncp->nop", w, x)
+            mag = mag + torch.einsum("oc,ncp->nop", w.abs(), x.abs())
+            gran = min(gran, granularity(x) * granularity(w))
+        check_sum_budget(mag, gran, f"chain stage {s}")
+        if live:
+            check_rounds(acc, f"chain stage {s} sum", pool=pool)
+            check_live(acc, f"chain stage {s} sum", min_distinct=4)
+        last = store(acc, st["slope"], "max" if float(st["slope"]) <= 1.0 else "min", f"s{s}")
+        outs.append(last)
+        pres.append(acc)
+    return outs, pres
+
+
+def head_round_ref(x, sub, w_in, b_in, a_in, w_feat, b_feat, a_feat, live=True, store=store_f16):
+    """`head_ref` (fp16) with rounding: both sums of k_head_h round once to fp16 before their packed-fp16 PReLU.  The mean-shifted pixels
+    stay fp16 values (that conversion has no sum behind it).  -> (out, conv_in sum, feat_in sum)."""
+    s, b = sub
+    t = check_storable(x * s.view(1, 3, 1, 1) + b.view(1, 3, 1, 1), torch.float16, "mean-shifted pixels")
+    check_storable(w_in, torch.float16, "conv_in weight (fp16 fragments)")
+    check_storable(w_feat, torch.float16, "feat_in weight (fp16 fragments)")
+    m0 = conv_ref(t, w_in, b_in, padding=1, what="conv_in")
+    if live:
+        check_rounds(m0, "conv_in sum")
+    mid = store(m0, a_in, "max" if float(a_in) <= 1.0 else "select", "in")
+    f0 = conv_ref(mid, w_feat.reshape(32, -1, 1, 1), b_feat, what="feat_in")
+    if live:
+        check_rounds(f0, "feat_in sum")
+    return store(f0, a_feat, "max" if float(a_feat) <= 1.0 else "select", "feat"), m0, f0
 
 
 # ---------------------------------------------------------------------------------------------------------------- comparison

@@ -8,6 +8,7 @@ import torch
 import torch.nn.functional as F
 
 import _exact as X
+from _round_cases import two_taps as _two_taps
 from video_super_resolution_amd.depth import _A, _B, _C, _D, _E, _F, _G
 
 SIGS = {"A": _A, "B": _B, "C": _C, "D": _D, "E": _E, "F": _F, "G": _G}
@@ -94,3 +95,51 @@ def gauss_ref(wts, x16):
         mid = F.relu(F.conv2d(x16, h(w1), f(b1))).to(torch.float16).double()
         outs.append(F.relu(F.conv2d(mid, h(wk), f(bk), padding=(wk.shape[-1] - 1) // 2)))
     return torch.cat(outs, 1)
+
+
+# ---------------------------------------------------------------------------------------------------------------- rounding
+# The Gaussian cases round their mid maps, but a float64 Gaussian sum is never half-way between two fp16 values and the 2 x bar above
+# is a tolerance.  These cases keep the float32 budget of tests/_exact.py and make the sums 13 to 15 bits wide: each mid map and each
+# output is the ONE round-to-nearest-even of an exact float32 sum behind its ReLU, ties included (`_exact.check_rounds`).
+ROUND_SIZES = [(17, 33), (33, 60)]      # (on smaller maps most taps of an 11 x 11 row fall into the padding: too few sums round)
+
+
+@functools.lru_cache(maxsize=None)
+def round_weights(name):
+    """1x1 rows: integers in +-8 on a share of the inputs that puts the sums of inputs in +-255 near 5000; k x k rows: two weights of +-1
+    on the ROUNDED mid map (a sum of two 11-bit values and an integer bias rounds again and stays inside the fp16 range)."""
+    cin, o0, rest = parts(SIGS[name])
+    rs = np.random.RandomState(sum(map(ord, name)) + 11)
+    dens = min(1.0, 5000.0 ** 2 / (255 * 256 / 3.0 * 25.5 * cin))
+
+    def bias(n):
+        return X.ints(rs, (n,), -2000, 2000)
+
+    w0 = X.sparse_weights(rs, (o0, cin, 1, 1), dens, 8)
+    branches = []
+    for mid, k, out in rest:
+        branches.append((X.sparse_weights(rs, (mid, cin, 1, 1), dens, 8), bias(mid), _two_taps(rs, out, mid * k * k).reshape(out, mid, k, k), bias(out)))
+    return (w0, bias(o0)), branches
+
+
+def round_input(name, hw):
+    """[NREF,cin,H,W] integers in +-255, float64."""
+    return X.ints(np.random.RandomState(hw[0] * 100 + hw[1] + 5), (NREF, parts(SIGS[name])[0]) + tuple(hw), -255, 255)
+
+
+def round_ref(wts, x):
+    """float64 sums inside the float32 budget, ReLU in float32, ONE rounding to fp16 at each of the two storage points; the k x k
+    convolutions read the rounded mid maps.  Every pre-rounding map meets `check_rounds`.  -> (output, list of the pre-rounding maps)."""
+    (w0, b0), branches = wts
+    pres = [X.conv_ref(x, w0, b0, what="plain 1x1")]
+    outs = [X.act_round_ref(pres[0], 1)]
+    for j, (w1, b1, wk, bk) in enumerate(branches):
+        m0 = X.conv_ref(x, w1, b1, what=f"branch {j} 1x1")
+        mid = X.act_round_ref(m0, 1)
+        k = wk.shape[-1]
+        o0 = X.conv_ref(mid, wk, bk, padding=(k - 1) // 2, what=f"branch {j} {k}x{k}")
+        outs.append(X.act_round_ref(o0, 1))
+        pres += [m0, o0]
+    for i, p in enumerate(pres):
+        X.check_rounds(p, f"inception pre-rounding map {i}")
+    return torch.cat(outs, 1), pres

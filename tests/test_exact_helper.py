@@ -738,3 +738,291 @@ def test_nearest_resize_ref_differs_from_the_rational_index_where_the_cases_say(
     x = torch.arange(n_in, dtype=torch.float16).view(1, 1, n_in, 1) + 0.5
     got = E.nearest_resize_ref(x, (n_out, 1))
     assert got.dtype == torch.float16 and torch.equal(got[0, 0, :, 0], E.nearest_sources(n_in, n_out).to(torch.float16) + 0.5)
+
+
+# ------------------------------------------------------------------------------------------------ rounding: round_f16 and its companions
+import _round_cases as R  # noqa: E402
+
+
+def _edge_sweep():
+    """Every tie and both of its float32 neighbours at the two ends of each binade from 2^-24 to 2^15 (ties behind an even and behind an
+    odd significand), the 65519 / 65520 pair and its neighbours, subnormal ties of both parities, +-0; both signs."""
+    v = [0.0, 65504.0, 65519.0, 65520.0, 65535.0, 65536.0, 2.0 ** -25, 3 * 2.0 ** -25, 2.0 ** -26, 2.0 ** -24]
+    for e in range(-24, 16):
+        q = 2.0 ** max(e - 10, -24)                                    # the fp16 spacing inside [2^e, 2^(e+1))
+        lo, hi = 2.0 ** e, 2.0 ** (e + 1)
+        v += [lo + q / 2, lo + 3 * q / 2, hi - q / 2, hi - 3 * q / 2, lo, hi - q]
+    for k in (0, 1, 2, 3, 510, 511, 1022, 1023):                       # subnormal ties (k + 1/2) 2^-24
+        v.append((k + 0.5) * 2.0 ** -24)
+    a = np.array(v, dtype=np.float32)
+    assert np.array_equal(a.astype(np.float64), np.array(v))           # (each is a float32 value)
+    a = np.concatenate([a, np.nextafter(a, np.float32(np.inf)), np.nextafter(a, np.float32(-np.inf))])
+    a = a[np.abs(a) < 3e38]
+    return np.concatenate([a, -a])
+
+
+def test_round_f16_equals_the_torch_and_numpy_casts_on_the_edge_sweep():
+    a = _edge_sweep()
+    got = E.round_f16(torch.from_numpy(a.astype(np.float64))).numpy()
+    with np.errstate(over="ignore"):
+        want_np = a.astype(np.float16).astype(np.float64)
+    want_t = torch.from_numpy(a).to(torch.float16).to(torch.float64).numpy()
+    want_t64 = torch.from_numpy(a.astype(np.float64)).to(torch.float16).to(torch.float64).numpy()
+    for want in (want_np, want_t, want_t64):
+        bad = np.nonzero(got != want)[0]
+        assert bad.size == 0, (a[bad[:5]], got[bad[:5]], want[bad[:5]])
+    # the literal corners
+    f = lambda x: float(E.round_f16(torch.tensor([x], dtype=torch.float64)))
+    assert (f(2049.0), f(2051.0), f(4098.0), f(4102.0)) == (2048.0, 2052.0, 4096.0, 4104.0)
+    assert f(65519.0) == 65504.0 and f(65520.0) == float("inf") and f(-65520.0) == float("-inf") and f(65519.99609375) == 65504.0
+    assert f(2.0 ** -25) == 0.0 and f(3 * 2.0 ** -25) == 2.0 ** -23 and f(2.0 ** -25 * (1 + 2.0 ** -23)) == 2.0 ** -24      # gradual underflow
+    with pytest.raises(E.BudgetError):
+        E.round_f16(torch.tensor([0.1], dtype=torch.float64))          # not a float32 value
+    with pytest.raises(E.BudgetError):
+        E.round_f16(torch.tensor([float("nan")], dtype=torch.float64))
+
+
+def test_round_f16_equals_an_int64_restatement_on_24_bit_integers():
+    rs = np.random.RandomState(24)
+    n = np.concatenate([rs.randint(0, 2 ** 24, size=20000), rs.randint(0, 2 ** 16, size=20000), np.arange(2040, 2060), np.arange(65500, 65540)]).astype(np.int64)
+    bl = np.floor(np.log2(np.maximum(n, 1))).astype(np.int64) + 1      # bit length (exact: n < 2^24 is a float64 integer)
+    s = np.maximum(bl - 11, 0)
+    lo = (n >> s) << s
+    rem, half = n - lo, (np.int64(1) << s) >> 1
+    up = (rem > half) | ((rem == half) & (s > 0) & (((n >> s) & 1) == 1))
+    want = (lo + np.where(up, np.int64(1) << s, 0)).astype(np.float64)
+    want[want >= 65536] = np.inf
+    for sign in (1.0, -1.0):
+        got = E.round_f16(torch.from_numpy(n.astype(np.float64) * sign)).numpy()
+        assert np.array_equal(got, want * sign)
+    # the alternatives differ exactly where they should: truncation wherever a remainder exists and RNE went up, "away" at ties behind even
+    x = torch.from_numpy(n[n < 65504].astype(np.float64))
+    p = E.rounding_profile(x)
+    rne, rtz, away = E.round_f16(x), E.round_f16_alt(x, "rtz"), E.round_f16_alt(x, "away")
+    assert torch.equal(rtz != rne, p["inexact"] & (rne.abs() > x.abs())) and bool((rtz.abs() <= x.abs()).all())
+    assert torch.equal(away != rne, p["tie_down"]) and int(p["tie_down"].sum()) > 100 and int(p["tie_up"].sum()) > 100
+    assert torch.equal(p["tie"], p["tie_up"] | p["tie_down"]) and not bool((p["tie"] & ~p["inexact"]).any())
+
+
+def test_act_round_and_packed_prelu_references_state_their_operations():
+    v = torch.arange(-40000, 40000, 7, dtype=torch.float64)
+    # trunk order: float32 multiply by float32(slope), one fp16 rounding (numpy's casts as the independent statement)
+    for slope in (0.1, 0.75, 0.2):
+        want = np.where(v.numpy() >= 0, v.numpy(), (v.numpy().astype(np.float32) * np.float32(slope)).astype(np.float64)).astype(np.float32).astype(np.float16)
+        assert np.array_equal(E.act_round_ref(v, 2, slope).numpy(), want.astype(np.float64))
+    assert torch.equal(E.act_round_ref(v, 1), E.round_f16(v.clamp(min=0))) and torch.equal(E.act_round_ref(v, 0), E.round_f16(v))
+    assert torch.equal(E.leaky_tenth_f16(v), E.act_round_ref(v, 2, 0.1))
+    # SR order: fp16 value times fp16 slope, rounded once, then max / min / select
+    v16 = E.round_f16(v)
+    for slope, build in ((0.2, "max"), (0.75, "max"), (0.75, "select"), (1.5, "min"), (1.5, "select"), (-0.75, "select"), (-0.75, "max")):
+        a = np.float16(np.float32(slope))
+        m = (v16.numpy().astype(np.float16).astype(np.float64) * float(a)).astype(np.float16).astype(np.float64)      # (22-bit product: exact in float64)
+        want = np.where(v16.numpy() < 0, m, v16.numpy())
+        assert np.array_equal(E.prelu_f16_ref(v16, slope, build).numpy(), want), (slope, build)
+    assert float(E.prelu_f16_ref(torch.tensor([-3.0], dtype=torch.float64), 0.2)) == float(np.float16(-3.0) * np.float16(0.2))
+    assert float(E.prelu_f16_ref(torch.tensor([-3.0], dtype=torch.float64), 0.2)) != float(np.float16(np.float32(-3.0) * np.float32(0.2)))
+    with pytest.raises(E.BudgetError, match="PReLU input"):
+        E.prelu_f16_ref(torch.tensor([2049.0], dtype=torch.float64), 0.5)
+
+
+def test_check_rounds_fires_on_each_of_its_conditions():
+    rs = np.random.RandomState(1)
+    good = torch.from_numpy(rs.randint(-20000, 20000, size=4096).astype(np.float64))
+    E.check_rounds(good, "good")
+    with pytest.raises(E.BudgetError, match="need rounding"):
+        E.check_rounds(torch.from_numpy(rs.randint(-2000, 2000, size=4096).astype(np.float64)), "all exact")
+    with pytest.raises(E.BudgetError, match="ties"):
+        E.check_rounds(good + 0.25, "no ties")
+    with pytest.raises(E.BudgetError, match="overflows"):
+        E.check_rounds(torch.cat([good, torch.tensor([65520.0], dtype=torch.float64)]), "overflow")
+    with pytest.raises(E.BudgetError, match="too few"):
+        E.check_rounds(good[:100], "small")
+    pool = []
+    E.check_rounds(good[:300], "a", pool=pool)
+    with pytest.raises(E.BudgetError, match="fewer than 512"):
+        E.check_rounds_pool(pool, "pool")
+    E.check_rounds(good[300:600], "b", pool=pool)
+    E.check_rounds_pool(pool, "pool")
+    up_only = torch.arange(2049, 4096, 4, dtype=torch.float64)          # 2049 + 4 k: every tie sits behind an even significand
+    with pytest.raises(E.BudgetError, match="ties go up"):
+        E.check_rounds(up_only, "one direction")
+
+
+def test_local_granularity_sees_the_fine_value_only_where_it_is_read():
+    x = torch.zeros((1, 2, 5, 5), dtype=torch.float64) + 4096.0
+    x[0, 1, 2, 2] = 2.0 ** -13
+    w = torch.zeros((1, 2, 3, 3), dtype=torch.float64)
+    w[0, 1, 1, 1] = w[0, 0, 0, 0] = 1.0
+    g = E.local_granularity(x, w, padding=1)
+    assert float(g[0, 0, 2, 2]) == 2.0 ** -13 and int((g != 1.0).sum()) == 1
+    with pytest.raises(E.BudgetError, match=r"\(0, 0, 2, 2\)"):          # 4096 + 2^-13 needs 26 bits
+        E.conv_ref(x, w, padding=1, local=True)
+    w[0, 0, 0, 0] = 0.0
+    E.conv_ref(x, w, padding=1, local=True)                              # one term per output: exact
+    with pytest.raises(E.BudgetError):
+        E.conv_ref(x, w, padding=1)                                      # the global budget refuses the map: 4096 against a granule of 2^-13
+
+
+# ------------------------------------------------------------------------------------------------ rounding: every case, and what each defect moves
+def _enough(n_moved, numel):
+    """At least 5 % of a stored map, or at least 16 elements of a map below 512."""
+    return n_moved >= (16 if numel < 512 else max(16, int(np.ceil(0.05 * numel))))
+
+
+@pytest.mark.parametrize("name", R.names())
+def test_trunk_rounding_case_is_live_and_tells_every_defect(name):
+    """The case builds (its budget and `check_rounds` run inside) and its reference differs from truncation, ties away from zero, the
+    activation behind the rounding (Leaky cases), the slope rounded to fp16 (Leaky 0.1) and a partial sum parked in fp16 in at least 5 % of the map: the device comparison,
+    which has no tolerance, fails for each of those defects."""
+    c = R.case(name)
+    alts = R.alternatives(c)
+    assert {"rtz", "away", "partial"} <= set(alts) and (("act_after" in alts) == (c["act"] == R.LEAKY))
+    assert ("slope16" in alts) == (c["act"] == R.LEAKY and c["slope"] == 0.1)
+    for kind, alt in alts.items():
+        assert _enough(R.moved(c, alt), c["want"].numel()), (name, kind, R.moved(c, alt), c["want"].numel())
+
+
+def test_trunk_composite_cases_are_live():
+    """HFlowHead (the flow rounds, the upsampling of the ROUNDED flow rounds again), HHourglassFront, the average pool, the float32-weight
+    cases: references, budgets and liveness; a kernel that read the UNROUNDED map or weight would move 5 % of the next one."""
+    for i in range(len(R.FLOW_HEAD)):
+        c = R.flow_head_case(i)
+        other = E.round_f16(E.deconv_ref(c["pre"], c["wu"], c["bu"], stride=2, padding=1))
+        assert _enough(int((other != c["up"]).sum()), c["up"].numel())
+    for i in range(len(R.HG_FRONT)):
+        c = R.hg_front_case(i)
+        other = E.act_round_ref(E.conv_ref(torch.relu(c["stem"]["pre"]), c["w1"], c["b1"]), R.RELU)
+        assert _enough(int((other != c["one"]).sum()), c["one"].numel())
+    for shape in ((2, 9, 7, 16), (3, 5, 33, 40)):
+        x16, want = R.avg_pool_case(shape)
+        two = torch.nn.functional.avg_pool2d(x16.double()[..., 8:].permute(0, 3, 1, 2), 2, 2)
+        assert _enough(int((E.round_f16_alt(two, "rtz") != want).sum()), want.numel())
+    for family, shape in (("gather", (1, 33, 6, 11, 17, 3, 1, 1)), ("tile", (1, 33, 11, 12, 65, 3, 1, 1))):
+        c = R.w32_case(family, shape)
+        assert _enough(R.moved(c, c["unrounded"]), c["want"].numel())
+
+
+@pytest.mark.parametrize("family", list(R.EDGE_SHAPES))
+def test_overflow_and_underflow_cases_hold_their_counts(family):
+    c = R.overflow_case(family)
+    assert c["n_inf"] >= 8 and c["n_max"] >= 8 and int(torch.isinf(c["want"]).sum()) == c["n_inf"]
+    assert int((c["want"].abs() == 65504.0).sum()) >= c["n_max"]
+    clamped = torch.clamp(c["want"], -65504.0, 65504.0)                  # a conversion that clamps
+    assert int((clamped != c["want"]).sum()) == c["n_inf"]
+    u = R.underflow_case(family)
+    flushed = torch.where(u["want"].abs() < 2.0 ** -14, torch.zeros_like(u["want"]), u["want"])      # a conversion that flushes subnormals
+    assert u["n_sub"] >= 0.25 * u["want"].numel() and int((flushed != u["want"]).sum()) >= 0.25 * u["want"].numel()
+    assert torch.equal(u["want"] * 2.0 ** 28 / 16.0, torch.round(u["want"] * 2.0 ** 28 / 16.0))      # multiples of 2^-24
+
+
+def _sr_defects(evaluate, ref_maps, slopes, parts):
+    """Each defect of `_round_cases.DEFECTS` through `evaluate(store, store_out)` -> dict of maps; it must move 5 % of at least one stored map."""
+    for kind in R.DEFECTS:
+        if kind == "slope" and not R.has_float32_slope(*slopes):
+            continue
+        store, store_out = R.sr_defect(kind, parts)
+        alt = evaluate(store, store_out)
+        assert any(_enough(int((alt[k] != ref_maps[k]).sum()), ref_maps[k].numel()) for k in ref_maps), (kind, {k: int((alt[k] != ref_maps[k]).sum()) for k in ref_maps})
+
+
+STAGE_CASES = [(S, shape, sel, post) for S in (4, 2, 3) for shape in R.SR_SHAPES[S] for sel, post in ((False, False), (False, True), (True, False), (True, True))]
+
+
+@pytest.mark.parametrize("S,shape,select,post", STAGE_CASES)
+def test_stage_rounding_case_is_live_and_tells_every_defect(S, shape, select, post):
+    c, ref = R.gen_round_stage(S, shape, select=select, post=post)
+    maps = {k: ref[k] for k in (("out", "post") if post else ("out",))}     # (a 2 x 2 map holds 128 elements: the bar is 16 of them)
+    parts = {"up": torch.nn.functional.conv_transpose2d(c["a"][:, :16], c["up_w"][:16], None, stride=S, padding=2)}
+    _sr_defects(lambda st, so: R.eval_stage(c, post, store=st, store_out=so), maps, (c["up_a"], c["dt_a"], c["dn_a"]) + ((c["post_a"],) if post else ()), parts)
+
+
+@pytest.mark.parametrize("select", [False, True])
+@pytest.mark.parametrize("S", [4, 2, 3])
+def test_a_defect_at_one_storage_point_of_a_stage_is_seen(S, select):
+    """The defects one storage point at a time (the third shape of each scale, with POST): a wrong rounding or an activation on the other side
+    at the deconvolution, the downtran, the output or the POST store ALONE moves 5 % of a stored map; so does the slope in the other format at
+    the one point whose slope is no fp16 value."""
+    shape = R.SR_SHAPES[S][2]
+    c, ref = R.gen_round_stage(S, shape, select=select, post=True)
+    maps = {k: ref[k] for k in ("out", "post")}
+    for point in ("up", "dt", "dn", "post"):
+        for kind in ("rtz", "away", "act_side") + (("slope",) if point == "post" else ()):
+            st, so = R.sr_defect(kind, only=point)
+            alt = R.eval_stage(c, True, store=st, store_out=so)
+            moved = {k: int((alt[k] != maps[k]).sum()) for k in maps}
+            assert any(_enough(moved[k], maps[k].numel()) for k in maps), (point, kind, moved)
+            if point == "post":
+                assert moved["out"] == 0
+    c, ref = R.gen_round_stage(S, shape, select=select, post=False)       # (without POST the output's own slope is 0.2)
+    st, so = R.sr_defect("slope", only="dn")
+    assert _enough(int((R.eval_stage(c, False, store=st, store_out=so)["out"] != ref["out"]).sum()), ref["out"].numel())
+
+
+@pytest.mark.parametrize("S", [4, 2, 3])
+def test_stage_with_float32_weights_is_live(S):
+    R.gen_round_stage_w32(S, R.SR_SHAPES[S][2])       # (raises unless the unrounded weights would move 5 % of the output)
+
+
+TAIL_CASES = [(S, shape, fold, last) for S in (4, 2, 3) for shape in R.SR_SHAPES[S] for fold in ((False, True) if S == 4 else (True,) if S == 2 else (False,))
+              for last in (False, True)]
+
+
+@pytest.mark.parametrize("S,shape,fold,last", TAIL_CASES)
+def test_tail_rounding_case_is_live_and_tells_every_defect(S, shape, fold, last):
+    c, ref = R.gen_round_tail(S, shape, fold=fold, last=last)
+    if last and ref["raw"].numel() < 512:
+        return      # geometry only: with slope 0.2 conv_out reads ONE HR value per plane, 48 to 192 outputs in all; liveness is pooled below
+    F = torch.nn.functional
+    parts = ({"co": F.conv2d(c["lr_a"], c["co_w"][:, :32].reshape(32, 32, 1, 1))} if fold
+             else {"out": F.conv_transpose2d(c["hid"][:, :16], c["out_w"][:16], None, stride=S, padding=2)})
+    _sr_defects(lambda st, so: R.eval_tail(c, store=st), {"raw": ref["raw"]}, (c["out_a"],) + ((c["co_a"],) if fold else ()), parts)
+
+
+@pytest.mark.parametrize("slopes", [(0.75, 0.2), (1.5, 0.1)])
+@pytest.mark.parametrize("shape", [(3, 2, 2), (8, 9, 40), (2, 37, 33)])
+def test_head_rounding_case_is_live_and_tells_every_defect(shape, slopes):
+    c, ref = R.gen_round_head(shape, slopes=slopes)
+    t = c["x"] * c["sub"][0].view(1, 3, 1, 1) + c["sub"][1].view(1, 3, 1, 1)
+    parts = {"in": torch.nn.functional.conv2d(t[:, :1], c["w_in"][:, :1], None, padding=1)}
+    _sr_defects(lambda st, so: R.eval_head(c, store=st), {"out": ref["out"]}, slopes, parts)
+
+
+CHAIN_ROUND_SPECS = {"2-p": [(2, False, False), (0, True, False)], "2m-1p-p": [(2, False, True), (1, True, False), (0, True, False)],
+                     "1m-1p-p": [(1, False, True), (1, True, False), (0, True, False)], "1-2p-1pm": [(1, False, False), (2, True, False), (1, True, True)]}
+
+
+@pytest.mark.parametrize("N,P", [(2, 65), (3, 1000)])
+@pytest.mark.parametrize("name", sorted(CHAIN_ROUND_SPECS))
+def test_chain_rounding_case_is_live_and_tells_every_defect(name, N, P):
+    stages, outs, _ = R.gen_round_chain(CHAIN_ROUND_SPECS[name], N, P)
+    x, wm = stages[0]["ins"][0]
+    parts = {"s0": torch.einsum("oc,ncp->nop", wm[:, :16], x[:, :16])}
+    maps = {f"s{i}": o for i, o in enumerate(outs)}
+    _sr_defects(lambda st, so: {f"s{i}": o for i, o in enumerate(E.chain_round_ref(stages, live=False, store=st)[0])}, maps, [s["slope"] for s in stages], parts)
+
+
+@pytest.mark.parametrize("slope", [0.2, 1.5])
+@pytest.mark.parametrize("nin,cm", [(1, False), (3, True)])
+@pytest.mark.parametrize("N,P", [(2, 65), (3, 1000)])
+def test_conv1x1_rounding_case_is_live_and_tells_every_defect(N, P, nin, cm, slope):
+    stages, outs, _ = R.gen_round_chain([(nin, False, cm)], N, P, slopes=(slope,))
+    x, wm = stages[0]["ins"][0]
+    parts = {"s0": torch.einsum("oc,ncp->nop", wm[:, :16], x[:, :16])}
+    _sr_defects(lambda st, so: {"s0": E.chain_round_ref(stages, live=False, store=st)[0][0]}, {"s0": outs[0]}, (slope,), parts)
+
+
+@pytest.mark.parametrize("mode", [3, 2])
+@pytest.mark.parametrize("shape", R.PRE_SHAPES)
+def test_folded_chain_stage_rounding_case_is_live_and_tells_every_defect(shape, mode):
+    c, ref = R.gen_round_pre(shape, mode)
+    parts = {"up": torch.nn.functional.conv_transpose2d(c["a"][:, :16], c["up_w"][:16], None, stride=3, padding=2)}
+    _sr_defects(lambda st, so: R.eval_stage(c, True, store=st, store_out=so), {k: ref[k] for k in ("out", "post")}, (c["up_a"], c["dt_a"], c["dn_a"], c["post_a"]), parts)
+
+
+def test_small_sr_cases_meet_the_liveness_numbers_as_pools():
+    """The 2 x 2 stage and tail cases and the 2 x 2 head hold maps below 512 elements: per storage point their pre-rounding sums are pooled
+    over the cases, and each pool meets `check_rounds` (a quarter inexact, a twentieth ties, 16 ties each way, no overflow)."""
+    pools = R.small_cases()
+    assert set(pools) == {"stage output sum", "POST 1x1 sum", "compress_out sum", "feat_in sum"}, sorted(pools)
+    for name, cases in pools.items():
+        E.check_rounds_pool(list(cases.values()), f"{name}, pooled over {len(cases)} small cases")

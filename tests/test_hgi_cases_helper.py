@@ -24,3 +24,21 @@ def test_the_budget_test_catches_a_mid_that_would_round():
     bad = [(w1 + 2.0 ** -12, b1, wk, bk) for (w1, b1, wk, bk) in branches]
     with pytest.raises(X.BudgetError):
         C.exact_ref(((w0, b0), bad), X.ints(np.random.RandomState(0), (1, 128, 9, 17)))
+
+
+@pytest.mark.parametrize("name", sorted(C.SIGS))
+def test_every_rounding_case_is_inside_the_budget_and_rounds(name):
+    """The rounding cases of tests/test_gpu_rounding.py: float32 budget, `check_rounds` on every mid map and every output sum (both run
+    inside `round_ref`), and a block that read its UNROUNDED mid maps would move 5 % of the output."""
+    import torch
+    wts = C.round_weights(name)
+    for hw in C.ROUND_SIZES:
+        x = C.round_input(name, hw)
+        y, pres = C.round_ref(wts, x)
+        assert len(pres) == 1 + 2 * len(wts[1])
+        outs = [X.act_round_ref(pres[0], 1)]
+        for j, (w1, b1, wk, bk) in enumerate(wts[1]):
+            k = wk.shape[-1]
+            outs.append(X.act_round_ref(X.conv_ref(torch.relu(pres[1 + 2 * j]), wk, bk, padding=(k - 1) // 2), 1))
+        other = torch.cat(outs, 1)
+        assert int((other != y).sum()) >= 0.05 * y.numel(), (name, hw)

@@ -43,6 +43,14 @@ static_assert(UTD_LDS <= 160 * 1024, "LDS budget");
 // nothing is scheduled across it: the hand-placed step schedules fence every MFMA gap
 #define VSR_FENCE() __builtin_amdgcn_sched_barrier(0)
 
+// Where the fused kernels round (tests/test_gpu_rounding.py holds each point to it, bit for bit):
+//   * a sum that stays inside the kernel or feeds a matrix core again (deconvolution, downtran 1x1, a chain stage, the head's two sums,
+//     the tails' deconvolution and folded compress_out, the POST 1x1): the float32 sum is converted to fp16 ONCE, round to nearest even
+//     (v_cvt_pk_f16_f32; overflow gives infinity, subnormals are kept), THEN PReLU runs on packed fp16: the slope is the float32
+//     parameter rounded to fp16, the product v * a is rounded once to fp16, max / min / select pick between v and the product;
+//   * a fused stage's OUTPUT (the reduce stages of k_utd .. k_utd4, k_utd_s2, k_utd_s2w, k_utd_s3): PReLU in float32 with the float32
+//     slope on the float32 sum (t = s * a, then fmaxf(s, t) or the select s >= 0 ? s : t, by kernel and build -- k_utd4 takes the
+//     maximum where every slope is <= 1, k_utd_s2 always selects; the same value for a <= 1), and ONE conversion to fp16 behind it.
 // PReLU on packed fp16 pairs: max(v, a*v) for a <= 1, min(v, a*v) for a > 1 (one v_pk_mul + one v_pk_max/min per pair)
 __device__ __forceinline__ h2 prelu_h2(h2 v, h2 a, bool use_max) {
     const h2 m = v * a;
