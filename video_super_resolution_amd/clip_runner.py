@@ -1,7 +1,8 @@
 """`ClipRunner`: a 4:2:0 clip streamed through the model on top of `frames`: every source frame uploaded once from pinned memory on a
 copy stream, converted once into a three-slot LR ring, the window formed on the device, the HR frame written out as 4:2:0 and copied
 back on a second copy stream.  What a run scores (`score=`, `baseline=`, `temporal=`) is a list of series, each a range of rows of one
-float64 tensor of sums (`sums_layout`); with `scene="sad"` scene cuts are found and the window composed under them on the device, in
+float64 tensor of sums (`sums_layout`); with `multiscale=True` the frames' multi-scale SSIM sums go into a tensor of their own; with
+`scene="sad"` scene cuts are found and the window composed under them on the device, in
 tensors of their own; `driver` imports `ClipRunner`, so `driver.ClipRunner` resolves as before.
 """
 from __future__ import annotations
@@ -12,8 +13,9 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 import torch
 
-from .frames import (METRIC_CHANNELS, FrameResizer, _scene_thresholds, ewarp, frame_metrics, psnr_ssim, scene_flags, scene_sums,
-                     scene_window, truth_flows, warp_error, yuv_coefficients, yuv_frame_bytes, yuv_ingest, yuv_write)
+from .frames import (METRIC_CHANNELS, MSSSIM_BETA, MSSSIM_MIN_SIZE, FrameResizer, _scene_thresholds, ewarp, frame_metrics, frame_msssim,
+                     msssim, psnr_ssim, scene_flags, scene_sums, scene_window, truth_flows, warp_error, yuv_coefficients, yuv_frame_bytes,
+                     yuv_ingest, yuv_write)
 
 # series of `sums_layout` -> the keys of `ClipRunner.metrics` its host step (`psnr_ssim` for a frame series, `ewarp` for a pair series)
 # fills; the occlusion mask depends on the flows alone, so the estimate's pairs give the one `valid_share`
@@ -82,6 +84,13 @@ class ClipRunner:
     baseline, `ewarp_baseline`, each [T-3] (empty for T = 3).  No upload, download or host wait is added; with `temporal=None` the
     launches are the ones described above.
 
+    `multiscale=True` (needs `score`, and 161 pixels each way after the shave): multi-scale SSIM of every output frame (`frame_msssim`,
+    Wang et al. 2003), one more scoring call per window on the buffers the per-frame scores already hold, with the same channels,
+    quantise and shave, into row j of a [T-2,P,5,2] float64 tensor of its own; with `baseline="bicubic"` the baseline frame gets one too,
+    into a second such tensor (both are views of one buffer).  One small copy at the end brings them back: `metrics` gains `msssim` and,
+    with a baseline, `msssim_baseline`, each [T-2] (`msssim`, the host step).  `sums_layout` and the [rows,4] tensor are untouched; no
+    upload, download or host wait is added; with `multiscale=False` the launches are the ones described above.
+
     `scene="sad"`: scene cuts found and handled on the device (include/vsr_hip_scene.h).  After source frame i >= 1 has been converted
     into its ring slot, `scene_sums` of the ring's frames i - 1 and i goes into row i - 1 of a [T-1,2] float64 tensor and `scene_flags`
     of that row, with the row above as the pair before, into element i - 1 of a [T-1] int32 tensor.  The window of frames i - 2 .. i
@@ -103,7 +112,7 @@ class ClipRunner:
     def __init__(self, model, shape: Tuple[int, int], fmt_in: str, fmt_out: str, scale_down: int = 1, overlap: bool = True,
                  matrix: str = "bt709", full_range: bool = False, siting: str = "left", score: Optional[str] = None,
                  shave: Optional[int] = None, decimate: str = "nearest", baseline: Optional[str] = None, temporal: Optional[str] = None,
-                 occ=None, scene: Optional[str] = None, scene_thresholds=None):
+                 occ=None, scene: Optional[str] = None, scene_thresholds=None, multiscale: bool = False):
         if decimate not in self.DECIMATE:
             raise ValueError(f"decimate must be 'nearest' or 'bicubic', got {decimate!r}")
         if baseline not in self.BASELINE:
@@ -139,6 +148,12 @@ class ClipRunner:
         self.score, self.shave = score, (S if shave is None else int(shave))
         if score is not None and (self.shave < 0 or min(self.shape) - 2 * self.shave < 11):
             raise ValueError(f"shave {self.shave} leaves less than SSIM's 11 pixels of {self.shape}")
+        self.multiscale = bool(multiscale)
+        if self.multiscale and score is None:
+            raise ValueError("multiscale=True is scored beside the estimate: it needs score='rgb' or 'y'")
+        if self.multiscale and min(self.shape) - 2 * self.shave < MSSSIM_MIN_SIZE:
+            raise ValueError(f"multiscale=True needs {MSSSIM_MIN_SIZE} pixels each way after the shave: shave {self.shave} leaves "
+                             f"{min(self.shape) - 2 * self.shave} of {self.shape}")
         self.metrics = None   # of the last run(): {"psnr": [T-2], "ssim": [T-2]} when scoring
         self.in_bytes = yuv_frame_bytes(fmt_in, H, W)
         self.out_bytes = yuv_frame_bytes(fmt_out, *self.out_shape)
@@ -212,8 +227,13 @@ class ClipRunner:
             scene_buf = torch.empty(20 * (T - 1), dtype=torch.uint8, device=self.device)
             scene_rows = scene_buf[:16 * (T - 1)].view(torch.float64).view(T - 1, 2)
             scene_flag = scene_buf[16 * (T - 1):].view(torch.int32)
+        # multiscale: the sums [series, T-2, P, 5, 2] float64 of `frame_msssim`, series 0 the estimate's and 1 the baseline's
+        ms = None
+        if self.multiscale:
+            ms = torch.empty((2 if self.baseline is not None else 1, T - 2, 3 if self.score == "rgb" else 1, len(MSSSIM_BETA), 2),
+                             dtype=torch.float64, device=self.device)
         return SimpleNamespace(
-            scene_buf=scene_buf, scene_sums=scene_rows, scene_flags=scene_flag,
+            ms=ms, scene_buf=scene_buf, scene_sums=scene_rows, scene_flags=scene_flag,
             out=np.empty((T - 2, self.out_bytes), dtype=np.uint8), layout=layout,
             sums=None if layout is None else torch.empty((rows, 4), dtype=torch.float64, device=self.device),
             main=main, s_in=s_in, s_out=s_out, est=None, prev_est=None,
@@ -272,9 +292,13 @@ class ClipRunner:
         est, truth, base = st.est[0], self._slot(self._truth, j), self._slot(self._base, j)
         yuv_ingest(self._dev_in[c], self.shape, self.fmt_in, self.coef_in, self.siting, lr_out=truth)
         frame_metrics(est, truth, self.score, True, self.shave, out=row("estimate", j))
+        if st.ms is not None:
+            frame_msssim(est, truth, self.score, True, self.shave, out=st.ms[0, j:j + 1])
         if base is not None:
             self._up(self._ring[(j + 1) % 3], quantise=False, out=base)
             frame_metrics(base, truth, self.score, True, self.shave, out=row("baseline", j))
+            if st.ms is not None:
+                frame_msssim(base, truth, self.score, True, self.shave, out=st.ms[1, j:j + 1])
         if self.temporal is not None and j >= 1:
             # the pair (j - 1, j) along the flows between source frames j and j + 1: the other truth buffer still holds source frame j,
             # `prev_est` the estimate of the window before
@@ -331,6 +355,11 @@ class ClipRunner:
             if kind == "pair" and self.cuts is not None:   # row r is scored along the flows between source frames r + 1 and r + 2
                 values[0][self.cuts[1:1 + rows]] = np.nan
             metrics.update((k, v) for k, v in zip(METRIC_KEYS[name], values) if k is not None)
+        if st.ms is not None:   # one more small copy, after the wait above
+            host = st.ms.cpu().numpy()
+            h, w = self.shape[0] - 2 * self.shave, self.shape[1] - 2 * self.shave
+            for k, name in enumerate(("msssim", "msssim_baseline")[:host.shape[0]]):
+                metrics[name] = msssim(host[k], h, w)
         return metrics
 
     def _collect_scene(self, st, T: int) -> None:

@@ -14,7 +14,7 @@ feeds it, on the GPU path and without OpenCV:
     save_checkpoint / load_checkpoint   utils/tools.py:68-73 and main.py:108-122,233-237: {'arch','epoch','state_dict':
                             SRmodel.model.state_dict(),'optimizer'} -- files interchange with the reference's
 
-The device bindings for frames in, out, resampled and scored (4:2:0 I/O, the resampler, PSNR / SSIM, the warping error) live in
+The device bindings for frames in, out, resampled and scored (4:2:0 I/O, the resampler, PSNR / SSIM, MS-SSIM, the warping error) live in
 `frames`, the streamed `ClipRunner` on top of them in `clip_runner`; their public names are imported here, so `driver.frame_metrics`,
 `driver.ClipRunner` and the rest resolve.
 
@@ -36,8 +36,9 @@ import torch
 
 from . import _lib as L
 from .clip_runner import ClipRunner, sums_layout  # noqa: F401
-from .frames import (METRIC_CHANNELS, METRIC_WHAT, RESIZE_KERNELS, RESIZE_MAX_TAPS, SCENE_THRESHOLDS, WARP_OCC, YUV_FORMATS,  # noqa: F401
-                     YUV_SITINGS, FrameResizer, ewarp, frame_metrics, frames_to_yuv, ingest_item_yuv, psnr_ssim, read_clip_yuv,
+from .frames import (METRIC_CHANNELS, METRIC_WHAT, MSSSIM_BETA, MSSSIM_MIN_SIZE, RESIZE_KERNELS, RESIZE_MAX_TAPS, SCENE_THRESHOLDS,  # noqa: F401
+                     WARP_OCC, YUV_FORMATS, YUV_SITINGS, FrameResizer, ewarp, frame_metrics, frame_msssim, frames_to_yuv,
+                     ingest_item_yuv, msssim, msssim_levels, psnr_ssim, read_clip_yuv,
                      resize_frames, resize_tables, scene_cuts, scene_flags, scene_sums, scene_window, ssim_window, truth_flows, warp_error,
                      yuv_coefficients, yuv_frame_bytes, yuv_ingest, yuv_write)
 
@@ -236,7 +237,7 @@ def run_c1(lr: int = 128, frames: int = 3, scale: int = 4, precision: str = "fp3
 
 def run_c1_yuv(pix_fmt: str, lr: int = 128, frames: int = 3, scale: int = 4, precision: str = "fp32", score: Optional[str] = None,
                decimate: str = "nearest", baseline: Optional[str] = None, temporal: Optional[str] = None, scene: Optional[str] = None,
-               scene_thresholds=None, cut_at: Optional[int] = None):
+               scene_thresholds=None, cut_at: Optional[int] = None, multiscale: bool = False):
     """Config C1 with a 4:2:0 boundary: the synthetic clip as `pix_fmt` frames on the host, streamed through `ClipRunner`
     (decimated by `scale`, super-resolved by `scale`).  -> (result line, output frames uint8 [T-2, frame_bytes] on the host).
     `score`: "rgb" | "y": the line also carries the per-frame PSNR / SSIM against the synthetic HR clip.  `decimate` / `baseline`: as
@@ -244,7 +245,8 @@ def run_c1_yuv(pix_fmt: str, lr: int = 128, frames: int = 3, scale: int = 4, pre
     `temporal` the clip means of E_warp of the estimate, of the truth frames (and of the baseline) and of the valid share (E_warp over the
     pairs that have valid pixels; null where there is none, or no pair: a clip of three frames).  `cut_at` = K: the clip's frames from K
     on come from a second seed, a scene cut between the frames K - 1 and K.  `scene` / `scene_thresholds`: as `ClipRunner`'s; the line
-    then carries `cuts`, the indices i of the pairs (i, i + 1) found to be cuts, and `scene_m`, the mean absolute luma difference per pair."""
+    then carries `cuts`, the indices i of the pairs (i, i + 1) found to be cuts, and `scene_m`, the mean absolute luma difference per pair.
+    `multiscale` (needs `score`): the line also carries the per-frame MS-SSIM as `msssim` (and its baseline mean with a baseline)."""
     import time
     from . import VSR
     from .weights import fill_module_
@@ -260,7 +262,7 @@ def run_c1_yuv(pix_fmt: str, lr: int = 128, frames: int = 3, scale: int = 4, pre
         video[cut_at:] = synthetic_video(frames, S * lr, S * lr, seed=4321)[cut_at:]
     clip = frames_to_yuv(torch.from_numpy(video).to(dev).float(), pix_fmt).cpu().numpy()
     runner = ClipRunner(model, (S * lr, S * lr), pix_fmt, pix_fmt, scale_down=S, score=score, decimate=decimate, baseline=baseline,
-                        temporal=temporal, scene=scene, scene_thresholds=scene_thresholds)
+                        temporal=temporal, scene=scene, scene_thresholds=scene_thresholds, multiscale=multiscale)
     runner.run(clip)                                                      # warm-up (packing, allocator)
     t0 = time.perf_counter()
     out = runner.run(clip)
@@ -271,6 +273,10 @@ def run_c1_yuv(pix_fmt: str, lr: int = 128, frames: int = 3, scale: int = 4, pre
     if score is not None:
         line.update(score=score, shave=runner.shave, psnr_db=[round(float(v), 4) for v in runner.metrics["psnr"]],
                     ssim=[round(float(v), 6) for v in runner.metrics["ssim"]])
+    if multiscale:
+        line.update(msssim=[round(float(v), 6) for v in runner.metrics["msssim"]])
+        if baseline is not None:
+            line.update(msssim_baseline_mean=round(float(np.mean(runner.metrics["msssim_baseline"])), 6))
     if decimate != "nearest":
         line.update(decimate=decimate)
     if baseline is not None:
@@ -333,6 +339,8 @@ def main(argv=None):
                     help="with --pix-fmt: per-frame PSNR / SSIM of the output against the synthetic HR clip, on RGB or on luma (BT.601 Y)")
     ap.add_argument("--decimate", default="nearest", choices=list(ClipRunner.DECIMATE),
                     help="with --pix-fmt: how the LR frames are made (nearest: the reference's decimation; bicubic: antialiased, stored as 8-bit)")
+    ap.add_argument("--multiscale", action="store_true",
+                    help="with --score: also the per-frame multi-scale SSIM (five levels; needs 161 pixels each way after the shave)")
     ap.add_argument("--baseline", default=None, choices=["bicubic"],
                     help="with --score: also score the bicubic enlargement of the LR frame; the line carries both means and psnr_gain")
     ap.add_argument("--temporal", default=None, choices=["warp"],
@@ -358,6 +366,8 @@ def main(argv=None):
         ap.error("--score needs --pix-fmt (the streamed clip runner scores its frames)")
     if args.decimate != "nearest" and args.pix_fmt is None:
         ap.error("--decimate needs --pix-fmt (the streamed clip runner makes the LR frames)")
+    if args.multiscale and args.score is None:
+        ap.error("--multiscale needs --score (it is scored beside the estimate)")
     if args.baseline is not None and args.score is None:
         ap.error("--baseline needs --score (it is scored beside the estimate)")
     if args.temporal is not None and args.score is None:
@@ -377,7 +387,7 @@ def main(argv=None):
                                loss_path=args.loss_path or "reference")
     elif args.pix_fmt is not None:
         line, _ = run_c1_yuv(args.pix_fmt, args.lr, args.frames, args.scale, args.precision, args.score, args.decimate, args.baseline,
-                             args.temporal, args.scene, args.scene_thresholds, args.cut_at)
+                             args.temporal, args.scene, args.scene_thresholds, args.cut_at, args.multiscale)
     else:
         line, _, _, _ = run_c1(args.lr, args.frames, args.scale, args.precision)
     print(json.dumps(line))

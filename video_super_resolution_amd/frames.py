@@ -1,4 +1,4 @@
-"""Frames in, out, resampled, scored and watched for scene cuts on the device: the Python side of five side libraries, one section each.
+"""Frames in, out, resampled, scored and watched for scene cuts on the device: the Python side of six side libraries, one section each.
 
     read_clip_yuv / ingest_item_yuv / frames_to_yuv     ingest, and write-out for what decoders emit: packed Y'CbCr 4:2:0 frames
                             (yuv420p, nv12, yuv420p10le, p010le), converted on the device (include/vsr_hip_yuv.h); the matrix
@@ -8,6 +8,9 @@
                             come from `resize_tables` alone
     frame_metrics / psnr_ssim   HR frames scored against ground truth on the device: the float64 sums behind PSNR and SSIM per frame
                             (include/vsr_hip_metric.h), and the host step that forms the two numbers from them
+    frame_msssim / msssim_levels / msssim   multi-scale SSIM on the device (include/vsr_hip_msssim.h): the float64 sums of the contrast-
+                            structure and SSIM maps per frame, plane and level, five levels pooled 2 x 2 on the device, and the host step
+                            that forms the means, the powers and their product
     truth_flows / warp_error / ewarp   the temporal warping error on the device (include/vsr_hip_warp.h): forward and backward FlowNet2
                             flows between ground-truth frames, frame t + 1 warped back onto frame t and the squared difference summed
                             over the pixels that are not occluded, in float64, and the host step that forms E_warp from the sums
@@ -15,7 +18,7 @@
                             of consecutive LR frames summed per pair, the cut rule on the sums as device flags, the 3-frame window and
                             the fed-back estimate composed under two flags, and the host step that applies the same rule to the sums
 
-`clip_runner.ClipRunner` streams a clip through all five; `driver` imports every public name here, so `driver.frame_metrics` and the rest
+`clip_runner.ClipRunner` streams a clip through all six; `driver` imports every public name here, so `driver.frame_metrics` and the rest
 resolve as before.  Transfer functions and 4:2:2 / 4:4:4 stay out.
 """
 from __future__ import annotations
@@ -359,6 +362,74 @@ def psnr_ssim(sums) -> Tuple[np.ndarray, np.ndarray]:
     on = n_ssim > 0
     ssim[on] = ssim_sum[on] / n_ssim[on]
     return psnr, ssim
+
+
+# ------------------------------------------------------------------------------------------------ multi-scale SSIM
+MSSSIM_BETA = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)   # the exponents of levels 1 to 5 (Wang, Simoncelli, Bovik 2003)
+MSSSIM_MIN_SIZE = 161                                    # VSR_MSSSIM_MIN_SIZE of include/vsr_hip_msssim.h: 161, 81, 41, 21, 11
+
+
+def msssim_levels(h: int, w: int) -> list:
+    """The five (h_j, w_j) of a plane of h x w (after the shave): every level half the one before, rounded up."""
+    out = []
+    for _ in range(len(MSSSIM_BETA)):
+        out.append((int(h), int(w)))
+        h, w = (h + 1) // 2, (w + 1) // 2
+    return out
+
+
+@L.on_device
+def frame_msssim(a: torch.Tensor, b: torch.Tensor, channels: str = "rgb", quantise: bool = True, shave: int = 0, luma4=None,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """float32 RGB frames `a`, `b` ([H,W,3], [1,H,W,3] or [F,H,W,3], 0..255) -> the device tensor [F,P,5,2] float64 of
+    {cs_sum, ssim_sum} per frame, plane (P = 3 for "rgb", 1 for "y") and level (vsr_msssim_frames); nothing is synchronised, `msssim`
+    is the host step.  `quantise`, `shave`, `channels`: as `frame_metrics`; `luma4`: four float32 {a0, a1, a2, o} of the luma of "y"
+    mode, default the BT.601 limited-range luma of `frame_metrics`; `out`: write the sums there ([F,P,5,2] float64)."""
+    import ctypes
+    code = _channel_code(channels)
+    fa, fb = _frame_pair(a, b, "F")
+    shave = int(shave)
+    F, H, W = int(fa.shape[0]), int(fa.shape[1]), int(fa.shape[2])
+    if shave < 0 or min(H, W) - 2 * shave < MSSSIM_MIN_SIZE:
+        raise ValueError(f"MS-SSIM needs {MSSSIM_MIN_SIZE} pixels each way after the shave, got {min(H, W) - 2 * shave} "
+                         f"(shave {shave} of {H} x {W})")
+    if channels == "y":
+        luma4 = _luma4("y", "bt601", False) if luma4 is None else np.ascontiguousarray(np.asarray(luma4, dtype=np.float32).reshape(4))
+    else:
+        luma4 = None
+    win = ssim_window()
+    M = L.load_msssim()
+    pa, pb = L.dptr(fa), L.dptr(fb)   # (raises on CPU tensors and on anything but float32)
+    if fb.device != fa.device:
+        raise ValueError("the two tensors live on different devices")
+    shape = (F, 1 if channels == "y" else 3, len(MSSSIM_BETA), 2)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float64, device=fa.device)
+    elif tuple(out.shape) != shape or out.device != fa.device:
+        raise ValueError(f"out must be float64 {shape} on {fa.device}, got {tuple(out.shape)} on {out.device}")
+    ws = torch.empty(int(M.vsr_msssim_ws_bytes(F, H, W, shave, code)), dtype=torch.uint8, device=fa.device)
+    L.check(M.vsr_msssim_frames(pa, pb, F, H, W, code, 1 if quantise else 0, shave,
+                                None if luma4 is None else luma4.ctypes.data_as(ctypes.c_void_p), win.ctypes.data_as(ctypes.c_void_p),
+                                L.dptr(out, torch.float64), L.dptr(ws, torch.uint8), L.stream()), "msssim_frames", lib=M)
+    return out
+
+
+def msssim(sums, h: int, w: int) -> np.ndarray:
+    """The host step after `frame_msssim`: sums [F,P,5,2] (a tensor, copied to the host here, or an array) of planes of h x w (after the
+    shave) -> MS-SSIM [F].  Per plane prod_{j<5} max(mcs_j, 0)^beta_j * max(mssim_5, 0)^beta_5, the means being the sums over
+    (h_j - 10)(w_j - 10) and beta `MSSSIM_BETA`; the result is the mean over the planes (the per-channel rule of
+    tf.image.ssim_multiscale and pytorch-msssim)."""
+    s = sums.detach().cpu().numpy() if isinstance(sums, torch.Tensor) else np.asarray(sums)
+    s = np.asarray(s, dtype=np.float64)
+    if s.ndim != 4 or s.shape[2:] != (len(MSSSIM_BETA), 2):
+        raise ValueError(f"expected sums [F,P,5,2], got {s.shape}")
+    n = np.array([(hj - 10) * (wj - 10) for hj, wj in msssim_levels(h, w)], dtype=np.float64)
+    if n[-1] <= 0:
+        raise ValueError(f"MS-SSIM needs {MSSSIM_MIN_SIZE} pixels each way, got {h} x {w}")
+    means = s / n[None, None, :, None]
+    terms = np.concatenate([means[:, :, :-1, 0], means[:, :, -1:, 1]], axis=2)   # mcs_1 .. mcs_4, mssim_5
+    per_plane = np.prod(np.maximum(terms, 0.0) ** np.array(MSSSIM_BETA), axis=2)
+    return per_plane.mean(axis=1)
 
 
 # ------------------------------------------------------------------------------------------------ temporal warping error
