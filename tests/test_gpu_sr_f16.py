@@ -367,7 +367,7 @@ def test_prelu_slopes_above_one_and_negative(gpu_vsr_f16, shape):
 def test_shared_planes_bit_identical(gpu_vsr_f16, shape, decimate_first):
     """VSR.forward's two SR calls share their first three planes (the LR frames): with `shared`, the second call computes
     head + FeedbackBlock for its other five planes only and must return exactly the frame of a full evaluation; a changed
-    weight set or frame size must not reuse stale maps."""
+    frame size must not reuse stale maps (a changed weight set: tests/test_gpu_weight_freshness.py::test_shared_maps_do_not_outlive_the_weights)."""
     m = gpu_vsr_f16.model
     h, w = shape
     rs = np.random.RandomState(h * 19 + w)

@@ -9,7 +9,9 @@ One library call (one kernel launch) updates every tensor of a parameter group (
 `max_grad_norm` one more call (two launches) first takes the norm over every parameter that has a gradient and leaves the coefficient
 on the device, where the update reads it.  `launches` counts the KERNEL LAUNCHES of the last `step()`: 1, or 3 with `max_grad_norm`
 (2 + one per group and distinct `step` value in general).
-`.grad` is never modified (torch.nn.utils.clip_grad_norm_ scales it in place; this step scales the value it reads).  There is no
+`.grad` is never modified (torch.nn.utils.clip_grad_norm_ scales it in place; this step scales the value it reads).  The kernels write
+through raw pointers, so after the launches `step()` moves the version counter of every tensor they wrote (`mark_updated`: the parameter,
+`exp_avg`, `exp_avg_sq`; on the host), as an in-place operator would: the inference kernels read packed copies keyed by it.  There is no
 fallback: a CPU, non-float32, non-contiguous or sparse parameter or gradient raises `VsrHipError`, and so do the variants the
 kernels do not implement (amsgrad, maximize, capturable, differentiable, decoupled_weight_decay).
 
@@ -41,6 +43,16 @@ def adam_scalars(lr: float, beta1: float, beta2: float, eps: float, weight_decay
     """The seven float32 scalars of vsr_opt_adam_f32, formed in float64 (Python floats) and rounded once at the call:
     (omb1, b2, omb2, step_size, rs, eps, wd)."""
     return (1.0 - beta1, beta2, 1.0 - beta2, lr / (1.0 - beta1 ** t), math.sqrt(1.0 - beta2 ** t), eps, weight_decay)
+
+
+def mark_updated(tensors) -> None:
+    """Tell torch that `tensors` were written through their raw pointers: their version counters move, as after an in-place operator.
+    Every packed copy of the weights (the SR net's pack, the trunk executors, the graphs of GraphedVSR) is keyed by (address, version),
+    so a write that leaves the version alone would leave those copies stale.  Host only: no launch, no synchronisation, no value read or
+    written; under no_grad it takes leaves that require grad."""
+    with torch.no_grad():
+        for t in tensors:
+            torch._C._increment_version(t)
 
 
 class _Plan:
@@ -214,4 +226,6 @@ class Adam(torch.optim.Optimizer):
                 self.launches += 1
                 for p, _, _, _ in entries:
                     self.state[p]["step"] += 1
+        # the kernel wrote p, exp_avg and exp_avg_sq behind torch's back (a parameter without a gradient was not touched: it keeps its version)
+        mark_updated(t for p, _, m, v in every for t in (p, m, v))
         return loss

@@ -756,6 +756,7 @@ class SRProjectionModule(nn.Module):
         if n_sh:
             live = {k: shared["live"][k] for k in (3, 6)}
         elif share_ok:
+            shared.pop("prefc_all", None)   # (it belonged to the maps replaced here: other weights or another geometry made it, `skey` names these)
             shared.update(live={k: live[k] for k in (3, 6)}, key=skey)
         kept = shared is not None and shared.get("key") == skey and taps is None   # (`prefc_all` belongs to the kept maps)
         return self._tail_f16(x, live, P, cmap_nhwc, taps, decimate, shared.get("prefc_all") if (n_sh and kept) else None, n_sh)

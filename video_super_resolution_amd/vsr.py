@@ -94,14 +94,20 @@ class VSR(nn.Module):
         # frame pair computed for window t are what window t+1 computes again.  With temporal_cache = True they are kept
         # across calls, keyed by the identity AND version counter of the frame tensors (views of one clip tensor, as
         # main.py:196-199 / driver.run_item hand them over): about two of G1's four hourglass runs and one of its two FlowNet2
-        # runs saved per window.  Same networks on the same frames, but on smaller batches -- the MFMA convolution picks its
-        # tile / split-K shape by the pixel count -- so the frames agree with the per-window evaluation to rounding, not bit for bit.
+        # runs saved per window.  Same networks on the same frames, but on smaller batches: the fp16 launchers are told the
+        # window's full batch (`_lib.route_batch`) and run the kernels they would run on it, so a frame equals the per-window
+        # evaluation bit for bit whatever the windows before it were.  The float32 trunks cannot promise that -- `trunk_f32._route`
+        # and the stock operator both choose by the batch they are given, and a prediction kept from another batch moved a
+        # 66 x 70 frame by 2.8 of 255, by an amount that depended on which windows had come before -- so the float32
+        # configuration keeps nothing: the flag is accepted and every window is evaluated in full there.
         # A cache entry HOLDS the frame tensors it was computed from, so their storage cannot be freed and handed out again
         # under the same address (windows built afresh by torch.stack / .to(dev) never hit: different storage, and the old
-        # one is still alive); what the key cannot see is a write into the SAME storage that bypasses the version counter
+        # one is still alive); what the key cannot see is a write into a FRAME's storage that bypasses the version counter
         # (a raw-pointer kernel launch): call `reset_temporal_cache()` after one.
+        # The entries also belong to the weights they were computed with: the cache remembers the keys of the hourglass and
+        # FlowNet2 executors (address and version of every parameter and buffer) and is emptied when either differs.
         self.temporal_cache = False
-        self._tcache = {"depth": {}, "flow": {}}
+        self._tcache = self._new_tcache()
         self.keep_loss_terms = False   # True: `last_loss_terms` = the four terms + masked tensors of the last train=True call
         self.last_loss_terms = None
         self._flow_exec = TrunkExecCache(self.FlowModule.net, FlowNet2Exec)
@@ -141,11 +147,15 @@ class VSR(nn.Module):
         new._flow_exec = TrunkExecCache(new.FlowModule.net, FlowNet2Exec)
         new._depth_exec = TrunkExecCache(new.DepthModule.model.netG, HourglassExec)
         new._vos_exec = TrunkExecCache(new.VOSModule.net, OSVOSExec)
-        new._tcache = {"depth": {}, "flow": {}}
+        new._tcache = self._new_tcache()
         return new
 
+    @staticmethod
+    def _new_tcache():
+        return {"depth": {}, "flow": {}, "weights": None}
+
     def reset_temporal_cache(self):
-        self._tcache = {"depth": {}, "flow": {}}
+        self._tcache = self._new_tcache()
 
     @staticmethod
     def _tkey(t):
@@ -186,8 +196,11 @@ class VSR(nn.Module):
             s_vos.wait_stream(main)
 
         # depth trunk once per distinct frame, all new frames as one batch
-        tc = self._tcache if (self.temporal_cache and cacheable) else None
+        tc = self._tcache if (self.temporal_cache and cacheable and fast) else None   # (float32: no entries, see __init__)
         if tc is not None:   # streaming mode: predictions of frames an earlier window already saw
+            wkey = (self._depth_exec.key(), self._flow_exec.key())
+            if tc.get("weights") != wkey:   # ... under other weights: not this model's predictions any more
+                tc.update(depth={}, flow={}, weights=wkey)
             for f in trip:
                 hit = tc["depth"].get(self._tkey(f))
                 if hit is not None and f.data_ptr() not in depth_cache:
