@@ -26,33 +26,12 @@ pytestmark = pytest.mark.gpu
 
 import _metric_ref as R  # noqa: E402
 from _poison import poisoned  # noqa: E402
+from _score_cases import MODES, _ids, _luma4, images, to_device  # noqa: E402
 from video_super_resolution_amd import driver  # noqa: E402
 
 SW, SR, FT = 64, 64, 64
 SHAPES = [(1, 11, 11, 0, False), (2, 12, 75, 0, False), (1, 23, 140, 3, False), (1, SR + 11, SW, 0, False), (3, 16, 64, 2, False),
           (2, 16, 64, 2, True), (1, 516, 1020, 4, False)]
-MODES = [(ch, q) for ch in ("rgb", "y") for q in (0, 1)]
-IMAGES = {"textured": R.textured, "near_flat": R.near_flat, "gaussian": R.gaussian, "awkward": R.awkward,
-          "awkward_no_nan": functools.partial(R.awkward, nan=False)}
-
-
-def _ids(v):
-    return "x".join(str(int(i)) for i in v) if isinstance(v, tuple) else str(v)   # (a shape; other parameters are plain values)
-
-
-def _luma4():
-    c = driver.yuv_coefficients("yuv420p", "bt601", False)
-    return np.array([c[0], c[1], c[2], c[9]], dtype=np.float32)
-
-
-@functools.lru_cache(maxsize=None)
-def images(kind, shape):
-    """A pair of float32 [F,H,W,3] arrays, made once per (kind, shape) and never modified."""
-    F, H, W, shave, _ = shape
-    a, b = IMAGES[kind](np.random.RandomState(H * 131 + W + len(kind)), F, H, W)
-    a.setflags(write=False)
-    b.setflags(write=False)
-    return a, b
 
 
 @functools.lru_cache(maxsize=None)
@@ -60,17 +39,6 @@ def reference(kind, shape, channels, quant, want_ssim=True):
     """float64 [F,4] of the restatement, once per case and shared by the tests that need it."""
     a, b = images(kind, shape)
     return R.metrics(a, b, channels, bool(quant), shape[3], _luma4(), want_ssim=want_ssim)
-
-
-def to_device(x, offset):
-    """The array on the device; `offset`: inside a flat buffer at a storage offset of one float (4 bytes past a 16-byte boundary)."""
-    if not offset:
-        return torch.tensor(x).cuda()   # (a copy: the cached arrays are read-only)
-    buf = torch.zeros(x.size + 8, dtype=torch.float32, device="cuda")
-    buf[1:1 + x.size] = torch.tensor(x).reshape(-1).cuda()
-    view = buf[1:1 + x.size].view(x.shape)
-    assert view.data_ptr() % 16 == 4 and view.is_contiguous()
-    return view
 
 
 def gpu(a, b, shape, channels, quant, what=("psnr", "ssim")):

@@ -25,40 +25,18 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-import _metric_ref as R  # noqa: E402
 import _msssim_ref as M  # noqa: E402
 from _poison import poisoned  # noqa: E402
+from _score_cases import MODES, _ids, _luma4, images, to_device  # noqa: E402
 from video_super_resolution_amd import driver  # noqa: E402
 
 SHAPES = [(1, 161, 161, 0, False), (2, 176, 208, 0, False), (1, 189, 211, 4, False), (2, 176, 208, 0, True), (1, 516, 1020, 4, False),
           (1, 161, 1200, 0, False), (1, 1190, 161, 0, False)]
-MODES = [(ch, q) for ch in ("rgb", "y") for q in (0, 1)]
-IMAGES = {"textured": R.textured, "near_flat": R.near_flat, "gaussian": R.gaussian, "awkward": R.awkward,
-          "awkward_no_nan": functools.partial(R.awkward, nan=False)}
 BAR = 1e-10   # the absolute bound tests/test_gpu_metric.py has for a frame's SSIM mean
-
-
-def _ids(v):
-    return "x".join(str(int(i)) for i in v) if isinstance(v, tuple) else str(v)
-
-
-def _luma4():
-    c = driver.yuv_coefficients("yuv420p", "bt601", False)
-    return np.array([c[0], c[1], c[2], c[9]], dtype=np.float32)
 
 
 def plane_size(shape):
     return shape[1] - 2 * shape[3], shape[2] - 2 * shape[3]
-
-
-@functools.lru_cache(maxsize=None)
-def images(kind, shape):
-    """A pair of float32 [F,H,W,3] arrays, made once per (kind, shape) and never modified."""
-    F, H, W, shave, _ = shape
-    a, b = IMAGES[kind](np.random.RandomState(H * 131 + W + len(kind)), F, H, W)
-    a.setflags(write=False)
-    b.setflags(write=False)
-    return a, b
 
 
 @functools.lru_cache(maxsize=None)
@@ -68,17 +46,6 @@ def reference(kind, shape, channels, quant):
     s = M.sums(a, b, channels, bool(quant), shape[3], _luma4())
     s.setflags(write=False)
     return s
-
-
-def to_device(x, offset):
-    """The array on the device; `offset`: inside a flat buffer at a storage offset of one float (4 bytes past a 16-byte boundary)."""
-    if not offset:
-        return torch.tensor(x).cuda()   # (a copy: the cached arrays are read-only)
-    buf = torch.zeros(x.size + 8, dtype=torch.float32, device="cuda")
-    buf[1:1 + x.size] = torch.tensor(x).reshape(-1).cuda()
-    view = buf[1:1 + x.size].view(x.shape)
-    assert view.data_ptr() % 16 == 4 and view.is_contiguous()
-    return view
 
 
 def gpu(a, b, shape, channels, quant):

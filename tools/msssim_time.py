@@ -9,7 +9,9 @@ streamed clip runner with and without `multiscale`.  Device events, rounds inter
   part 2, C3-A (540x960 x4, fp16): ClipRunner on a 2160x3840 nv12 clip (decimated by 4) with score="y" and with multiscale=True on
           top, legs interleaved, in frames/s, host clock around work that ends in a wait for the last copy.
 
-    python tools/msssim_time.py [--frames 22] [--rounds 3] [--skip-runner]
+    python tools/msssim_time.py [--frames 22] [--rounds 3] [--skip-runner] [--unaligned]
+
+--unaligned: part 1 on frames at a storage offset of one float (bases 4 bytes past a 16-byte boundary): the element-load path.
 """
 import argparse
 import ctypes
@@ -30,6 +32,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--frames", type=int, default=22, help="frames of the clip of part 2 (windows = frames - 2)")
 ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--skip-runner", action="store_true")
+ap.add_argument("--unaligned", action="store_true")
 args = ap.parse_args()
 assert torch.cuda.is_available(), "needs the GPU (no fallback)"
 torch.cuda.set_device(0)
@@ -47,10 +50,20 @@ def events(fn, reps):
     return e0.elapsed_time(e1) * 1e3 / reps   # us
 
 
+def placed(x):
+    if not args.unaligned:
+        return x.contiguous()
+    buf = torch.zeros(x.numel() + 8, dtype=torch.float32, device=dev)
+    buf[1:1 + x.numel()] = x.reshape(-1)
+    view = buf[1:1 + x.numel()].view(x.shape)
+    assert view.data_ptr() % 16 == 4
+    return view
+
+
 # ------------------------------------------------------------------------------------------------ part 1
 M, MS = L.load_metric(), L.load_msssim()
-fa = [torch.rand(H, W, 3, device=dev) * 300 - 20 for _ in range(SETS)]
-fb = [(fa[k] + torch.randn(H, W, 3, device=dev) * 4).contiguous() for k in range(SETS)]
+fa = [placed(torch.rand(H, W, 3, device=dev) * 300 - 20) for _ in range(SETS)]
+fb = [placed(fa[k] + torch.randn(H, W, 3, device=dev) * 4) for k in range(SETS)]
 sums = torch.empty(1, 4, dtype=torch.float64, device=dev)
 win = driver.ssim_window()
 c = driver.yuv_coefficients("yuv420p", "bt601", False)
@@ -83,7 +96,8 @@ for rnd in range(5):
 levels = driver.msssim_levels(H - 2 * SHAVE, W - 2 * SHAVE)
 n = [(h - 10) * (w - 10) for h, w in levels]
 pooled = sum(h * w for h, w in levels[1:])
-print(f"part 1: one {H}x{W} frame per call (quantise 1, shave {SHAVE}), {SETS} buffer sets in rotation, 5 interleaved rounds of {REPS} "
+print(f"part 1: one {H}x{W} frame per call (quantise 1, shave {SHAVE}{', unaligned bases' if args.unaligned else ''}), {SETS} buffer sets "
+      f"in rotation, 5 interleaved rounds of {REPS} "
       "calls, best round (all rounds)")
 for name in legs:
     print(f"  {name:36s} {min(times[name]):8.1f} us   rounds us: " + " ".join(f"{t:.1f}" for t in times[name]))

@@ -1,28 +1,21 @@
 // frame_metric.hip -- HR frames scored against ground truth on the device (include/vsr_hip_metric.h; libvsr_hip_metric.so is built
 // from this source alone): per frame the float64 sums behind PSNR and SSIM.
 //
-//   k_metric : one workgroup (4 waves) = one tile of SW = 64 map columns x SR = 64 map rows of one frame; with SSIM the tile reads
-//              (SW + 10) x (SR + 10) pixels of the shaved plane, without it the map IS the plane and there is no halo.  The tile
-//              marches down its rows four at a time: wave v takes input row 4 t + v.
-//                load    : the row's 74 x 3 floats of a and b into LDS as they lie in memory (WIDE: one aligned 16-byte load per lane;
-//                          otherwise four element loads per lane): a frame is read about once plus halo from HBM; the second and third
-//                          plane of RGB read their rows again through the L2 of the same compute unit
-//                convert : lane l takes pixels l and l + 64: quantise, luma (Y) or channel p (RGB, p the plane of this pass), both
-//                          frames, to doubles in LDS; SSE is taken here, from the pixels the tile OWNS (the first SW x SR of its
-//                          rectangle; the last strip / segment also owns its halo), in the first pass for all three channels
-//                rows    : lane c = map column c: the five 11-tap sums along the row into an LDS ring of NW + 10 = 14 rows
-//                columns : wave v takes map row 4 t + v - 10 (its eleven ring rows are complete): the five 11-tap sums down the
-//                          column, the formula, the thread's running sum
-//              three barriers per step.  RGB runs the march once per plane with one ring (36 KB; three rings would leave one workgroup
-//              per compute unit).  At the end a fixed-order tree over the 256 threads and one pair of doubles into the workspace.
+//   k_metric : one workgroup (4 waves) = one tile of SW = 64 map columns x SR = 64 map rows of one frame, scored by the march of
+//              frame_ssim.h (load, convert, rows, columns; three barriers per step); with SSIM the tile reads (SW + 10) x (SR + 10)
+//              pixels of the shaved plane, without it the map IS the plane, there is no halo and the march ends at convert.  A frame
+//              is read about once plus halo from HBM; the second and third plane of RGB read their rows again through the L2 of the
+//              same compute unit.  SSE is taken in the convert step, from the pixels the tile OWNS (the first SW x SR of its rectangle;
+//              the last strip / segment also owns its halo), in the first pass for all three channels; in Y mode the luma is formed
+//              once, for the SSE and for the converted row.  At the end a fixed-order tree over the 256 threads and one pair of
+//              doubles into the workspace.
 //   k_finish : one workgroup of 64 threads per frame: thread t adds the partials t, t + 64, ... in that order, then the same tree;
 //              thread 0 writes the frame's four numbers (0 in the slots not asked for).
 // Nothing here is atomic and no order depends on timing or on F: a frame's numbers are the same bits in every run.
 //
 // The whole file is compiled without floating-point contraction (Makefile and the pragma below): luma, the SSE terms and the SSIM
 // formula round operation by operation as the header writes them; the window sums ask for their fmas by name.
-#include "frame_sums.h"
-#include "vsr_common.h"
+#include "frame_ssim.h"
 
 #include "../../include/vsr_hip_metric.h"
 
@@ -30,26 +23,16 @@
 
 namespace {
 
-using vsr::sums::Luma;
-using vsr::sums::quant;
+using namespace vsr::ssim;
 
-constexpr int SW = VSR_METRIC_STRIP_WIDTH, SR = VSR_METRIC_SEGMENT_ROWS, FT = VSR_METRIC_FINISH_THREADS;
-constexpr int NW = 4;              // waves per workgroup = input rows per step
-constexpr int K = 11;              // window taps
-constexpr int RING = NW + K - 1;   // ring rows: the 11 rows of the oldest map row of a step up to the newest input row
-constexpr int RAW = 256;           // floats of one staged row: 74 x 3 = 222, + 3 before an aligned start, rounded up to 64 lanes x 4
-constexpr int XS = 80;             // doubles of one converted row (74 used)
-
-struct Win {
-    double w[K];
-};
+constexpr int FT = VSR_METRIC_FINISH_THREADS;
+static_assert(VSR_METRIC_STRIP_WIDTH == SW && VSR_METRIC_SEGMENT_ROWS == SR, "the header's tile is the march's");
 
 template <bool SSIM, bool YMODE, bool QUANT, bool WIDE>
 __global__ void __launch_bounds__(NW * 64)
 k_metric(const float* __restrict__ a, const float* __restrict__ b, int H, int W, int shave, int want_sse, Luma lu, Win win,
          double* __restrict__ ws) {
     constexpr int HALO = SSIM ? K - 1 : 0;
-    constexpr double C1 = (0.01 * 255) * (0.01 * 255), C2 = (0.03 * 255) * (0.03 * 255);
     __shared__ __align__(16) float raw[NW][2][RAW];
     __shared__ double xs[NW][2][XS];
     __shared__ double ring[SSIM ? RING : 1][5][SW];
@@ -79,23 +62,7 @@ k_metric(const float* __restrict__ a, const float* __restrict__ b, int H, int W,
             // ---- load
             if (row_on) {
                 const size_t s = ((size_t)(shave + oy0 + ri) * W + shave + ox0) * 3;
-                if (WIDE) {
-                    const size_t s4 = s & ~(size_t)3;        // H * W * 3 is a multiple of 4: an aligned group ends inside the frame
-                    o = (int)(s - s4);
-                    if (4 * lane < o + nfl) {
-                        *reinterpret_cast<float4*>(&raw[wv][0][4 * lane]) = *reinterpret_cast<const float4*>(fa + s4 + 4 * lane);
-                        *reinterpret_cast<float4*>(&raw[wv][1][4 * lane]) = *reinterpret_cast<const float4*>(fb + s4 + 4 * lane);
-                    }
-                } else {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const int i = lane + 64 * k;
-                        if (i < nfl) {
-                            raw[wv][0][i] = fa[s + i];
-                            raw[wv][1][i] = fb[s + i];
-                        }
-                    }
-                }
+                o = stage_row<WIDE>(raw[wv], fa, fb, s, nfl, lane);
             }
             __syncthreads();
             // ---- convert (+ SSE)
@@ -132,55 +99,21 @@ k_metric(const float* __restrict__ a, const float* __restrict__ b, int H, int W,
                             }
                         }
                         if (SSIM && !YMODE) {
-                            const float va = qa[p], vb = qb[p];
-                            xs[wv][0][j] = (double)(QUANT ? quant(va) : va);
-                            xs[wv][1][j] = (double)(QUANT ? quant(vb) : vb);
+                            xs[wv][0][j] = level1<false, QUANT>(qa, p, lu);
+                            xs[wv][1][j] = level1<false, QUANT>(qb, p, lu);
                         }
                     }
                 }
             }
             if (SSIM) {
                 __syncthreads();
-                // ---- rows: five 11-tap sums into the ring
-                if (row_on && lane < ncols_out) {
-                    double sa = 0.0, sb = 0.0, saa = 0.0, sbb = 0.0, sab = 0.0;
-#pragma unroll
-                    for (int k = 0; k < K; ++k) {
-                        const double va = xs[wv][0][lane + k], vb = xs[wv][1][lane + k];
-                        const double paa = va * va, pbb = vb * vb, pab = va * vb;
-                        sa = __builtin_fma(win.w[k], va, sa);
-                        sb = __builtin_fma(win.w[k], vb, sb);
-                        saa = __builtin_fma(win.w[k], paa, saa);
-                        sbb = __builtin_fma(win.w[k], pbb, sbb);
-                        sab = __builtin_fma(win.w[k], pab, sab);
-                    }
-                    const int slot = ri % RING;
-                    ring[slot][0][lane] = sa;
-                    ring[slot][1][lane] = sb;
-                    ring[slot][2][lane] = saa;
-                    ring[slot][3][lane] = sbb;
-                    ring[slot][4][lane] = sab;
-                }
+                if (row_on && lane < ncols_out) row_pass(win, &xs[wv][0][lane], &xs[wv][1][lane], ring[ri % RING], lane);
                 __syncthreads();
-                // ---- columns: map row q needs input rows q .. q + 10, all in the ring once row 4 t + 3 is
                 const int q = t * NW + wv - (K - 1);
                 if (q >= 0 && q < nrows_out && lane < ncols_out) {
-                    double ma = 0.0, mb = 0.0, eaa = 0.0, ebb = 0.0, eab = 0.0;
-                    int slot = q % RING;
-#pragma unroll
-                    for (int k = 0; k < K; ++k) {
-                        ma = __builtin_fma(win.w[k], ring[slot][0][lane], ma);
-                        mb = __builtin_fma(win.w[k], ring[slot][1][lane], mb);
-                        eaa = __builtin_fma(win.w[k], ring[slot][2][lane], eaa);
-                        ebb = __builtin_fma(win.w[k], ring[slot][3][lane], ebb);
-                        eab = __builtin_fma(win.w[k], ring[slot][4][lane], eab);
-                        slot = slot + 1 == RING ? 0 : slot + 1;
-                    }
-                    const double maa = ma * ma, mbb = mb * mb, mab = ma * mb;
-                    const double s_aa = eaa - maa, s_bb = ebb - mbb, s_ab = eab - mab;
-                    ssim += ((2.0 * mab + C1) * (2.0 * s_ab + C2)) / (((maa + mbb) + C1) * ((s_aa + s_bb) + C2));
+                    const Terms m = column_pass(win, ring, q, lane);
+                    ssim += (m.num_l * m.num_cs) / (m.den_l * m.den_cs);
                 }
-                // (the next step's ring stores come after its first two barriers: every read above has been issued by then)
             }
         }
         __syncthreads();   // a pass is over: the ring and the staging rows are free for the next plane
@@ -192,7 +125,7 @@ __global__ void __launch_bounds__(FT)
 k_finish(const double* __restrict__ ws, double* __restrict__ sums, unsigned nwg, int what, double n_sse, double n_ssim) {
     __shared__ double red[2][FT];
     const int tid = threadIdx.x;
-    vsr::sums::finish_pair<FT>(ws, nwg, red, tid);
+    vsr::sums::finish_pair<FT>(ws + (size_t)blockIdx.x * nwg * 2, 0, nwg, red, tid);
     if (tid == 0) {
         double* out = sums + (size_t)blockIdx.x * 4;
         out[0] = (what & VSR_METRIC_SSE) ? red[0][0] : 0.0;
@@ -223,16 +156,6 @@ int check_shape(int F, int H, int W, int shave, int what, Geometry* g) {
     return VSR_OK;
 }
 
-template <bool SSIM, bool YMODE>
-void launch(bool quant, bool wide, dim3 grid, hipStream_t s, const float* a, const float* b, int H, int W, int shave, int want_sse,
-            const Luma& lu, const Win& win, double* ws) {
-    const dim3 block(NW * 64);
-    if (quant && wide) hipLaunchKernelGGL((k_metric<SSIM, YMODE, true, true>), grid, block, 0, s, a, b, H, W, shave, want_sse, lu, win, ws);
-    else if (quant) hipLaunchKernelGGL((k_metric<SSIM, YMODE, true, false>), grid, block, 0, s, a, b, H, W, shave, want_sse, lu, win, ws);
-    else if (wide) hipLaunchKernelGGL((k_metric<SSIM, YMODE, false, true>), grid, block, 0, s, a, b, H, W, shave, want_sse, lu, win, ws);
-    else hipLaunchKernelGGL((k_metric<SSIM, YMODE, false, false>), grid, block, 0, s, a, b, H, W, shave, want_sse, lu, win, ws);
-}
-
 }  // namespace
 
 extern "C" {
@@ -248,25 +171,18 @@ size_t vsr_metric_ws_bytes(int F, int H, int W, int shave, int what) {
 
 int vsr_metric_frames(const float* a, const float* b, int F, int H, int W, int what, int channels, int quantise, int shave,
                       const float* luma4, const double* win11, double* sums, void* ws, vsr_stream_t stream) {
-    VSR_REQUIRE(a && b && sums && ws, "metric_frames: null pointer");
+    const char* who = "metric_frames";
     Geometry g;
-    const int rc0 = check_shape(F, H, W, shave, what, &g);
-    if (rc0) return rc0;
+    bool wide;
+    if (int rc = check_pointers(who, a, b, sums, ws)) return rc;
+    if (int rc = check_shape(F, H, W, shave, what, &g)) return rc;
     VSR_REQUIRE(channels == VSR_METRIC_RGB || channels == VSR_METRIC_Y, "metric_frames: unknown channels %d", channels);
-    VSR_REQUIRE(quantise == 0 || quantise == 1, "metric_frames: quantise must be 0 or 1, got %d", quantise);
+    if (int rc = check_quantise(who, quantise)) return rc;
     const bool ssim = (what & VSR_METRIC_SSIM) != 0, ymode = channels == VSR_METRIC_Y;
     VSR_REQUIRE(!ssim || win11, "metric_frames: null win11 with SSIM asked for");
-    VSR_REQUIRE(!ymode || luma4, "metric_frames: null luma4 in Y mode");
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    VSR_REQUIRE(((pa | pb) & 3) == 0, "metric_frames: the frames must be 4-byte aligned");
-    VSR_REQUIRE(((reinterpret_cast<uintptr_t>(sums) | reinterpret_cast<uintptr_t>(ws)) & 7) == 0,
-                "metric_frames: sums and the workspace must be 8-byte aligned");
-    Win win = {};
-    if (ssim)
-        for (int i = 0; i < K; ++i) win.w[i] = win11[i];
+    if (int rc = check_frames(who, ymode, luma4, a, b, W, sums, ws, &wide)) return rc;
+    const Win win = ssim ? win_of(win11) : Win{};
     const Luma lu = ymode ? vsr::sums::luma_of(luma4) : Luma{};
-    // 16-byte loads: both bases aligned and a row pitch (so a frame) of a whole number of 16-byte groups
-    const bool wide = ((pa | pb) & 15) == 0 && W % 4 == 0;
     const int planes = ymode ? 1 : 3;
     const double hw = (double)(H - 2 * shave) * (double)(W - 2 * shave);
     const double n_sse = planes * hw, n_ssim = ssim ? planes * ((double)g.mh * (double)g.mw) : 0.0;
@@ -274,10 +190,12 @@ int vsr_metric_frames(const float* a, const float* b, int F, int H, int W, int w
     hipStream_t s = vsr::S(stream);
     const int want_sse = what & VSR_METRIC_SSE;
     double* wsd = static_cast<double*>(ws);
-    if (ssim && ymode) launch<true, true>(quantise, wide, grid, s, a, b, H, W, shave, want_sse, lu, win, wsd);
-    else if (ssim) launch<true, false>(quantise, wide, grid, s, a, b, H, W, shave, want_sse, lu, win, wsd);
-    else if (ymode) launch<false, true>(quantise, wide, grid, s, a, b, H, W, shave, want_sse, lu, win, wsd);
-    else launch<false, false>(quantise, wide, grid, s, a, b, H, W, shave, want_sse, lu, win, wsd);
+    dispatch(ssim, ymode, [&](auto S_, auto Y_) {
+        dispatch(quantise != 0, wide, [&](auto Q_, auto W_) {
+            hipLaunchKernelGGL((k_metric<decltype(S_)::value, decltype(Y_)::value, decltype(Q_)::value, decltype(W_)::value>), grid,
+                               dim3(NW * 64), 0, s, a, b, H, W, shave, want_sse, lu, win, wsd);
+        });
+    });
     const int rc = vsr::launched("metric_frames/tiles");
     if (rc) return rc;
     hipLaunchKernelGGL(k_finish, dim3(F), dim3(FT), 0, s, (const double*)wsd, sums, g.strips * g.segs, what, n_sse, n_ssim);

@@ -9,19 +9,18 @@
 //               value of each plane and frame from its 2 x 2 pixels (quantise, luma or channel, to double); levels 3 to 5 follow from
 //               LDS with 64, 16 and 4 threads.  Every value goes to the workspace as a double; level 1 never does.
 //   k_score   : one workgroup (4 waves) = one tile of SW = 64 map columns x SR = 64 map rows of ONE level of one frame; the grid's x
-//               runs over the tiles of level 1, then level 2, ... level 5.  The march over the tile's rows, the LDS ring of row-filtered
-//               sums and the column pass restate k_metric of frame_metric.hip; a level-1 tile stages and converts the float32 frames
-//               (load, convert), a tile of a higher level reads its row of doubles from the workspace straight into the converted
-//               row.  RGB runs the march once per plane with one ring.  Two running sums per thread (cs, ssim), at the end a
-//               fixed-order tree over the 256 threads and one pair of doubles per plane into the workspace.
+//               runs over the tiles of level 1, then level 2, ... level 5.  The tile is scored by the march of frame_ssim.h, the one
+//               k_metric of frame_metric.hip runs: a level-1 tile stages and converts the float32 frames (load, convert), a tile of a
+//               higher level reads its row of doubles from the workspace straight into the converted row.  Two running sums per
+//               thread (cs, ssim), at the end of a plane's pass a fixed-order tree over the 256 threads and one pair of doubles per
+//               plane into the workspace.
 //   k_finish  : one workgroup of 64 threads per (level, plane, frame): thread t adds the level's partials t, t + 64, ... in that order,
 //               then the same tree; thread 0 writes the two numbers.
 // Nothing here is atomic and no order depends on timing or on F: a frame's numbers are the same bits in every run.
 //
 // The whole file is compiled without floating-point contraction (Makefile and the pragma below): luma, the 2 x 2 mean and the two
 // formulas round operation by operation as the header writes them; the window sums ask for their fmas by name.
-#include "frame_sums.h"
-#include "vsr_common.h"
+#include "frame_ssim.h"
 
 #include "../../include/vsr_hip_msssim.h"
 
@@ -29,22 +28,12 @@
 
 namespace {
 
-using vsr::sums::Luma;
-using vsr::sums::quant;
+using namespace vsr::ssim;
 
 constexpr int NL = VSR_MSSSIM_LEVELS;
-constexpr int PR = VSR_MSSSIM_PYR_ROWS, PC = VSR_MSSSIM_PYR_COLS;
-constexpr int SW = VSR_MSSSIM_STRIP_WIDTH, SR = VSR_MSSSIM_SEGMENT_ROWS, FT = VSR_MSSSIM_FINISH_THREADS;
-constexpr int NW = 4;              // waves per workgroup = input rows per step
-constexpr int K = 11;              // window taps
-constexpr int RING = NW + K - 1;   // ring rows: the 11 rows of the oldest map row of a step up to the newest input row
-constexpr int RAW = 256;           // floats of one staged row: 74 x 3 = 222, + 3 before an aligned start, rounded up to 64 lanes x 4
-constexpr int XS = 80;             // doubles of one converted row (74 used)
+constexpr int PR = VSR_MSSSIM_PYR_ROWS, PC = VSR_MSSSIM_PYR_COLS, FT = VSR_MSSSIM_FINISH_THREADS;
 constexpr int PYR = 8 * 32 + 4 * 16 + 2 * 8 + 1 * 4;   // doubles of one plane's descendants of a pyramid tile
-
-struct Win {
-    double w[K];
-};
+static_assert(VSR_MSSSIM_STRIP_WIDTH == SW && VSR_MSSSIM_SEGMENT_ROWS == SR, "the header's tile is the march's");
 
 // the five levels of one call: sizes, where a level's pooled planes start inside one plane's block of the workspace (levels 2 to 5),
 // and the scoring tiles, numbered level by level
@@ -53,33 +42,6 @@ struct Plan {
     unsigned strips[NL], t0[NL + 1];
     unsigned long long off[NL], plane_doubles;   // off[0] is unused: level 1 is the frames themselves
 };
-
-// a row's `nfl` floats starting at float `s` of frame `f` into raw[]; returns where the row starts in raw[]
-template <bool WIDE>
-__device__ inline int stage_row(float* raw, const float* __restrict__ f, size_t s, int nfl, int lane) {
-    if (WIDE) {
-        const size_t s4 = s & ~(size_t)3;   // H * W * 3 is a multiple of 4: an aligned group ends inside the frame
-        const int o = (int)(s - s4);
-        if (4 * lane < o + nfl) *reinterpret_cast<float4*>(&raw[4 * lane]) = *reinterpret_cast<const float4*>(f + s4 + 4 * lane);
-        return o;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int i = lane + 64 * k;
-        if (i < nfl) raw[i] = f[s + i];
-    }
-    return 0;
-}
-
-// plane `p` of the pixel at q[0..2] as the double of level 1 (Y: the luma; RGB: channel p)
-template <bool YMODE, bool QUANT>
-__device__ inline double level1(const float* q, int p, const Luma& lu) {
-    if (YMODE) {
-        const float r = QUANT ? quant(q[0]) : q[0], g = QUANT ? quant(q[1]) : q[1], b = QUANT ? quant(q[2]) : q[2];
-        return vsr::sums::luma(lu, r, g, b);
-    }
-    return (double)(QUANT ? quant(q[p]) : q[p]);
-}
 
 template <bool YMODE, bool QUANT, bool WIDE>
 __global__ void __launch_bounds__(NW * 64)
@@ -101,8 +63,7 @@ k_pyramid(const float* __restrict__ a, const float* __restrict__ b, int H, int W
         const int r = wv * (PR / NW) + k;
         if (r < n1r) {
             const size_t s = ((size_t)(shave + y0 + r) * W + shave + x0) * 3;
-            const int o = stage_row<WIDE>(raw[r][0], fa, s, n1c * 3, lane);
-            stage_row<WIDE>(raw[r][1], fb, s, n1c * 3, lane);
+            const int o = stage_row<WIDE>(raw[r], fa, fb, s, n1c * 3, lane);
             if (lane == 0) start[r] = o;
         }
     }
@@ -152,7 +113,6 @@ k_score(const float* __restrict__ a, const float* __restrict__ b, int H, int W, 
         const double* __restrict__ pyr, double* __restrict__ part) {
     constexpr int P = YMODE ? 1 : 3;
     constexpr int HALO = K - 1;
-    constexpr double C1 = (0.01 * 255) * (0.01 * 255), C2 = (0.03 * 255) * (0.03 * 255);
     __shared__ __align__(16) float raw[NW][2][RAW];
     __shared__ double xs[NW][2][XS];
     __shared__ double ring[RING][5][SW];
@@ -187,8 +147,7 @@ k_score(const float* __restrict__ a, const float* __restrict__ b, int H, int W, 
                 // ---- load
                 if (row_on) {
                     const size_t s = ((size_t)(shave + oy0 + ri) * W + shave + ox0) * 3;
-                    o = stage_row<WIDE>(raw[wv][0], fa, s, nfl, lane);
-                    stage_row<WIDE>(raw[wv][1], fb, s, nfl, lane);
+                    o = stage_row<WIDE>(raw[wv], fa, fb, s, nfl, lane);
                 }
                 __syncthreads();
                 // ---- convert
@@ -215,55 +174,19 @@ k_score(const float* __restrict__ a, const float* __restrict__ b, int H, int W, 
                 }
             }
             __syncthreads();
-            // ---- rows: five 11-tap sums into the ring
-            if (row_on && lane < ncols_out) {
-                double sa = 0.0, sb = 0.0, saa = 0.0, sbb = 0.0, sab = 0.0;
-#pragma unroll
-                for (int k = 0; k < K; ++k) {
-                    const double va = xs[wv][0][lane + k], vb = xs[wv][1][lane + k];
-                    const double paa = va * va, pbb = vb * vb, pab = va * vb;
-                    sa = __builtin_fma(win.w[k], va, sa);
-                    sb = __builtin_fma(win.w[k], vb, sb);
-                    saa = __builtin_fma(win.w[k], paa, saa);
-                    sbb = __builtin_fma(win.w[k], pbb, sbb);
-                    sab = __builtin_fma(win.w[k], pab, sab);
-                }
-                const int slot = ri % RING;
-                ring[slot][0][lane] = sa;
-                ring[slot][1][lane] = sb;
-                ring[slot][2][lane] = saa;
-                ring[slot][3][lane] = sbb;
-                ring[slot][4][lane] = sab;
-            }
+            if (row_on && lane < ncols_out) row_pass(win, &xs[wv][0][lane], &xs[wv][1][lane], ring[ri % RING], lane);
             __syncthreads();
-            // ---- columns: map row q needs input rows q .. q + 10, all in the ring once row 4 t + 3 is
             const int q = t * NW + wv - (K - 1);
             if (q >= 0 && q < nrows_out && lane < ncols_out) {
-                double ma = 0.0, mb = 0.0, eaa = 0.0, ebb = 0.0, eab = 0.0;
-                int slot = q % RING;
-#pragma unroll
-                for (int k = 0; k < K; ++k) {
-                    ma = __builtin_fma(win.w[k], ring[slot][0][lane], ma);
-                    mb = __builtin_fma(win.w[k], ring[slot][1][lane], mb);
-                    eaa = __builtin_fma(win.w[k], ring[slot][2][lane], eaa);
-                    ebb = __builtin_fma(win.w[k], ring[slot][3][lane], ebb);
-                    eab = __builtin_fma(win.w[k], ring[slot][4][lane], eab);
-                    slot = slot + 1 == RING ? 0 : slot + 1;
-                }
-                const double maa = ma * ma, mbb = mb * mb, mab = ma * mb;
-                const double s_aa = eaa - maa, s_bb = ebb - mbb, s_ab = eab - mab;
-                const double num_cs = 2.0 * s_ab + C2, den_cs = (s_aa + s_bb) + C2;
-                cs += num_cs / den_cs;
-                ssim += ((2.0 * mab + C1) * num_cs) / (((maa + mbb) + C1) * den_cs);
+                const Terms m = column_pass(win, ring, q, lane);
+                cs += m.num_cs / m.den_cs;
+                ssim += (m.num_l * m.num_cs) / (m.den_l * m.den_cs);
             }
             // (the next step's ring stores come after a barrier of that step, two at level 1: every read above has been issued by
             // then; xs[wv] is written and read by wave wv alone)
         }
         // ---- a pass is over: the threads' sums through the tree, one pair per plane
-        red[0][tid] = cs;
-        red[1][tid] = ssim;
-        vsr::sums::tree<NW * 64>(red[0], tid);
-        vsr::sums::tree<NW * 64>(red[1], tid);
+        vsr::sums::tree_pair<NW * 64>(red, tid, cs, ssim);
         if (tid == 0) {
             double* out = part + (((size_t)blockIdx.z * P + p) * pl.t0[NL] + blockIdx.x) * 2;
             out[0] = red[0][0];
@@ -279,16 +202,7 @@ k_finish(const double* __restrict__ part, double* __restrict__ sums, Plan pl) {
     __shared__ double red[2][FT];
     const int tid = threadIdx.x, lev = blockIdx.x;
     const size_t fp = (size_t)blockIdx.z * gridDim.y + blockIdx.y;
-    const double* p = part + fp * pl.t0[NL] * 2;
-    double s0 = 0.0, s1 = 0.0;
-    for (unsigned i = pl.t0[lev] + tid; i < pl.t0[lev + 1]; i += FT) {
-        s0 += p[2 * (size_t)i];
-        s1 += p[2 * (size_t)i + 1];
-    }
-    red[0][tid] = s0;
-    red[1][tid] = s1;
-    vsr::sums::tree<FT>(red[0], tid);
-    vsr::sums::tree<FT>(red[1], tid);
+    vsr::sums::finish_pair<FT>(part + fp * pl.t0[NL] * 2, pl.t0[lev], pl.t0[lev + 1], red, tid);
     if (tid == 0) {
         double* out = sums + (fp * NL + lev) * 2;
         out[0] = red[0][0];
@@ -320,25 +234,6 @@ int check_shape(int F, int H, int W, int shave, int channels, Plan* pl) {
     return VSR_OK;
 }
 
-template <bool YMODE>
-void launch(bool quant, bool wide, dim3 pgrid, dim3 sgrid, hipStream_t s, const float* a, const float* b, int H, int W, int shave,
-            const Luma& lu, const Win& win, const Plan& pl, double* pyr, double* part, int* rc) {
-    const dim3 block(NW * 64);
-#define VSR_MSSSIM_LAUNCH(Q, WD)                                                                                              \
-    do {                                                                                                                      \
-        hipLaunchKernelGGL((k_pyramid<YMODE, Q, WD>), pgrid, block, 0, s, a, b, H, W, shave, lu, pl, pyr);                    \
-        *rc = vsr::launched("msssim_frames/pyramid");                                                                         \
-        if (*rc) return;                                                                                                      \
-        hipLaunchKernelGGL((k_score<YMODE, Q, WD>), sgrid, block, 0, s, a, b, H, W, shave, lu, win, pl, (const double*)pyr, part); \
-        *rc = vsr::launched("msssim_frames/tiles");                                                                           \
-    } while (0)
-    if (quant && wide) VSR_MSSSIM_LAUNCH(true, true);
-    else if (quant) VSR_MSSSIM_LAUNCH(true, false);
-    else if (wide) VSR_MSSSIM_LAUNCH(false, true);
-    else VSR_MSSSIM_LAUNCH(false, false);
-#undef VSR_MSSSIM_LAUNCH
-}
-
 }  // namespace
 
 extern "C" {
@@ -355,32 +250,37 @@ size_t vsr_msssim_ws_bytes(int F, int H, int W, int shave, int channels) {
 
 int vsr_msssim_frames(const float* a, const float* b, int F, int H, int W, int channels, int quantise, int shave, const float* luma4,
                       const double* win11, double* sums, void* ws, vsr_stream_t stream) {
-    VSR_REQUIRE(a && b && sums && ws, "msssim_frames: null pointer");
-    VSR_REQUIRE(win11, "msssim_frames: null win11");
+    const char* who = "msssim_frames";
     Plan pl;
-    const int rc0 = check_shape(F, H, W, shave, channels, &pl);
-    if (rc0) return rc0;
-    VSR_REQUIRE(quantise == 0 || quantise == 1, "msssim_frames: quantise must be 0 or 1, got %d", quantise);
+    bool wide;
+    if (int rc = check_pointers(who, a, b, sums, ws)) return rc;
+    VSR_REQUIRE(win11, "msssim_frames: null win11");
+    if (int rc = check_shape(F, H, W, shave, channels, &pl)) return rc;
+    if (int rc = check_quantise(who, quantise)) return rc;
     const bool ymode = channels == VSR_MSSSIM_Y;
-    VSR_REQUIRE(!ymode || luma4, "msssim_frames: null luma4 in Y mode");
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    VSR_REQUIRE(((pa | pb) & 3) == 0, "msssim_frames: the frames must be 4-byte aligned");
-    VSR_REQUIRE(((reinterpret_cast<uintptr_t>(sums) | reinterpret_cast<uintptr_t>(ws)) & 7) == 0,
-                "msssim_frames: sums and the workspace must be 8-byte aligned");
-    Win win;
-    for (int i = 0; i < K; ++i) win.w[i] = win11[i];
+    if (int rc = check_frames(who, ymode, luma4, a, b, W, sums, ws, &wide)) return rc;
+    const Win win = win_of(win11);
     const Luma lu = ymode ? vsr::sums::luma_of(luma4) : Luma{};
-    // 16-byte loads: both bases aligned and a row pitch (so a frame) of a whole number of 16-byte groups
-    const bool wide = ((pa | pb) & 15) == 0 && W % 4 == 0;
     const int P = ymode ? 1 : 3;
     // the workspace: the pooled planes [F][2][P][plane_doubles], then the partials [F][P][tiles][2]
     double* pyr = static_cast<double*>(ws);
     double* part = pyr + (size_t)F * 2 * P * pl.plane_doubles;
-    const dim3 pgrid(vsr::cdiv(pl.w[0], PC), vsr::cdiv(pl.h[0], PR), F), sgrid(pl.t0[NL], 1, F);
+    const dim3 pgrid(vsr::cdiv(pl.w[0], PC), vsr::cdiv(pl.h[0], PR), F), sgrid(pl.t0[NL], 1, F), block(NW * 64);
     hipStream_t s = vsr::S(stream);
     int rc = VSR_OK;
-    if (ymode) launch<true>(quantise, wide, pgrid, sgrid, s, a, b, H, W, shave, lu, win, pl, pyr, part, &rc);
-    else launch<false>(quantise, wide, pgrid, sgrid, s, a, b, H, W, shave, lu, win, pl, pyr, part, &rc);
+    dispatch(quantise != 0, wide, [&](auto Q_, auto W_) {
+        constexpr bool Q = decltype(Q_)::value, WD = decltype(W_)::value;
+        const auto both = [&](auto Y_) {
+            constexpr bool Y = decltype(Y_)::value;
+            hipLaunchKernelGGL((k_pyramid<Y, Q, WD>), pgrid, block, 0, s, a, b, H, W, shave, lu, pl, pyr);
+            rc = vsr::launched("msssim_frames/pyramid");
+            if (rc) return;
+            hipLaunchKernelGGL((k_score<Y, Q, WD>), sgrid, block, 0, s, a, b, H, W, shave, lu, win, pl, (const double*)pyr, part);
+            rc = vsr::launched("msssim_frames/tiles");
+        };
+        if (ymode) both(std::true_type{});
+        else both(std::false_type{});
+    });
     if (rc) return rc;
     hipLaunchKernelGGL(k_finish, dim3(NL, P, F), dim3(FT), 0, s, (const double*)part, sums, pl);
     return vsr::launched("msssim_frames/finish");

@@ -1,9 +1,10 @@
 // frame_sums.h -- the device helpers the float64-sum kernels share: quantisation as write-out does it, the luma of "y" mode, the
 // fixed-order tree, and the two halves of "one pair of doubles per workgroup, then a finish kernel adds the partials".
 //
-// For frame_metric.hip, frame_warp_error.hip, frame_resize.hip, train_update.hip and clip_scene.hip ONLY: the sources compiled with -ffp-contract=off
-// (Makefile) that state the pragma themselves, whose results the tests pin bit for bit.  Every operation below rounds once, in the
-// order written, as it did when each of those sources held its own copy; no source built with contraction includes this header.
+// For frame_metric.hip, frame_msssim.hip (both also through frame_ssim.h), frame_warp_error.hip, frame_resize.hip, train_update.hip and
+// clip_scene.hip ONLY: the sources compiled with -ffp-contract=off (Makefile) that state the pragma themselves, whose results the tests
+// pin bit for bit.  Every operation below rounds once, in the order written, as it did when each of those sources held its own copy; no
+// source built with contraction includes this header.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -39,14 +40,20 @@ __device__ inline void tree(double* red, int tid) {
     __syncthreads();
 }
 
-// the end of a tile kernel of N threads: the threads' two running sums through the tree, one pair of doubles per workgroup into the
-// workspace, workgroups numbered x fastest, then y, then z
+// two running sums per thread of a workgroup of N, each through the tree; the totals end in red[0][0] and red[1][0]
 template <int N>
-__device__ inline void workgroup_pair(double (*red)[N], int tid, double s0, double s1, double* ws) {
+__device__ inline void tree_pair(double (*red)[N], int tid, double s0, double s1) {
     red[0][tid] = s0;
     red[1][tid] = s1;
     tree<N>(red[0], tid);
     tree<N>(red[1], tid);
+}
+
+// the end of a tile kernel of N threads: the threads' two running sums through the tree, one pair of doubles per workgroup into the
+// workspace, workgroups numbered x fastest, then y, then z
+template <int N>
+__device__ inline void workgroup_pair(double (*red)[N], int tid, double s0, double s1, double* ws) {
+    tree_pair<N>(red, tid, s0, s1);
     if (tid == 0) {
         const size_t wg = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
         ws[2 * wg] = red[0][0];
@@ -54,20 +61,16 @@ __device__ inline void workgroup_pair(double (*red)[N], int tid, double s0, doub
     }
 }
 
-// the body of a finish kernel of FT threads, one workgroup per frame or pair (blockIdx.x) over its nwg pairs: thread t adds the
-// partials t, t + FT, ... in that order, then the same tree; the two totals end in red[0][0] and red[1][0], for thread 0's epilogue
+// the body of a finish kernel of FT threads, one workgroup per sum over the pairs [i0, i1) of `p`: thread t adds the partials i0 + t,
+// i0 + t + FT, ... in that order, then the same tree; the two totals end in red[0][0] and red[1][0], for thread 0's epilogue
 template <int FT>
-__device__ inline void finish_pair(const double* ws, unsigned nwg, double (*red)[FT], int tid) {
-    const double* p = ws + (size_t)blockIdx.x * nwg * 2;
+__device__ inline void finish_pair(const double* p, unsigned i0, unsigned i1, double (*red)[FT], int tid) {
     double s0 = 0.0, s1 = 0.0;
-    for (unsigned i = tid; i < nwg; i += FT) {
+    for (unsigned i = i0 + tid; i < i1; i += FT) {
         s0 += p[2 * (size_t)i];
         s1 += p[2 * (size_t)i + 1];
     }
-    red[0][tid] = s0;
-    red[1][tid] = s1;
-    tree<FT>(red[0], tid);
-    tree<FT>(red[1], tid);
+    tree_pair<FT>(red, tid, s0, s1);
 }
 
 }  // namespace sums

@@ -123,7 +123,7 @@ __global__ void __launch_bounds__(FT)
 k_finish(const double* __restrict__ ws, double* __restrict__ sums, unsigned nwg, double planes, double n_pixels) {
     __shared__ double red[2][FT];
     const int tid = threadIdx.x;
-    vsr::sums::finish_pair<FT>(ws, nwg, red, tid);
+    vsr::sums::finish_pair<FT>(ws + (size_t)blockIdx.x * nwg * 2, 0, nwg, red, tid);
     if (tid == 0) {
         double* out = sums + (size_t)blockIdx.x * 4;
         out[0] = red[0][0];

@@ -295,12 +295,12 @@ def _luma4(channels: str, matrix: str, full_range: bool) -> Optional[np.ndarray]
     return np.ascontiguousarray(np.array([c[0], c[1], c[2], c[9]], dtype=np.float32))
 
 
-def _sums_out(out: Optional[torch.Tensor], n: int, device) -> torch.Tensor:
-    """The [n,4] float64 tensor the sums go to: `out` if it fits (rows of a larger tensor will do), else a new one."""
+def _sums_out(out: Optional[torch.Tensor], shape: tuple, device) -> torch.Tensor:
+    """The float64 tensor of `shape` the sums go to: `out` if it fits (rows of a larger tensor will do), else a new one."""
     if out is None:
-        return torch.empty((n, 4), dtype=torch.float64, device=device)
-    if tuple(out.shape) != (n, 4) or out.device != device:
-        raise ValueError(f"out must be float64 {(n, 4)} on {device}, got {tuple(out.shape)} on {out.device}")
+        return torch.empty(shape, dtype=torch.float64, device=device)
+    if tuple(out.shape) != shape or out.device != device:
+        raise ValueError(f"out must be float64 {shape} on {device}, got {tuple(out.shape)} on {out.device}")
     return out
 
 
@@ -308,6 +308,29 @@ def _sums_array(sums) -> np.ndarray:
     """Sums [n,4] (a tensor, copied to the host here, or an array) as a float64 array [n,4]."""
     s = sums.detach().cpu().numpy() if isinstance(sums, torch.Tensor) else np.asarray(sums)
     return np.asarray(s, dtype=np.float64).reshape(-1, 4)
+
+
+def _score_frames(name: str, a, b, quantise, shave, refuse, luma4, out, out_shape: tuple, head: tuple) -> torch.Tensor:
+    """What `frame_metrics` (name "metric") and `frame_msssim` ("msssim") do alike around vsr_<name>_frames: the frame pair, the shave
+    and the size (`refuse(H, W, shave)` raises what the entry would refuse), the window, the device pointers, the sums [F] + `out_shape`
+    and the workspace.  `head`: the entry's arguments between W and quantise; the first of them is also vsr_<name>_ws_bytes' last."""
+    import ctypes
+    fa, fb = _frame_pair(a, b, "F")
+    shave = int(shave)
+    F, H, W = int(fa.shape[0]), int(fa.shape[1]), int(fa.shape[2])
+    refuse(H, W, shave)
+    win = ssim_window()
+    M = getattr(L, "load_" + name)()
+    pa, pb = L.dptr(fa), L.dptr(fb)   # (raises on CPU tensors and on anything but float32)
+    if fb.device != fa.device:
+        raise ValueError("the two tensors live on different devices")
+    out = _sums_out(out, (F,) + out_shape, fa.device)
+    ws = torch.empty(int(getattr(M, f"vsr_{name}_ws_bytes")(F, H, W, shave, head[0])), dtype=torch.uint8, device=fa.device)
+    L.check(getattr(M, f"vsr_{name}_frames")(pa, pb, F, H, W, *head, 1 if quantise else 0, shave,
+                                             None if luma4 is None else luma4.ctypes.data_as(ctypes.c_void_p),
+                                             win.ctypes.data_as(ctypes.c_void_p), L.dptr(out, torch.float64), L.dptr(ws, torch.uint8),
+                                             L.stream()), name + "_frames", lib=M)
+    return out
 
 
 @L.on_device
@@ -318,7 +341,6 @@ def frame_metrics(a: torch.Tensor, b: torch.Tensor, channels: str = "rgb", quant
     `quantise`: score what write-out stores (clamp to 0..255, round half to even); `shave`: pixels dropped on every side;
     `channels="y"`: on the luma of `matrix` / `full_range` (row 0 of `yuv_coefficients`; the default is BT.601 limited range, the
     literature's "Y"); `what`: "psnr" and / or "ssim" (the slots of the other are 0); `out`: write the sums there ([F,4] float64)."""
-    import ctypes
     code = _channel_code(channels)
     names = (what,) if isinstance(what, str) else tuple(what)
     if not names or any(n not in METRIC_WHAT for n in names):
@@ -326,25 +348,14 @@ def frame_metrics(a: torch.Tensor, b: torch.Tensor, channels: str = "rgb", quant
     bits = 0
     for n in names:
         bits |= METRIC_WHAT[n]
-    fa, fb = _frame_pair(a, b, "F")
-    shave = int(shave)
-    F, H, W = int(fa.shape[0]), int(fa.shape[1]), int(fa.shape[2])
-    if shave < 0 or 2 * shave >= min(H, W):
-        raise ValueError(f"shave {shave} leaves nothing of {H} x {W}")
-    if bits & 2 and min(H, W) - 2 * shave < 11:
-        raise ValueError(f"SSIM needs 11 pixels each way after the shave, got {min(H, W) - 2 * shave}")
-    luma4 = _luma4(channels, matrix, full_range)
-    win = ssim_window()
-    M = L.load_metric()
-    pa, pb = L.dptr(fa), L.dptr(fb)   # (raises on CPU tensors and on anything but float32)
-    if fb.device != fa.device:
-        raise ValueError("the two tensors live on different devices")
-    out = _sums_out(out, F, fa.device)
-    ws = torch.empty(int(M.vsr_metric_ws_bytes(F, H, W, shave, bits)), dtype=torch.uint8, device=fa.device)
-    L.check(M.vsr_metric_frames(pa, pb, F, H, W, bits, code, 1 if quantise else 0, shave,
-                                None if luma4 is None else luma4.ctypes.data_as(ctypes.c_void_p), win.ctypes.data_as(ctypes.c_void_p),
-                                L.dptr(out, torch.float64), L.dptr(ws, torch.uint8), L.stream()), "metric_frames", lib=M)
-    return out
+
+    def refuse(H, W, shave):
+        if shave < 0 or 2 * shave >= min(H, W):
+            raise ValueError(f"shave {shave} leaves nothing of {H} x {W}")
+        if bits & 2 and min(H, W) - 2 * shave < 11:
+            raise ValueError(f"SSIM needs 11 pixels each way after the shave, got {min(H, W) - 2 * shave}")
+
+    return _score_frames("metric", a, b, quantise, shave, refuse, _luma4(channels, matrix, full_range), out, (4,), (bits, code))
 
 
 def psnr_ssim(sums) -> Tuple[np.ndarray, np.ndarray]:
@@ -385,33 +396,18 @@ def frame_msssim(a: torch.Tensor, b: torch.Tensor, channels: str = "rgb", quanti
     {cs_sum, ssim_sum} per frame, plane (P = 3 for "rgb", 1 for "y") and level (vsr_msssim_frames); nothing is synchronised, `msssim`
     is the host step.  `quantise`, `shave`, `channels`: as `frame_metrics`; `luma4`: four float32 {a0, a1, a2, o} of the luma of "y"
     mode, default the BT.601 limited-range luma of `frame_metrics`; `out`: write the sums there ([F,P,5,2] float64)."""
-    import ctypes
     code = _channel_code(channels)
-    fa, fb = _frame_pair(a, b, "F")
-    shave = int(shave)
-    F, H, W = int(fa.shape[0]), int(fa.shape[1]), int(fa.shape[2])
-    if shave < 0 or min(H, W) - 2 * shave < MSSSIM_MIN_SIZE:
-        raise ValueError(f"MS-SSIM needs {MSSSIM_MIN_SIZE} pixels each way after the shave, got {min(H, W) - 2 * shave} "
-                         f"(shave {shave} of {H} x {W})")
+
+    def refuse(H, W, shave):
+        if shave < 0 or min(H, W) - 2 * shave < MSSSIM_MIN_SIZE:
+            raise ValueError(f"MS-SSIM needs {MSSSIM_MIN_SIZE} pixels each way after the shave, got {min(H, W) - 2 * shave} "
+                             f"(shave {shave} of {H} x {W})")
+
     if channels == "y":
         luma4 = _luma4("y", "bt601", False) if luma4 is None else np.ascontiguousarray(np.asarray(luma4, dtype=np.float32).reshape(4))
     else:
         luma4 = None
-    win = ssim_window()
-    M = L.load_msssim()
-    pa, pb = L.dptr(fa), L.dptr(fb)   # (raises on CPU tensors and on anything but float32)
-    if fb.device != fa.device:
-        raise ValueError("the two tensors live on different devices")
-    shape = (F, 1 if channels == "y" else 3, len(MSSSIM_BETA), 2)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float64, device=fa.device)
-    elif tuple(out.shape) != shape or out.device != fa.device:
-        raise ValueError(f"out must be float64 {shape} on {fa.device}, got {tuple(out.shape)} on {out.device}")
-    ws = torch.empty(int(M.vsr_msssim_ws_bytes(F, H, W, shave, code)), dtype=torch.uint8, device=fa.device)
-    L.check(M.vsr_msssim_frames(pa, pb, F, H, W, code, 1 if quantise else 0, shave,
-                                None if luma4 is None else luma4.ctypes.data_as(ctypes.c_void_p), win.ctypes.data_as(ctypes.c_void_p),
-                                L.dptr(out, torch.float64), L.dptr(ws, torch.uint8), L.stream()), "msssim_frames", lib=M)
-    return out
+    return _score_frames("msssim", a, b, quantise, shave, refuse, luma4, out, (1 if channels == "y" else 3, len(MSSSIM_BETA), 2), (code,))
 
 
 def msssim(sums, h: int, w: int) -> np.ndarray:
@@ -502,7 +498,7 @@ def warp_error(a: torch.Tensor, b: torch.Tensor, flows, channels: str = "rgb", q
     pf, pg = L.dptr(fwd, fwd.dtype), L.dptr(bwd, bwd.dtype)
     if any(t.device != fa.device for t in (fb, fwd, bwd)):
         raise ValueError("the frames and the flows live on different devices")
-    out = _sums_out(out, P, fa.device)
+    out = _sums_out(out, (P, 4), fa.device)
     ws = torch.empty(int(M.vsr_warp_ws_bytes(P, h, w, shave)), dtype=torch.uint8, device=fa.device)
     L.check(M.vsr_warp_error(pa, pb, P, H, W, y0, x0, h, w, pf, pg, ftype, strides[0], strides[1], strides[2], code,
                              1 if quantise else 0, shave, None if luma4 is None else luma4.ctypes.data_as(ctypes.c_void_p),
