@@ -9,13 +9,17 @@ Every test that forces a route sets the cross-check library's switches inside a 
 test's own source text: such tests carry `@pytest.mark.xcheck`, and `_switches` restores every knob in a `finally`.
 The routes are asserted from `vsr_last_route()`, so a heuristic change cannot silently move a case to another kernel."""
 import contextlib
+import functools
 import re
 
 import numpy as np
 import pytest
 import torch
 
+import _conv_cases as CC
 import _exact as E
+from _conv_cases import (ACTS, C1_CASES, DECONV_MODES, DECONV_SHAPES, GATHER_ROUTES, PAIR_CASES, PATCH_ROUTES, PATCH_SHAPES, PLAN_CONV, PLAN_DECONV, PLAN_STEM,
+                         SHAPES, SPLIT_K_FILLS, SPLIT_K_SHAPES, STEM_CASES, TILE_SHAPES, TILE_SPLITS, TILE_WIDTHS)
 
 pytestmark = pytest.mark.gpu
 
@@ -23,7 +27,6 @@ from video_super_resolution_amd import _lib as L, igemm, trunk_f32  # noqa: E402
 
 NONE, RELU, LEAKY = igemm.ACT_NONE, igemm.ACT_RELU, igemm.ACT_LEAKY
 _DEFAULTS = (0, 1128, 2001, 4000, 5000, 6001, 7000, 8000, 9001)   # every knob of vsr_conv2d_tuning at its default
-ACTS = ((NONE, 0.1), (RELU, 0.1), (LEAKY, 0.25), (LEAKY, 0.1))     # none, ReLU, Leaky with a dyadic slope, Leaky 0.1 (restated, _exact.leaky_tenth_f16)
 
 
 @contextlib.contextmanager
@@ -97,30 +100,6 @@ def check_nhwc(got, c, what, out_coff=0, sliced=False):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the gather kernel
-SHAPES = [  # (N, cin, H, W, cout, k, stride, pad): ragged in every dimension the kernels tile
-    (1, 1, 5, 7, 1, 3, 1, 1), (2, 31, 9, 6, 2, 3, 1, 1), (1, 33, 6, 11, 17, 3, 1, 1), (1, 65, 7, 5, 65, 1, 1, 0), (1, 97, 4, 9, 129, 3, 2, 1),
-    (1, 64, 1, 23, 32, 3, 1, 1),      # one row
-    (1, 32, 19, 1, 16, 5, 1, 2),      # one column
-    (1, 16, 2, 2, 8, 7, 1, 3),        # an image smaller than the kernel's padding
-    (3, 40, 5, 6, 24, 3, 1, 1),       # batch 3, a different image in each slot
-    (1, 32, 8, 16, 64, 3, 1, 1),      # exactly one 128-pixel tile
-    (1, 32, 3, 43, 64, 3, 1, 1),      # one tile plus one pixel
-    (1, 1026, 4, 6, 2, 3, 1, 1),      # K = 9234: predict_flow (last chunk: channels 1024, 1025)
-    (1, 473, 8, 16, 256, 3, 1, 1),    # FlowNetC conv3_1 (odd channel count), split-K by default
-    (1, 1056, 6, 10, 128, 3, 1, 1),   # 32 k + 0 with a long K
-    (2, 128, 17, 13, 128, 5, 2, 2),   # 5x5 stride 2
-    (1, 12, 11, 9, 64, 11, 1, 5),     # 11x11
-]
-
-GATHER_ROUTES = {  # name -> (switches, pattern of the route string)
-    "default": ((), r"(gather|tile)<"),
-    "gather64": ((2000, 11), r"gather<(16|32|64)>"),
-    "gather128": ((2000, 10), r"gather<"),
-    "first_build": ((8,), r"gather<(16|32|64)>"),
-    "ring5": ((2000, 11, 8002), r"gather<(16|32|64)>"),
-}
-
-
 @pytest.mark.xcheck
 @pytest.mark.parametrize("route", list(GATHER_ROUTES))
 @pytest.mark.parametrize("i", range(len(SHAPES)))
@@ -139,13 +118,13 @@ def test_gather_routes_equal_float64(i, route):
 
 
 @pytest.mark.xcheck
-@pytest.mark.parametrize("shape", [(1, 1026, 4, 6, 2, 3, 1, 1), (1, 473, 8, 16, 256, 3, 1, 1), (2, 512, 7, 9, 320, 3, 2, 1), (1, 97, 4, 9, 129, 3, 2, 1)])
+@pytest.mark.parametrize("shape", SPLIT_K_SHAPES)
 def test_gather_split_k_counts_agree_with_each_other_and_the_reference(shape):
     """Sums are exact, so split-K off, the default and every forced fill threshold (another split count each) give the SAME bits as
     each other and as float64 -- not only run-to-run identity."""
     c = make_conv(7, *shape, act=LEAKY, slope=0.1)
     seen = {}
-    for fill in (1000, 1016, 1064, 1128, 1300, 1999):
+    for fill in SPLIT_K_FILLS:
         with _switches(2000, 11, fill):
             got, r = run_hconv(c)
         assert r.startswith("gather<"), r
@@ -159,13 +138,6 @@ def test_gather_split_k_counts_agree_with_each_other_and_the_reference(shape):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the tile kernel
-TILE_SHAPES = [
-    (1, 256, 9, 13, 512, 3, 2, 1), (1, 473, 8, 16, 256, 3, 1, 1), (1, 33, 11, 12, 65, 3, 1, 1), (3, 160, 9, 7, 192, 1, 1, 0), (1, 1056, 6, 10, 128, 3, 1, 1),
-    (1, 32, 8, 16, 64, 3, 1, 1), (1, 32, 3, 43, 64, 3, 1, 1), (1, 64, 1, 23, 64, 3, 1, 1), (1, 32, 19, 1, 128, 5, 1, 2), (2, 128, 17, 13, 128, 5, 2, 2),
-    (1, 31, 20, 21, 70, 7, 1, 3),
-]
-
-
 @pytest.mark.xcheck
 @pytest.mark.parametrize("i", range(len(TILE_SHAPES)))
 def test_tile_kernel_widths_and_splits_equal_float64(i):
@@ -175,8 +147,8 @@ def test_tile_kernel_widths_and_splits_equal_float64(i):
     c = make_conv(200 + i, *TILE_SHAPES[i], act=act, slope=slope, step=0.25 if i % 4 == 3 else 1.0)
     can128 = igemm._cout_pad(c["cout"]) % 128 == 0
     routes = set()
-    for bn in (64, 128):
-        for splits in (1, 2, 3, 7):
+    for bn in TILE_WIDTHS:
+        for splits in TILE_SPLITS:
             with _switches(2003, 4000 + bn, 5000 + splits):
                 got, r = run_hconv(c)
             assert r.startswith(f"tile<{bn if (bn == 64 or can128) else 64}>"), r
@@ -188,18 +160,6 @@ def test_tile_kernel_widths_and_splits_equal_float64(i):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the LDS-patch kernels
-PATCH_SHAPES = [  # (N, cin, H, W, cout, k): stride 1, pad k // 2; at least 4 x 16 outputs (the launcher's condition), ragged tiles
-    (1, 64, 9, 21, 16, 11), (2, 33, 7, 40, 16, 7), (1, 31, 5, 17, 13, 5), (1, 96, 13, 19, 17, 3), (2, 65, 9, 33, 1, 3), (1, 194, 6, 18, 2, 3),
-    (1, 64, 17, 16, 32, 7), (1, 64, 19, 33, 65, 5), (2, 64, 8, 50, 129, 3), (1, 32, 4, 16, 64, 3), (3, 97, 5, 17, 48, 3),
-]
-PATCH_ROUTES = {
-    "patch_r8": ((2, 2000, 6000, 9000), r"patch_r8<|patch_rows<|patch<"),
-    "patch_lw": ((2, 2000, 6002, 9000), r"patch_lw<|patch_r8<|patch_rows<|patch<"),
-    "patch_pf64": ((2, 2000, 9002), r"patch_pf<|patch_r8<|patch_rows<|patch<"),
-    "patch_pf32": ((2, 2000, 9003), r"patch_pf<|patch_r8<|patch_rows<|patch<"),
-    "patch_rows": ((6, 2000), r"patch_rows<|patch<"),
-    "patch": ((7, 2000), r"patch<"),
-}
 _patch_routes_seen = {}
 
 
@@ -230,8 +190,7 @@ def test_patch_cases_reached_every_build():
 
 # ---------------------------------------------------------------------------------------------------------------- 1x1 streaming
 @pytest.mark.xcheck
-@pytest.mark.parametrize("case", [(1, 128, 259, 271, 208, RELU, 0.1, 0, 0), (1, 96, 300, 230, 77, LEAKY, 0.1, 0, 0), (1, 128, 270, 250, 224, LEAKY, 0.5, 32, 32),
-                                  (3, 33, 160, 140, 129, NONE, 0.1, 0, 0)])
+@pytest.mark.parametrize("case", C1_CASES)
 def test_conv1x1_streaming_and_transposing_builds_equal_float64(case):
     N, cin, H, W, cout, act, slope, coff, extra = case
     c = make_conv(cin + cout, N, cin, H, W, cout, 1, 1, 0, act=act, slope=slope)
@@ -281,8 +240,7 @@ def test_one_unit_in_one_weight_of_k_9234_is_seen_with_its_footprint(modes):
 
 
 # ---------------------------------------------------------------------------------------------------------------- other fp16 layers
-@pytest.mark.parametrize("case", [(2, 3, 13, 17, 128, 7, 1, 3, RELU, 0.1), (2, 3, 20, 30, 64, 7, 2, 3, LEAKY, 0.1), (1, 1, 9, 8, 17, 3, 1, 1, NONE, 0.1),
-                                  (1, 4, 1, 20, 16, 5, 1, 2, LEAKY, 0.5), (1, 3, 270, 250, 128, 7, 1, 3, RELU, 0.1), (3, 2, 5, 1, 65, 7, 1, 3, NONE, 0.1)])
+@pytest.mark.parametrize("case", STEM_CASES)
 def test_stem_convolution_equals_float64(case):
     N, cin, H, W, cout, k, s, p, act, slope = case
     c = make_conv(cout + k, N, cin, H, W, cout, k, s, p, act=act, slope=slope, mag_x=8)
@@ -293,7 +251,7 @@ def test_stem_convolution_equals_float64(case):
     check_nhwc(got, c, f"stem {case} {r}")
 
 
-@pytest.mark.parametrize("case", [(2, 12, 16, 24, 64, 7, 3), (1, 12, 37, 50, 64, 7, 3), (1, 16, 20, 34, 33, 5, 2), (1, 5, 9, 8, 16, 3, 1), (3, 1, 2, 2, 1, 3, 1)])
+@pytest.mark.parametrize("case", PAIR_CASES)
 def test_pair_convolution_stride2_equals_float64(case):
     N, cin, H, W, cout, k, pad = case
     c = make_conv(cin + k + W, N, cin, H, W, cout, k, 2, pad, act=LEAKY, slope=0.1)
@@ -304,14 +262,14 @@ def test_pair_convolution_stride2_equals_float64(case):
 
 
 @pytest.mark.xcheck
-@pytest.mark.parametrize("shape", [(1, 64, 7, 9, 32), (2, 1026, 4, 5, 129), (1, 33, 1, 30, 64), (1, 31, 19, 1, 2), (1, 32, 97, 130, 2), (2, 96, 11, 13, 192)])
+@pytest.mark.parametrize("shape", DECONV_SHAPES)
 def test_transposed_convolution_k4s2_equals_float64(shape):
     """HDeconv4s2: four phases in one launch, through the heuristic's route, the gather kernel and (wide layers) the tile kernel."""
     N, cin, H, W, cout = shape
     c = make_conv(cin + cout, N, cin, H, W, cout, 4, 2, 1, act=LEAKY, slope=0.1, transposed=True)
     dc = igemm.HDeconv4s2(c["w"].float().cuda(), c["b"].float().cuda(), act=LEAKY, slope=0.1)
     xs = E.nhwc(c["x"], torch.float16, igemm.pad32(cin)).cuda()
-    for modes, pat in (((), r"deconv4s2"), ((1,), r"deconv4s2 gather<"), ((2003,), r"deconv4s2 tile<" if cout > 32 else r"deconv4s2")):
+    for modes, pat in zip(DECONV_MODES, (r"deconv4s2", r"deconv4s2 gather<", r"deconv4s2 tile<" if cout > 32 else r"deconv4s2")):
         with _switches(*modes):
             got = dc(xs)
             torch.cuda.synchronize()
@@ -324,8 +282,14 @@ def test_transposed_convolution_k4s2_equals_float64(shape):
             assert _route() == "deconv4s2_patch", _route()
 
 
-@pytest.mark.parametrize("case", [(2, 1024, 8, 15, 0, True, True), (1, 1026, 5, 7, 32, True, False), (1, 194, 33, 40, 32, False, False), (1, 33, 21, 50, 0, True, True),
-                                  (3, 16, 9, 7, 16, False, False), (1, 512, 1, 3, 0, True, False), (1, 31, 6, 1, 0, True, True)])
+FLOW_HEAD_CASES = [(2, 1024, 8, 15, 0, True, True), (1, 1026, 5, 7, 32, True, False), (1, 194, 33, 40, 32, False, False), (1, 33, 21, 50, 0, True, True),
+                   (3, 16, 9, 7, 16, False, False), (1, 512, 1, 3, 0, True, False), (1, 31, 6, 1, 0, True, True),
+                   (1, 33, 97, 170, 32, False, False), (1, 40, 129, 128, 0, True, True)]   # from 16,384 pixels: the 8 x 8 tiles, ragged in both directions
+HG_FRONT_SHAPES = [(2, 9, 11, 48), (1, 16, 32, 8), (1, 5, 64, 208)]
+_self_named_seen = []   # the route of every flow-head / hourglass-front case that ran
+
+
+@pytest.mark.parametrize("case", FLOW_HEAD_CASES)
 def test_flow_head_equals_float64(case):
     """HFlowHead: predict_flow (3x3, 2 outputs) and the fused ConvTranspose2d(2, 2, 4, 2, 1) of the kernel's fp16 flow into a slice."""
     N, cin, H, W, extra, with_up, up_bias = case
@@ -340,7 +304,8 @@ def test_flow_head_equals_float64(case):
     up_out = torch.full((N, 2 * H, 2 * W, 32), 3.0, dtype=torch.float16, device="cuda") if with_up else None
     flow = head(xs.cuda(), up_out=up_out, up_coff=6)
     r = _route()
-    assert re.match(r"flow_head<(4,4|8,8),%d>" % (2 if with_up else 1), r), r
+    assert r == "flow_head<%s,%d>" % ("4,4" if N * H * W < 16384 else "8,8", 2 if with_up else 1), r
+    _self_named_seen.append(r)
     check_nhwc(flow, c, f"flow head {case} {r}")
     if with_up:
         up = E.deconv_ref(c["want"], wu, bu, stride=2, padding=1, what="flow upsampling", store=torch.float16)
@@ -348,7 +313,7 @@ def test_flow_head_equals_float64(case):
         assert bool((up_out[..., :6] == 3.0).all()) and bool((up_out[..., 8:] == 3.0).all())
 
 
-@pytest.mark.parametrize("shape", [(2, 9, 11, 48), (1, 16, 32, 8), (1, 5, 64, 208)])
+@pytest.mark.parametrize("shape", HG_FRONT_SHAPES)
 def test_hourglass_front_equals_float64(shape):
     """HHourglassFront: 7x7 stem (3 -> 128) + ReLU, its 2x2 max pool and the 1x1 + ReLU on it, one launch, three outputs."""
     N, H, W, c2 = shape
@@ -365,10 +330,23 @@ def test_hourglass_front_equals_float64(shape):
     stem_out = torch.full((N, H, W, 160), 3.0, dtype=torch.float16, device="cuda")
     front(E.nhwc(s["x"], torch.float16, 4).cuda(), out2, pooled=pooled, stem_out=stem_out)
     assert _route() == "hg_front"
+    _self_named_seen.append(_route())
     E.assert_exact(E.nchw64(stem_out, 128), s["want"], "hourglass stem")
     E.assert_exact(E.nchw64(pooled), pool, "hourglass pooled stem")
     E.assert_exact(E.nchw64(out2, c2), one, "hourglass 1x1")
     assert bool((stem_out[..., 128:] == 3.0).all()) and bool((out2[..., c2:] == 3.0).all())
+
+
+def test_self_named_routes_of_the_trunks_all_ran():
+    """(runs after the cases above) `flow_head<..>` and `hg_front` have no plan function: every such route the trunks launch at the BASELINE
+    sizes (tests/golden/g14_trunk_layers.json, `self_named`) was the route of a case above."""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g14_trunk_layers.json")) as f:
+        want = {r for r in json.load(f)["self_named"] if r.startswith(("flow_head<", "hg_front"))}
+    assert len(want) >= 4
+    if len(_self_named_seen) >= len(FLOW_HEAD_CASES) + len(HG_FRONT_SHAPES):   # (the whole file ran, not a selection of its cases)
+        assert want <= set(_self_named_seen), sorted(want - set(_self_named_seen))
 
 
 @pytest.mark.parametrize("shape", [(2, 9, 7, 16), (1, 2, 2, 8), (3, 5, 33, 40), (1, 34, 3, 128)])
@@ -405,14 +383,6 @@ def _plan(kind, conv, N, H, W, in_ld, out_ld, out_coff=0, out_hw=None, stride_x=
     return plan_route(L.load(), kind, args, 1, igemm._WS_BYTES)
 
 
-PLAN_CONV = ([(SHAPES[i], m) for i, m in ((3, ()), (4, ()), (7, ()), (12, ()), (13, ()), (14, ()), (12, (2000, 11)), (13, (2000, 10)), (9, (8,)), (12, (2000, 11, 1300)))]
-             + [(TILE_SHAPES[i], m) for i, m in ((0, (2003,)), (4, (2003, 4128, 5003)), (9, (2003, 4064, 5001)))]
-             + [(PATCH_SHAPES[i] + (1, PATCH_SHAPES[i][5] // 2), PATCH_ROUTES[r][0]) for i, r in ((0, "patch_r8"), (6, "patch_lw"), (8, "patch_lw"), (7, "patch_pf64"),
-                                                                                                (3, "patch_pf32"), (4, "patch_rows"), (1, "patch_rows"), (5, "patch"), (10, "patch_r8"))]
-             + [((2, 64, 128, 240, 16, 3, 1, 1), ()), ((2, 32, 128, 240, 64, 3, 1, 1), ()),      # the smallest map with the patch family by heuristic: H * W >= 8192
-                ((1, 128, 259, 271, 208, 1, 1, 0), ()), ((1, 128, 259, 271, 208, 1, 1, 0), (7001,))])
-
-
 @pytest.mark.xcheck
 @pytest.mark.parametrize("i", range(len(PLAN_CONV)))
 def test_plan_names_the_route_the_convolution_takes(i):
@@ -443,7 +413,7 @@ def test_plan_routes_cover_split_k_and_every_family():
 
 
 @pytest.mark.xcheck
-@pytest.mark.parametrize("case", [(2, 3, 13, 17, 128, 7, 1, 3), (2, 3, 20, 30, 64, 7, 2, 3), (1, 3, 270, 250, 128, 7, 1, 3)])
+@pytest.mark.parametrize("case", PLAN_STEM)
 def test_plan_names_the_route_the_stem_takes(case):
     N, cin, H, W, cout, k, s, p = case
     c = make_conv(cout + k, N, cin, H, W, cout, k, s, p, act=RELU, mag_x=8)
@@ -455,7 +425,7 @@ def test_plan_names_the_route_the_stem_takes(case):
 
 
 @pytest.mark.xcheck
-@pytest.mark.parametrize("shape,modes", [((1, 64, 7, 9, 32), ()), ((2, 1026, 4, 5, 129), ()), ((2, 1026, 4, 5, 129), (1,)), ((2, 96, 11, 13, 192), (2003,)), ((1, 32, 97, 130, 2), ())])
+@pytest.mark.parametrize("shape,modes", PLAN_DECONV)
 def test_plan_names_the_route_the_transposed_convolution_takes(shape, modes):
     N, cin, H, W, cout = shape
     c = make_conv(cin + cout, N, cin, H, W, cout, 4, 2, 1, act=LEAKY, slope=0.1, transposed=True)
@@ -472,7 +442,7 @@ def test_plan_names_the_route_the_transposed_convolution_takes(shape, modes):
 
 @pytest.mark.xcheck
 def test_plan_names_the_route_the_pair_convolution_takes():
-    N, cin, H, W, cout, k, pad = 2, 12, 16, 24, 64, 7, 3
+    N, cin, H, W, cout, k, pad = PAIR_CASES[0]
     c = make_conv(cin + k + W, N, cin, H, W, cout, k, 2, pad, act=LEAKY, slope=0.1)
     conv = igemm.HConvPairS2(c["w"].float().cuda(), c["b"].float().cuda(), pad=pad, act=LEAKY, slope=0.1)
     planned = _plan(0, conv.inner, N, H, W // 2, 32, igemm.pad32(cout), out_hw=((H + 2 * pad - k) // 2 + 1, (W + 2 * pad - k) // 2 + 1), stride_x=1)
@@ -480,6 +450,101 @@ def test_plan_names_the_route_the_pair_convolution_takes():
     r = _route()
     assert planned == r, (planned, r)
     check_nhwc(got, c, f"pair {r}")
+
+
+# ---------------------------------------------------------------------------------------------------------------- one case per production build
+@functools.lru_cache(maxsize=None)
+def _build_case(i):
+    """Operands and float64 reference of BUILD_CASES[i]: computed once, shared by the tests below, never modified."""
+    kind, shape, _, (act, slope) = CC.BUILD_CASES[i]
+    if kind == CC.DECONV:
+        N, cin, H, W, cout = shape
+        return make_conv(700 + i, N, cin, H, W, cout, 4, 2, 1, act=act, slope=slope, transposed=True)
+    return make_conv(700 + i, *shape, act=act, slope=slope, mag_x=8 if kind == CC.STEM else 3)
+
+
+def _run_build_case(i, w=None):
+    """BUILD_CASES[i] through the igemm class of its kind, under its switches, with the weights `w` (default: the reference's) ->
+    (planned route, NHWC output, route of the launch)."""
+    kind, shape, modes, (act, slope) = CC.BUILD_CASES[i]
+    c = _build_case(i)
+    w = (c["w"] if w is None else w).float().cuda()
+    b = c["b"].float().cuda()
+    N, cin, H, W = c["x"].shape
+    cout = c["cout"]
+    with _switches(*modes):
+        if kind == CC.CONV:
+            conv = igemm.HConv(w, b, stride=c["stride"], pad=c["pad"], act=act, slope=slope)
+            planned = _plan(0, conv, N, H, W, igemm.pad32(cin), igemm.pad32(cout))
+            got, r = run_hconv(c, conv=conv)
+            return planned, got, r
+        if kind == CC.STEM:
+            stem = igemm.HConvStem(w, b, stride=c["stride"], pad=c["pad"], act=act, slope=slope)
+            planned = _plan(1, stem, N, H, W, 4, igemm.pad32(cout))
+            got = stem(E.nhwc(c["x"], torch.float16, 4).cuda())
+        elif kind == CC.PAIR:
+            k, pad = shape[5], shape[7]
+            conv = igemm.HConvPairS2(w, b, pad=pad, act=act, slope=slope)
+            planned = _plan(0, conv.inner, N, H, W // 2, 32, igemm.pad32(cout), out_hw=((H + 2 * pad - k) // 2 + 1, (W + 2 * pad - k) // 2 + 1), stride_x=1)
+            got = conv(E.nhwc(c["x"], torch.float16, 16).cuda())
+        else:
+            dc = igemm.HDeconv4s2(w, b, act=act, slope=slope)
+            planned = _plan(2, dc.phases[0], N, H, W, igemm.pad32(cin), igemm.pad32(cout))
+            got = dc(E.nhwc(c["x"], torch.float16, igemm.pad32(cin)).cuda())
+        torch.cuda.synchronize()
+        return planned, got, _route()
+
+
+@pytest.mark.xcheck
+@pytest.mark.parametrize("i", range(len(CC.BUILD_CASES)))
+def test_every_production_build_equals_float64(i):
+    """One case per kernel build that the trunks launch at the BASELINE sizes and no other table of tests/_conv_cases.py plans to
+    (tests/test_conv_build_census.py keeps that list complete): the launch takes the planned route -- the whole string, template
+    arguments included -- and equals float64 bit for bit."""
+    planned, got, r = _run_build_case(i)
+    assert planned == r, (planned, r)
+    import test_conv_build_census as census
+    assert census.build_key(r, *_kh_stride(i)) == census.case_keys([CC.BUILD_CASES[i]])[0]   # (the census planned the launch that ran)
+    check_nhwc(got, _build_case(i), f"{CC.BUILD_CASES[i][:3]} {r}")
+
+
+def _kh_stride(i):
+    kind, shape = CC.BUILD_CASES[i][:2]
+    return (2, 1) if kind == CC.DECONV else (shape[5], shape[6])
+
+
+# one case per template family that gained a build above: (row of BUILD_CASES, the family)
+SENSITIVITY = [(3, "patch_r8<11,2>"), (4, "patch_lw<3,4>"), (8, "gather<128>"), (12, "tile<64>"), (16, "conv1x1_stream<8>")]
+
+
+@pytest.mark.xcheck
+@pytest.mark.parametrize("i,route", SENSITIVITY)
+def test_one_unit_in_one_weight_of_a_production_build_is_seen_with_its_footprint(i, route):
+    """The kernel gets weights in which ONE element differs by one unit from what the reference gets: the last out-channel, the last
+    input channel (the ragged 32-chunk), the bottom-left tap.  The comparison with the reference must fail, the outputs that differ
+    must be exactly those the changed product reaches THROUGH the activation, and the whole result must equal the float64 evaluation
+    with that weight."""
+    kind, shape, _, (act, slope) = CC.BUILD_CASES[i]
+    assert kind == CC.CONV
+    N, cin, H, W, cout, k, s, p = shape
+    c = _build_case(i)
+    co, ci, ky, kx = cout - 1, cin - 1, k - 1, 0
+    w2 = c["w"].clone()
+    w2[co, ci, ky, kx] += 1.0
+    _, got, r = _run_build_case(i, w=w2)
+    assert r.startswith(route), r
+    Ho, Wo = c["want"].shape[2:]
+    xp = torch.nn.functional.pad(c["x"][:, ci], (p, p, p, p))
+    pre2 = c["pre"].clone()
+    pre2[:, co] += xp[:, ky:ky + (Ho - 1) * s + 1:s, kx:kx + (Wo - 1) * s + 1:s]
+    want2 = E.act_ref(pre2, act, slope)
+    pred = want2 != c["want"]
+    assert 50 < int(pred.sum()) and not bool(pred[:, :co].any())
+    got = E.nchw64(got, cout)
+    with pytest.raises(AssertionError, match="differ from the float64 evaluation"):
+        E.assert_exact(got, c["want"], r)
+    assert torch.equal(E.diff_mask(got, c["want"]), pred), (r, E.bbox(E.diff_mask(got, c["want"])), E.bbox(pred))
+    E.assert_exact(got, want2, f"{shape} {r} with the changed weight")
 
 
 # ---------------------------------------------------------------------------------------------------------------- the FlowNetC cost volume

@@ -58,6 +58,9 @@ def _run(inc, x, in_coff, fused):
     return buf[..., coff:coff + c].permute(0, 3, 1, 2).contiguous().cpu(), hist
 
 
+_exact_routes_seen = []   # the route of every fused launch of test_fused_block_is_exact
+
+
 def _wide(x64, in_coff, fill):
     """[N,cin,H,W] float64 -> device [N,H,W,in_coff + cin + 32] fp16 with the live slice at in_coff and `fill` in every other channel."""
     N, C, H, W = x64.shape
@@ -76,10 +79,23 @@ def test_fused_block_is_exact(name, hw):
     ref = C.exact_ref(wts, x)
     for n in (1, NREF):
         for in_coff in (0, 32):
-            got, _ = _run(inc, _wide(x[:n], in_coff, 1000.0), in_coff, fused=True)
+            got, hist = _run(inc, _wide(x[:n], in_coff, 1000.0), in_coff, fused=True)
+            _exact_routes_seen.extend(hist)
             X.assert_exact(got, ref[:n], f"block {name} {hw[0]}x{hw[1]} N={n} in_coff={in_coff} (fused)")
     four, _ = _run(inc, _wide(x, 32, 1000.0), 32, fused=False)
     X.assert_exact(four, ref, f"block {name} {hw[0]}x{hw[1]} (four launches)")
+
+
+def test_exact_cases_ran_every_inception_route_the_trunks_launch():
+    """(runs after the cases above) `hg_inception<..>` has no plan function: every such route the trunks launch at the BASELINE sizes
+    (tests/golden/g14_trunk_layers.json, `self_named`) was the route of an exact case."""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g14_trunk_layers.json")) as f:
+        want = {r for r in json.load(f)["self_named"] if r.startswith("hg_inception<")}
+    assert len(want) >= 2
+    if len(_exact_routes_seen) >= 4 * len(SIZES) * len(SIGS):   # (the whole list ran, not a selection of its cases)
+        assert want <= set(_exact_routes_seen), sorted(want - set(_exact_routes_seen))
 
 
 # ---------------------------------------------------------------------------------------------------------------- 2. Gaussian

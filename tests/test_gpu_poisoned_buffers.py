@@ -22,6 +22,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import _conv_cases as CC  # noqa: E402
 import test_gpu_conv as TC  # noqa: E402
 import test_gpu_conv_f32 as TC32  # noqa: E402
 import test_gpu_flow_ops as TF  # noqa: E402
@@ -328,20 +329,28 @@ def test_conv_forced_patch_route(route, case):
         _hconv_case((N, cin, H, W, cout, k, 1, k // 2, act), route)
 
 
-@pytest.mark.parametrize("case", _params(TC.test_stem_conv_matches_torch, "case"))
-def test_stem_conv(case):
+def _stem_case(case):
     N, cin, H, W, cout, k, s, p, act = case
     w, b, xa, xb = _conv_operands(case, cout + k)
     run_poisoned(lambda: igemm.HConvStem(w, b, stride=s, pad=p, act=act), lambda conv, x: conv(igemm.to_nhwc_half(x, 4)), xa, xb,
                  check=_pad_is_zero(cout), what=f"HConvStem {case}")
 
 
-@pytest.mark.parametrize("case", _params(TC.test_pair_conv_stride2, "case"))
-def test_pair_conv_stride2(case):
+@pytest.mark.parametrize("case", _params(TC.test_stem_conv_matches_torch, "case"))
+def test_stem_conv(case):
+    _stem_case(case)
+
+
+def _pair_case(case):
     N, cin, H, W, cout, k, pad = case
     w, b, xa, xb = _conv_operands(case, cin + k + W)
     run_poisoned(lambda: igemm.HConvPairS2(w, b, pad=pad, act=igemm.ACT_LEAKY, slope=0.1), lambda conv, x: conv(igemm.to_nhwc_half(x, 16)),
                  xa, xb, check=_pad_is_zero(cout), what=f"HConvPairS2 {case}")
+
+
+@pytest.mark.parametrize("case", _params(TC.test_pair_conv_stride2, "case"))
+def test_pair_conv_stride2(case):
+    _pair_case(case)
 
 
 def _deconv_case(shape, what):
@@ -366,6 +375,27 @@ def test_transposed_conv_k4s2_forced_route(shape, route):
         return   # (no tile build below 64 out-channels: the value test forces it from there too)
     with _tuned((2003,) if route == "tile" else (1,)):
         _deconv_case(shape, f"HDeconv4s2 {route}")
+
+
+@pytest.mark.xcheck
+@pytest.mark.parametrize("i", range(len(CC.BUILD_CASES)))
+def test_conv_production_builds(i):
+    """tests/_conv_cases.py BUILD_CASES: one case per kernel build that the trunks launch and no list above reaches (kept complete by
+    tests/test_conv_build_census.py), through the runner of its entry; the launch takes the route the census planned for the row."""
+    import test_conv_build_census as census
+    kind, shape, modes, (act, _) = CC.BUILD_CASES[i]
+    with _tuned(modes):
+        if kind == CC.CONV:
+            _hconv_case(shape + (act,), "production build")
+        elif kind == CC.STEM:
+            _stem_case(shape + (act,))
+        elif kind == CC.PAIR:
+            _pair_case(shape[:6] + (shape[7],))
+        else:
+            _deconv_case(shape, "production build")
+        route = L.load().vsr_last_route().decode()
+    kh, stride = (2, 1) if kind == CC.DECONV else shape[5:7]
+    assert census.build_key(route, kh, stride) == census.case_keys([CC.BUILD_CASES[i]])[0], route
 
 
 @pytest.mark.xcheck
