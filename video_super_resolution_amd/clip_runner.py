@@ -1,6 +1,7 @@
-"""`ClipRunner`: a 4:2:0 clip streamed through the model on top of `frames`: every source frame uploaded once from pinned memory on a
-copy stream, converted once into a three-slot LR ring, the window formed on the device, the HR frame written out as 4:2:0 and copied
-back on a second copy stream.  What a run scores (`score=`, `baseline=`, `temporal=`) is a list of series, each a range of rows of one
+"""`ClipRunner`: a clip of planar Y'CbCr frames (any name of `frames.PIX_FORMATS`: 4:2:0, 4:2:2, 4:4:4) streamed through the model on top of
+`frames`: every source frame read straight into pinned memory and uploaded once on a copy stream, converted once into a three-slot LR
+ring, the window formed on the device, the HR frame written out in the output format, copied back on a second copy stream and handed
+to a sink from its pinned slot: no host array of the clip's length exists on either side (`run_stream`; `run` is the array form).  What a run scores (`score=`, `baseline=`, `temporal=`) is a list of series, each a range of rows of one
 float64 tensor of sums (`sums_layout`); with `multiscale=True` the frames' multi-scale SSIM sums go into a tensor of their own; with
 `scene="sad"` scene cuts are found and the window composed under them on the device, in
 tensors of their own; `driver` imports `ClipRunner`, so `driver.ClipRunner` resolves as before.
@@ -14,8 +15,8 @@ import numpy as np
 import torch
 
 from .frames import (METRIC_CHANNELS, MSSSIM_BETA, MSSSIM_MIN_SIZE, FrameResizer, _scene_thresholds, ewarp, frame_metrics, frame_msssim,
-                     msssim, psnr_ssim, scene_flags, scene_sums, scene_window, truth_flows, warp_error, yuv_coefficients, yuv_frame_bytes,
-                     yuv_ingest, yuv_write)
+                     msssim, pix_coefficients, pix_frame_bytes, pix_ingest, pix_write, psnr_ssim, scene_flags, scene_sums, scene_window,
+                     truth_flows, warp_error)
 
 # series of `sums_layout` -> the keys of `ClipRunner.metrics` its host step (`psnr_ssim` for a frame series, `ewarp` for a pair series)
 # fills; the occlusion mask depends on the flows alone, so the estimate's pairs give the one `valid_share`
@@ -46,10 +47,34 @@ def sums_layout(T: int, score: Optional[str], baseline: Optional[str] = None,
     return layout
 
 
+class ArraySource:
+    """A host array [T, frame_bytes] as a frame source: `read_into(buf)` copies the next row, False after the last (`len`: the rows)."""
+
+    def __init__(self, frames: np.ndarray):
+        self.frames, self._i = frames, 0
+
+    def __len__(self) -> int:
+        return self.frames.shape[0]
+
+    def read_into(self, buf: np.ndarray) -> bool:
+        if self._i >= self.frames.shape[0]:
+            return False
+        buf[:] = self.frames[self._i]
+        self._i += 1
+        return True
+
+
 class ClipRunner:
-    """A 4:2:0 clip streamed through `model` frame by frame.  `shape` = (H, W) of the source frames in `fmt_in`; the model sees them
+    """A clip streamed through `model` frame by frame.  `shape` = (H, W) of the source frames in `fmt_in`; the model sees them
     decimated by `scale_down` (1: as they are) and returns frames of (S * (H // scale_down), S * (W // scale_down)), written out as
-    `fmt_out`.  `run(frames)`: host array [T, frame_bytes] -> host array [T-2, out_frame_bytes] (one frame per 3-frame window).
+    `fmt_out`; both formats are names of `frames.PIX_FORMATS`, and an output shape `fmt_out` cannot hold (an odd width for 4:2:2, an odd
+    size for 4:2:0) is refused here.  `run_stream(source, sink, frames=T)`: `source.read_into(buf) -> bool` fills a uint8 array of
+    `in_bytes` elements with the next frame (a `y4m.Y4MReader`, an `ArraySource`); the runner hands it the pinned upload slot itself, so
+    a frame goes from the file to pinned memory in one read.  `sink(j, frame)` is called once per output frame j = 0 .. T-3, in order,
+    with a uint8 view of the pinned output slot that is valid during the call only (a `y4m.Y4MWriter`).  `frames`: how many source frames
+    to take, default `len(source)`; the sums of a scored run are sized by it, nothing else is.  `run(frames)`: host array
+    [T, frame_bytes] -> host array [T-2, out_frame_bytes] (one frame per 3-frame window): `run_stream` over an `ArraySource` with a
+    collecting sink.
 
     Per source frame: one upload from one of two pinned slots on the copy-in stream, one conversion into a slot of a three-slot LR
     ring; per window: the ring's slots stacked on the device, `model(x, None, None, est, train=False)` on the current stream with the
@@ -155,10 +180,13 @@ class ClipRunner:
             raise ValueError(f"multiscale=True needs {MSSSIM_MIN_SIZE} pixels each way after the shave: shave {self.shave} leaves "
                              f"{min(self.shape) - 2 * self.shave} of {self.shape}")
         self.metrics = None   # of the last run(): {"psnr": [T-2], "ssim": [T-2]} when scoring
-        self.in_bytes = yuv_frame_bytes(fmt_in, H, W)
-        self.out_bytes = yuv_frame_bytes(fmt_out, *self.out_shape)
-        self.coef_in = yuv_coefficients(fmt_in, matrix, full_range, inverse=True)
-        self.coef_out = yuv_coefficients(fmt_out, matrix, full_range)
+        self.in_bytes = pix_frame_bytes(fmt_in, H, W)
+        try:
+            self.out_bytes = pix_frame_bytes(fmt_out, *self.out_shape)
+        except ValueError as e:
+            raise ValueError(f"the output frames of {self.out_shape[0]} x {self.out_shape[1]} do not fit {fmt_out}: {e}") from None
+        self.coef_in = pix_coefficients(fmt_in, matrix, full_range, inverse=True)
+        self.coef_out = pix_coefficients(fmt_out, matrix, full_range)
         self.device = next(model.parameters()).device
         dev = self.device
         self._pin_in = [torch.empty(self.in_bytes, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
@@ -195,13 +223,26 @@ class ClipRunner:
         frames = np.asarray(frames)
         if frames.dtype != np.uint8 or frames.ndim != 2 or frames.shape[1] != self.in_bytes or frames.shape[0] < 3:
             raise ValueError(f"expected uint8 [T >= 3, {self.in_bytes}], got {frames.dtype} {frames.shape}")
-        T = frames.shape[0]
+        out = np.empty((frames.shape[0] - 2, self.out_bytes), dtype=np.uint8)
+
+        def collect(j, frame):
+            out[j] = frame
+
+        self.run_stream(ArraySource(frames), collect)
+        return out
+
+    def run_stream(self, source, sink, frames: Optional[int] = None) -> int:
+        """`source` -> `sink`, frame by frame (the class docstring); returns the number of output frames, T - 2."""
+        T = len(source) if frames is None else int(frames)
+        if T < 3:
+            raise ValueError(f"a run needs at least 3 source frames (one window), got {T}")
         self.h2d_bytes = self.d2h_bytes = self.frames_in = self.frames_out = 0
         self.metrics = self.cuts = self.scene_m = None
         with torch.cuda.device(self.device), torch.no_grad():
             st = self._begin(T)
+            st.sink, st.T = sink, T
             for i in range(T):
-                self._upload(st, i, frames[i])
+                self._upload(st, i, source)
                 if i < 2:
                     continue
                 self._forward(st, i)
@@ -213,10 +254,10 @@ class ClipRunner:
                 self._collect_scene(st, T)
             if st.layout is not None:
                 self.metrics = self._collect(st)
-        return st.out
+        return T - 2
 
     def _begin(self, T: int):
-        """The state of one run: the output array, the one tensor of sums, the streams and the events that order every reuse of a slot."""
+        """The state of one run: the sink, the one tensor of sums, the streams and the events that order every reuse of a slot."""
         layout = sums_layout(T, self.score, self.baseline, self.temporal)
         rows = sum(n for _, n, _ in layout.values()) if layout is not None else 0
         main = torch.cuda.current_stream(self.device)
@@ -234,19 +275,21 @@ class ClipRunner:
                              dtype=torch.float64, device=self.device)
         return SimpleNamespace(
             ms=ms, scene_buf=scene_buf, scene_sums=scene_rows, scene_flags=scene_flag,
-            out=np.empty((T - 2, self.out_bytes), dtype=np.uint8), layout=layout,
+            sink=None, layout=layout,
             sums=None if layout is None else torch.empty((rows, 4), dtype=torch.float64, device=self.device),
             main=main, s_in=s_in, s_out=s_out, est=None, prev_est=None,
             uploaded=[None, None],    # per input slot: the upload from its pinned buffer has finished (event on s_in)
             converted=[None, None],   # per input slot: the conversion has read its device buffer (event on main)
             copied=[None, None])      # per output slot: (frame index, event on s_out: the copy into its pinned buffer has finished)
 
-    def _upload(self, st, i: int, frame: np.ndarray) -> None:
-        """Source frame `i`: from its pinned slot to the device on the copy-in stream, converted into ring slot i % 3 on the current one."""
+    def _upload(self, st, i: int, source) -> None:
+        """Source frame `i`: read into its pinned slot, from there to the device on the copy-in stream, converted into ring slot i % 3 on
+        the current one."""
         a = i % 2
         if st.uploaded[a] is not None:
             st.uploaded[a].synchronize()   # the pinned slot is free again (host wait on one event)
-        self._pin_in[a].numpy()[:] = frame
+        if not source.read_into(self._pin_in[a].numpy()):   # (straight into the pinned slot: no temporary in between)
+            raise ValueError(f"the source ended before frame {i} of the {st.T} asked for")
         if st.converted[a] is not None:
             st.s_in.wait_event(st.converted[a])
         with torch.cuda.stream(st.s_in):
@@ -258,9 +301,9 @@ class ClipRunner:
         st.main.wait_event(st.uploaded[a])
         # (ring slot i % 3 was last read by the window of frames i-3 .. i-1, stacked on this stream)
         if self._down is None:
-            yuv_ingest(self._dev_in[a], self.shape, self.fmt_in, self.coef_in, self.siting, self.lr_shape, lr_out=self._ring[i % 3])
+            pix_ingest(self._dev_in[a], self.shape, self.fmt_in, self.coef_in, self.siting, self.lr_shape, lr_out=self._ring[i % 3])
         else:   # (the HR buffer was last read by the previous frame's reduction, on this stream)
-            yuv_ingest(self._dev_in[a], self.shape, self.fmt_in, self.coef_in, self.siting, lr_out=self._full)
+            pix_ingest(self._dev_in[a], self.shape, self.fmt_in, self.coef_in, self.siting, lr_out=self._full)
             self._down(self._full, quantise=True, out=self._ring[i % 3])
         st.converted[a] = torch.cuda.Event()
         st.converted[a].record(st.main)
@@ -290,7 +333,7 @@ class ClipRunner:
         # then scored; the slot's next upload waits for this read as it does for the LR conversion
         c = (j + 1) % 2
         est, truth, base = st.est[0], self._slot(self._truth, j), self._slot(self._base, j)
-        yuv_ingest(self._dev_in[c], self.shape, self.fmt_in, self.coef_in, self.siting, lr_out=truth)
+        pix_ingest(self._dev_in[c], self.shape, self.fmt_in, self.coef_in, self.siting, lr_out=truth)
         frame_metrics(est, truth, self.score, True, self.shave, out=row("estimate", j))
         if st.ms is not None:
             frame_msssim(est, truth, self.score, True, self.shave, out=st.ms[0, j:j + 1])
@@ -314,12 +357,12 @@ class ClipRunner:
         st.converted[c].record(st.main)
 
     def _write_out(self, st, j: int) -> None:
-        """Output frame `j`: written as 4:2:0 into device slot j % 2 on the current stream, copied back on the copy-out stream."""
+        """Output frame `j`: written as `fmt_out` into device slot j % 2 on the current stream, copied back on the copy-out stream."""
         b = j % 2
         if st.copied[b] is not None:   # frame j-2 leaves the slot pair: wait for its copy, take it from the pinned buffer
             self._take(st, b)
             st.main.wait_event(st.copied[b][1])
-        yuv_write(st.est[0], self.fmt_out, self.coef_out, self.siting, out=self._dev_out[b])
+        pix_write(st.est[0], self.fmt_out, self.coef_out, self.siting, out=self._dev_out[b])
         ready = torch.cuda.Event()
         ready.record(st.main)
         st.s_out.wait_event(ready)
@@ -332,16 +375,16 @@ class ClipRunner:
         self.frames_out += 1
 
     def _take(self, st, b: int) -> None:
-        """The frame in pinned output slot `b` into the output array, once its copy has finished (host wait on one event)."""
+        """The frame in pinned output slot `b` to the sink, once its copy has finished (host wait on one event); the view is valid during
+        the call: the slot's next copy is enqueued after it returns."""
         jj, ev = st.copied[b]
         ev.synchronize()
-        st.out[jj] = self._pin_out[b].numpy()
+        st.sink(jj, self._pin_out[b].numpy())
 
     def _drain(self, st) -> None:
         """The last two output frames, and every slot idle when run() returns."""
-        for b in range(2):
-            if st.copied[b] is not None:
-                self._take(st, b)
+        for b in sorted((b for b in range(2) if st.copied[b] is not None), key=lambda b: st.copied[b][0]):   # (the sink sees them in order)
+            self._take(st, b)
         for ev in st.uploaded + st.converted:
             if ev is not None:
                 ev.synchronize()

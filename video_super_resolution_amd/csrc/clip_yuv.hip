@@ -13,18 +13,13 @@
 //                 exactly one thread, so every byte is written once and nothing else is.
 // All three are HBM-bound byte passes.  The up-sampling weights are dyadic (1, 1/2, 1/4, 3/4) and the code values below 2^10, so the
 // up-sampled chroma is exact in float32 in any order; the matrix is three nested fmas spelled out (a restatement can follow them).
-#include "vsr_common.h"
+#include "clip_yuv.h"   // Coef, midway, cosited, to_rgb, clamp255, dot_row, store_run, read_coef: shared with clip_pix.hip
 
 #include <type_traits>
 
 #include "../../include/vsr_hip_yuv.h"
 
 namespace {
-
-struct Coef {
-    float a[9];
-    float o[3];
-};
 
 template <int FMT>
 struct Fmt {
@@ -51,27 +46,6 @@ struct Fmt {
     __device__ static inline size_t cr_step(int H, int W) { return kSemi ? 1 : (size_t)(H >> 1) * (W >> 1); }
 };
 
-// midway siting along one axis: luma index i between chroma samples i0 (weight w0) and i1 (weight 1 - w0), clamped to 0..n-1
-__device__ inline void midway(int i, int n, int& i0, int& i1, float& w0) {
-    const int k = i >> 1;
-    if (i & 1) {
-        i0 = k, i1 = k + 1 < n ? k + 1 : n - 1, w0 = 0.75f;
-    } else {
-        i0 = k > 0 ? k - 1 : 0, i1 = k, w0 = 0.25f;
-    }
-}
-
-// co-sited along one axis: even luma index = the sample, odd = the mean of its neighbours
-__device__ inline void cosited(int i, int n, int& i0, int& i1, float& w0) {
-    const int k = i >> 1;
-    i0 = k;
-    if (i & 1) {
-        i1 = k + 1 < n ? k + 1 : n - 1, w0 = 0.5f;
-    } else {
-        i1 = k, w0 = 1.0f;
-    }
-}
-
 // the up-sampled (Cb', Cr') at luma position (y, x) of the frame at `fr`: 4 samples per component
 template <int FMT, int SIT>
 __device__ inline void chroma_up(const typename Fmt<FMT>::T* __restrict__ fr, int H, int W, int y, int x, float& cb, float& cr) {
@@ -86,14 +60,6 @@ __device__ inline void chroma_up(const typename Fmt<FMT>::T* __restrict__ fr, in
     const float vy = 1.0f - wy, vx = 1.0f - wx;
     cb = wy * (wx * P::dec(fr[i00]) + vx * P::dec(fr[i01])) + vy * (wx * P::dec(fr[i10]) + vx * P::dec(fr[i11]));
     cr = wy * (wx * P::dec(fr[i00 + d]) + vx * P::dec(fr[i01 + d])) + vy * (wx * P::dec(fr[i10 + d]) + vx * P::dec(fr[i11 + d]));
-}
-
-__device__ inline void to_rgb(const Coef& k, float yc, float cb, float cr, float* out) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float v = __builtin_fmaf(k.a[3 * c + 2], cr, __builtin_fmaf(k.a[3 * c + 1], cb, __builtin_fmaf(k.a[3 * c], yc, k.o[c])));
-        out[c] = fminf(fmaxf(v, 0.0f), 255.0f);
-    }
 }
 
 template <int FMT, int SIT>
@@ -192,37 +158,6 @@ k_yuv_full(const typename Fmt<FMT>::T* __restrict__ in, float* __restrict__ out1
     }
 }
 
-__device__ inline float clamp255(float v) {
-    v = v >= 0.0f ? v : 0.0f;   // negatives and NaN
-    return v > 255.0f ? 255.0f : v;
-}
-
-__device__ inline float dot_row(const Coef& k, int c, float r, float g, float b) {
-    return __builtin_fmaf(k.a[3 * c + 2], b, __builtin_fmaf(k.a[3 * c + 1], g, __builtin_fmaf(k.a[3 * c], r, k.o[c])));
-}
-
-// N samples (codes already positioned in their words) to consecutive addresses: one store when WIDE, element stores otherwise
-template <typename T, int N, bool WIDE>
-__device__ inline void store_run(T* q, const unsigned* c) {
-    if constexpr (WIDE) {
-        constexpr int per = 4 / (int)sizeof(T);   // samples per 32-bit word
-        constexpr int NW = N / per;
-        static_assert(NW == 1 || NW == 2 || NW == 4, "a run is one 4-, 8- or 16-byte store");
-        unsigned w[NW];
-#pragma unroll
-        for (int i = 0; i < NW; ++i) {
-            if constexpr (sizeof(T) == 1) w[i] = c[4 * i] | (c[4 * i + 1] << 8) | (c[4 * i + 2] << 16) | (c[4 * i + 3] << 24);
-            else w[i] = c[2 * i] | (c[2 * i + 1] << 16);
-        }
-        if constexpr (NW == 1) *reinterpret_cast<unsigned*>(q) = w[0];
-        else if constexpr (NW == 2) *reinterpret_cast<uint2*>(q) = make_uint2(w[0], w[1]);
-        else *reinterpret_cast<uint4*>(q) = make_uint4(w[0], w[1], w[2], w[3]);
-    } else {
-#pragma unroll
-        for (int i = 0; i < N; ++i) q[i] = (T)c[i];
-    }
-}
-
 template <int FMT, int SIT, int NC>
 __global__ void __launch_bounds__(256)
 k_yuv_write(const float* __restrict__ rgb, typename Fmt<FMT>::T* __restrict__ out, int H, int W, Coef k) {
@@ -307,13 +242,6 @@ k_yuv_write(const float* __restrict__ rgb, typename Fmt<FMT>::T* __restrict__ ou
 }
 
 inline bool is16(int fmt) { return fmt == VSR_YUV_420P10LE || fmt == VSR_YUV_P010LE; }
-
-inline Coef read_coef(const float* coef12) {
-    Coef k;
-    for (int i = 0; i < 9; ++i) k.a[i] = coef12[i];
-    for (int i = 0; i < 3; ++i) k.o[i] = coef12[9 + i];
-    return k;
-}
 
 // the checks the two entries share; `what` names the entry in the message
 int check_frames(const char* what, const void* frames, int fmt, const float* coef12, int siting, int F, int H, int W) {

@@ -22,7 +22,8 @@ The device bindings for frames in, out, resampled and scored (4:2:0 I/O, the res
 main-like plumbing) on the GPU path (`tools/c1_check.py` runs the CPU checker beside it and reports the PSNR between the two:
 the package itself never touches the checker).
 Decoding compressed video (cv2.VideoCapture, video_utils.py:17-23) is out of scope: a clip enters as a uint8 RGB array
-(`.npy`, raw rgb24, or synthetic) or as raw 4:2:0 frames (`ffmpeg -f rawvideo`; transfer functions, 4:2:2 / 4:4:4 stay out too).
+(`.npy`, raw rgb24, or synthetic) or as planar Y'CbCr frames, 4:2:0, 4:2:2 or 4:4:4, in a `.y4m` file or headerless (`ffmpeg -f rawvideo`):
+`--input` streams such a file through `ClipRunner.run_stream` (`run_file`); transfer functions stay out.
 """
 from __future__ import annotations
 
@@ -35,12 +36,13 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .clip_runner import ClipRunner, sums_layout  # noqa: F401
-from .frames import (METRIC_CHANNELS, METRIC_WHAT, MSSSIM_BETA, MSSSIM_MIN_SIZE, RESIZE_KERNELS, RESIZE_MAX_TAPS, SCENE_THRESHOLDS,  # noqa: F401
-                     WARP_OCC, YUV_FORMATS, YUV_SITINGS, FrameResizer, ewarp, frame_metrics, frame_msssim, frames_to_yuv,
-                     ingest_item_yuv, msssim, msssim_levels, psnr_ssim, read_clip_yuv,
-                     resize_frames, resize_tables, scene_cuts, scene_flags, scene_sums, scene_window, ssim_window, truth_flows, warp_error,
+from .clip_runner import ArraySource, ClipRunner, sums_layout  # noqa: F401
+from .frames import (METRIC_CHANNELS, METRIC_WHAT, MSSSIM_BETA, MSSSIM_MIN_SIZE, PIX_FORMATS, RESIZE_KERNELS, RESIZE_MAX_TAPS,  # noqa: F401
+                     SCENE_THRESHOLDS, WARP_OCC, YUV_FORMATS, YUV_SITINGS, FrameResizer, ewarp, frame_metrics, frame_msssim, frames_to_pix,
+                     frames_to_yuv, ingest_item_pix, ingest_item_yuv, msssim, msssim_levels, pix_coefficients, pix_frame_bytes, pix_ingest,
+                     pix_write, psnr_ssim, read_clip_yuv, resize_frames, resize_tables, scene_cuts, scene_flags, scene_sums, scene_window, ssim_window, truth_flows, warp_error,
                      yuv_coefficients, yuv_frame_bytes, yuv_ingest, yuv_write)
+from .y4m import RawReader, RawWriter, Y4MReader, Y4MWriter  # noqa: F401
 
 
 # ------------------------------------------------------------------------------------------------ dataset
@@ -238,7 +240,7 @@ def run_c1(lr: int = 128, frames: int = 3, scale: int = 4, precision: str = "fp3
 def run_c1_yuv(pix_fmt: str, lr: int = 128, frames: int = 3, scale: int = 4, precision: str = "fp32", score: Optional[str] = None,
                decimate: str = "nearest", baseline: Optional[str] = None, temporal: Optional[str] = None, scene: Optional[str] = None,
                scene_thresholds=None, cut_at: Optional[int] = None, multiscale: bool = False):
-    """Config C1 with a 4:2:0 boundary: the synthetic clip as `pix_fmt` frames on the host, streamed through `ClipRunner`
+    """Config C1 with a Y'CbCr boundary (`pix_fmt`: any name of `PIX_FORMATS`): the synthetic clip as `pix_fmt` frames on the host, streamed through `ClipRunner`
     (decimated by `scale`, super-resolved by `scale`).  -> (result line, output frames uint8 [T-2, frame_bytes] on the host).
     `score`: "rgb" | "y": the line also carries the per-frame PSNR / SSIM against the synthetic HR clip.  `decimate` / `baseline`: as
     `ClipRunner`'s; with a baseline the line carries its mean PSNR / SSIM beside the estimate's and `psnr_gain`, their difference in dB; with
@@ -260,7 +262,7 @@ def run_c1_yuv(pix_fmt: str, lr: int = 128, frames: int = 3, scale: int = 4, pre
         if not 0 < cut_at < frames:
             raise ValueError(f"cut_at must lie inside the clip of {frames} frames, got {cut_at}")
         video[cut_at:] = synthetic_video(frames, S * lr, S * lr, seed=4321)[cut_at:]
-    clip = frames_to_yuv(torch.from_numpy(video).to(dev).float(), pix_fmt).cpu().numpy()
+    clip = frames_to_pix(torch.from_numpy(video).to(dev).float(), pix_fmt).cpu().numpy()
     runner = ClipRunner(model, (S * lr, S * lr), pix_fmt, pix_fmt, scale_down=S, score=score, decimate=decimate, baseline=baseline,
                         temporal=temporal, scene=scene, scene_thresholds=scene_thresholds, multiscale=multiscale)
     runner.run(clip)                                                      # warm-up (packing, allocator)
@@ -270,6 +272,17 @@ def run_c1_yuv(pix_fmt: str, lr: int = 128, frames: int = 3, scale: int = 4, pre
     line = dict(config=f"C1: {frames}-frame {lr}x{lr} LR synthetic clip, x{S}, {pix_fmt} in and out, streamed clip runner, GPU path",
                 precision=precision, windows=frames - 2, frames_per_s=round((frames - 2) / dt, 3), out_shape=list(out.shape),
                 h2d_bytes_per_frame=runner.in_bytes, d2h_bytes_per_frame=runner.out_bytes)
+    _score_fields(line, runner, score, baseline, temporal, scene, multiscale, decimate)
+    if cut_at is not None:
+        line.update(cut_at=cut_at)
+    if scene is not None:
+        line.update(scene=scene, scene_thresholds=list(runner.scene_thresholds), cuts=[int(i) for i in np.flatnonzero(runner.cuts)],
+                    scene_m=[round(float(v), 4) for v in runner.scene_m])
+    return line, out
+
+
+def _score_fields(line: dict, runner, score, baseline, temporal, scene, multiscale, decimate) -> None:
+    """The fields a scored / watched `ClipRunner` run adds to a result line (what `run_c1_yuv` and `run_file` report alike)."""
     if score is not None:
         line.update(score=score, shave=runner.shave, psnr_db=[round(float(v), 4) for v in runner.metrics["psnr"]],
                     ssim=[round(float(v), 6) for v in runner.metrics["ssim"]])
@@ -291,12 +304,71 @@ def run_c1_yuv(pix_fmt: str, lr: int = 128, frames: int = 3, scale: int = 4, pre
         line.update(temporal=temporal, ewarp=mean(m["ewarp"]), ewarp_truth=mean(m["ewarp_truth"]), valid_share=mean(m["valid_share"]))
         if baseline is not None:
             line.update(ewarp_baseline=mean(m["ewarp_baseline"]))
-    if cut_at is not None:
-        line.update(cut_at=cut_at)
+
+
+def run_file(path: str, output: Optional[str] = None, size: Optional[Tuple[int, int]] = None, pix_fmt: Optional[str] = None,
+             out_pix_fmt: Optional[str] = None, matrix: str = "bt709", siting: Optional[str] = None, checkpoint: Optional[str] = None,
+             scale_down: Optional[int] = None, frames: Optional[int] = None, scale: int = 4, precision: str = "fp32",
+             score: Optional[str] = None, decimate: str = "nearest", baseline: Optional[str] = None, temporal: Optional[str] = None,
+             scene: Optional[str] = None, scene_thresholds=None, multiscale: bool = False, model=None) -> dict:
+    """A clip file streamed through `ClipRunner.run_stream`: `path` a `.y4m` file (size, rate, format, siting and range from its header)
+    or a headerless one (`size` = (H, W) and `pix_fmt` required); `output`: the output frames as `out_pix_fmt` (default: the input's),
+    with a header when it ends in `.y4m` (S x the LR size, the input's F and A), raw otherwise, or None: the frames are dropped.  The file
+    is decimated by `scale_down` (default 1; with `score`: `scale`, the file is the ground truth) and super-resolved by `scale`.  `siting`
+    overrides the file's; `checkpoint`: `load_checkpoint` into the seeded model (`model`: use this one instead).  Host memory does not
+    depend on the clip's length.  -> the result line."""
+    import time
+    from . import VSR
+    from .weights import fill_module_
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    S = scale
+    if path.endswith(".y4m"):
+        src = Y4MReader(path, siting=siting)
+    else:
+        if size is None or pix_fmt is None:
+            raise ValueError("a headerless clip needs size=(H, W) and pix_fmt")
+        src = RawReader(path, size, pix_fmt, siting or "left")
+    fmt_in, fmt_out = src.fmt, (out_pix_fmt or src.fmt)
+    weights = "seeded"
+    if model is None:
+        model = fill_module_(VSR(upscale_factor=S).eval(), seed=0).to(dev)
+        model.precision = model.model.precision = precision
+    else:
+        weights = "given"
+    if checkpoint is not None:
+        load_checkpoint(model, checkpoint, map_location=dev)
+        weights = checkpoint
+    if scale_down is None:
+        scale_down = S if score is not None else 1
+    runner = ClipRunner(model, src.shape, fmt_in, fmt_out, scale_down=scale_down, matrix=matrix, full_range=src.full_range,
+                        siting=src.siting, score=score, decimate=decimate, baseline=baseline, temporal=temporal, scene=scene,
+                        scene_thresholds=scene_thresholds, multiscale=multiscale)
+    T = len(src) if frames is None else int(frames)
+    if output is None:
+        sink = lambda j, frame: None   # noqa: E731
+    elif output.endswith(".y4m"):
+        sink = Y4MWriter(output, runner.out_shape, fmt_out, src.fps or (25, 1), src.siting, src.full_range, src.aspect)   # (a headerless input has no rate: 25:1, and A0:0 = unknown)
+    else:
+        sink = RawWriter(output, runner.out_bytes)
+    t0 = time.perf_counter()
+    try:
+        n = runner.run_stream(src, sink, frames=T)
+    finally:
+        src.close()
+        if output is not None:
+            sink.close()
+    dt = time.perf_counter() - t0
+    line = dict(config=f"{T}-frame {src.shape[0]}x{src.shape[1]} clip from a file, /{scale_down} x{S}, streamed clip runner, GPU path",
+                input=path, output=output, frames=T, precision=precision, windows=n, frames_per_s=round(n / dt, 3),
+                out_shape=[n, runner.out_bytes], out_size=list(runner.out_shape), pix_fmt_in=fmt_in, pix_fmt_out=fmt_out, matrix=matrix,
+                siting=src.siting, full_range=bool(src.full_range), weights=weights, fps=list(src.fps) if src.fps else None,
+                h2d_bytes_per_frame=runner.in_bytes, d2h_bytes_per_frame=runner.out_bytes)
+    _score_fields(line, runner, score, baseline, temporal, scene, multiscale, decimate)
     if scene is not None:
         line.update(scene=scene, scene_thresholds=list(runner.scene_thresholds), cuts=[int(i) for i in np.flatnonzero(runner.cuts)],
                     scene_m=[round(float(v), 4) for v in runner.scene_m])
-    return line, out
+    return line
 
 
 def run_c1_train(steps: int, lr: int = 128, frames: int = 3, scale: int = 4, precision: str = "fp32", max_grad_norm: Optional[float] = None,
@@ -333,8 +405,20 @@ def main(argv=None):
     ap.add_argument("--frames", type=int, default=3, help="frames of the clip (3 = one window)")
     ap.add_argument("--scale", type=int, default=4, choices=[2, 3, 4], help="4 = the reference's geometry; 2 = C1's label")
     ap.add_argument("--precision", default="fp32", choices=["fp16", "fp32"])
-    ap.add_argument("--pix-fmt", default=None, choices=sorted(YUV_FORMATS),
-                    help="the clip enters and leaves as 4:2:0 frames of this format through ClipRunner (default: the RGB path)")
+    ap.add_argument("--pix-fmt", default=None, choices=sorted(PIX_FORMATS),
+                    help="the clip enters and leaves as Y'CbCr frames of this format through ClipRunner (default: the RGB path); with a "
+                         "headerless --input: the file's format")
+    ap.add_argument("--input", default=None, metavar="PATH",
+                    help="stream this clip through ClipRunner instead of the synthetic one: a .y4m file, or a headerless file with --size and --pix-fmt")
+    ap.add_argument("--size", default=None, metavar="HxW", help="with a headerless --input: the frame size")
+    ap.add_argument("--output", default=None, metavar="PATH", help="with --input: write the output frames there (.y4m gets a header, anything else is raw)")
+    ap.add_argument("--out-pix-fmt", default=None, choices=sorted(PIX_FORMATS), help="with --input: the output format (default: the input's)")
+    ap.add_argument("--matrix", default="bt709", choices=["bt601", "bt709", "bt2020"], help="with --input: the Y'CbCr matrix of the file")
+    ap.add_argument("--siting", default=None, choices=sorted(YUV_SITINGS), help="with --input: the chroma siting (overrides the file's)")
+    ap.add_argument("--checkpoint", default=None, metavar="PATH", help="with --input: load the SR net from this checkpoint (default: the seeded weights)")
+    ap.add_argument("--scale-down", type=int, default=None, metavar="N",
+                    help="with --input: decimate the file's frames by N before the model (default 1: the file is upscaled by --scale; with "
+                         "--score the default is --scale: the file is the ground truth)")
     ap.add_argument("--score", default=None, choices=sorted(METRIC_CHANNELS),
                     help="with --pix-fmt: per-frame PSNR / SSIM of the output against the synthetic HR clip, on RGB or on luma (BT.601 Y)")
     ap.add_argument("--decimate", default="nearest", choices=list(ClipRunner.DECIMATE),
@@ -362,6 +446,33 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.loss_path is not None and args.train_steps is None:
         ap.error("--loss-path needs --train-steps")
+    if args.input is None:
+        for name in ("size", "output", "out_pix_fmt", "siting", "checkpoint", "scale_down"):
+            if getattr(args, name) is not None:
+                ap.error(f"--{name.replace('_', '-')} needs --input")
+    else:
+        if args.train_steps is not None or args.cut_at is not None:
+            ap.error("--input takes neither --train-steps nor --cut-at")
+        if args.input.endswith(".y4m") == (args.size is not None or args.pix_fmt is not None):
+            ap.error("--input: a .y4m file carries its size and format (no --size / --pix-fmt); a headerless file needs both")
+        if args.size is not None:
+            try:
+                args.size = tuple(int(v) for v in args.size.lower().split("x"))
+                assert len(args.size) == 2
+            except (ValueError, AssertionError):
+                ap.error("--size is HxW, two integers")
+        if args.multiscale and args.score is None:
+            ap.error("--multiscale needs --score (it is scored beside the estimate)")
+        if (args.baseline is not None or args.temporal is not None) and args.score is None:
+            ap.error("--baseline and --temporal need --score (they are scored beside the estimate)")
+        if args.scene_thresholds is not None and args.scene is None:
+            ap.error("--scene-thresholds needs --scene")
+        line = run_file(args.input, args.output, size=args.size, pix_fmt=args.pix_fmt, out_pix_fmt=args.out_pix_fmt, matrix=args.matrix,
+                        siting=args.siting, checkpoint=args.checkpoint, scale_down=args.scale_down, frames=None, scale=args.scale,
+                        precision=args.precision, score=args.score, decimate=args.decimate, baseline=args.baseline, temporal=args.temporal,
+                        scene=args.scene, scene_thresholds=args.scene_thresholds, multiscale=args.multiscale)
+        print(json.dumps(line))
+        return
     if args.score is not None and args.pix_fmt is None:
         ap.error("--score needs --pix-fmt (the streamed clip runner scores its frames)")
     if args.decimate != "nearest" and args.pix_fmt is None:

@@ -18,8 +18,11 @@
                             of consecutive LR frames summed per pair, the cut rule on the sums as device flags, the 3-frame window and
                             the fed-back estimate composed under two flags, and the host step that applies the same rule to the sums
 
-`clip_runner.ClipRunner` streams a clip through all six; `driver` imports every public name here, so `driver.frame_metrics` and the rest
-resolve as before.  Transfer functions and 4:2:2 / 4:4:4 stay out.
+    pix_ingest / pix_write / ingest_item_pix / frames_to_pix   the same two steps for every planar layout: the four 4:2:0 names through
+                            the library above, yuv422p, yuv444p, yuv422p10le and yuv444p10le through include/vsr_hip_pix.h
+
+`clip_runner.ClipRunner` streams a clip through all of them; `driver` imports every public name here, so `driver.frame_metrics` and the
+rest resolve as before.  `y4m` reads and writes the YUV4MPEG2 files a clip arrives in.  Transfer functions stay out.
 """
 from __future__ import annotations
 
@@ -99,14 +102,10 @@ def _coef12(coef12) -> np.ndarray:
     return c
 
 
-@L.on_device
-def yuv_ingest(frames: torch.Tensor, shape: Tuple[int, int], fmt: str, coef12, siting: str = "left", lr_shape: Optional[Tuple[int, int]] = None,
-               want_hr: bool = False, lr_out: Optional[torch.Tensor] = None):
-    """The low-level call (vsr_yuv_ingest) with any 12 coefficients: uint8 [..., frame_bytes] on the device -> float32 RGB
-    (lr [..., h, w, 3], hr [..., H, W, 3] | None); `lr_shape` = (h, w), default the full size; `lr_out`: write lr there."""
+def _ingest(side: str, code: int, fb: int, frames: torch.Tensor, shape, fmt: str, coef12, siting: str, lr_shape, want_hr: bool, lr_out):
+    """What `yuv_ingest` and `pix_ingest` do alike around vsr_<side>_ingest: `code` is the format's code in that library, `fb` its frame bytes."""
     import ctypes
     H, W = int(shape[0]), int(shape[1])
-    fb = yuv_frame_bytes(fmt, H, W)
     if frames.dtype != torch.uint8 or frames.dim() < 1 or frames.shape[-1] != fb:
         raise ValueError(f"expected uint8 [..., {fb}] ({fmt} {H}x{W}), got {frames.dtype} {tuple(frames.shape)}")
     h, w = (H, W) if lr_shape is None else (int(lr_shape[0]), int(lr_shape[1]))
@@ -117,21 +116,20 @@ def yuv_ingest(frames: torch.Tensor, shape: Tuple[int, int], fmt: str, coef12, s
     if tuple(lr.shape) != lead + (h, w, 3):
         raise ValueError(f"lr_out must be {lead + (h, w, 3)}, got {tuple(lr.shape)}")
     hr = torch.empty(lead + (H, W, 3), dtype=torch.float32, device=frames.device) if want_hr else None
-    Y = L.load_yuv()
-    L.check(Y.vsr_yuv_ingest(L.dptr(frames, torch.uint8), YUV_FORMATS[fmt], c.ctypes.data_as(ctypes.c_void_p), YUV_SITINGS[siting], L.dptr(lr),
-                             L.optr(hr), F, H, W, h, w, L.stream()), "yuv_ingest", lib=Y)
+    Y = getattr(L, "load_" + side)()
+    L.check(getattr(Y, f"vsr_{side}_ingest")(L.dptr(frames, torch.uint8), code, c.ctypes.data_as(ctypes.c_void_p), YUV_SITINGS[siting], L.dptr(lr),
+                                             L.optr(hr), F, H, W, h, w, L.stream()), side + "_ingest", lib=Y)
     return lr, hr
 
 
-@L.on_device
-def yuv_write(frames: torch.Tensor, fmt: str, coef12, siting: str = "left", out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """The low-level call (vsr_yuv_write) with any 12 coefficients: float32 [..., H, W, 3] -> uint8 [..., frame_bytes]."""
+def _write(side: str, codes: dict, frame_bytes, frames: torch.Tensor, fmt: str, coef12, siting: str, out) -> torch.Tensor:
+    """What `yuv_write` and `pix_write` do alike around vsr_<side>_write: `codes` the library's formats, `frame_bytes` their sizes."""
     import ctypes
     if frames.dim() < 3 or frames.shape[-1] != 3:
         raise ValueError(f"expected float32 [..., H, W, 3], got {tuple(frames.shape)}")
     f = frames.detach().to(torch.float32).contiguous()
     H, W = int(f.shape[-3]), int(f.shape[-2])
-    fb = yuv_frame_bytes(fmt, H, W)
+    fb = frame_bytes(fmt, H, W)
     lead = tuple(f.shape[:-3])
     F = int(np.prod(lead)) if lead else 1
     c = _coef12(coef12)
@@ -139,10 +137,25 @@ def yuv_write(frames: torch.Tensor, fmt: str, coef12, siting: str = "left", out:
         out = torch.empty(lead + (fb,), dtype=torch.uint8, device=f.device)
     elif tuple(out.shape) != lead + (fb,):
         raise ValueError(f"out must be {lead + (fb,)}, got {tuple(out.shape)}")
-    Y = L.load_yuv()
-    L.check(Y.vsr_yuv_write(L.dptr(f), L.dptr(out, torch.uint8), YUV_FORMATS[fmt], c.ctypes.data_as(ctypes.c_void_p), YUV_SITINGS[siting],
-                            F, H, W, L.stream()), "yuv_write", lib=Y)
+    Y = getattr(L, "load_" + side)()
+    L.check(getattr(Y, f"vsr_{side}_write")(L.dptr(f), L.dptr(out, torch.uint8), codes[fmt], c.ctypes.data_as(ctypes.c_void_p), YUV_SITINGS[siting],
+                                            F, H, W, L.stream()), side + "_write", lib=Y)
     return out
+
+
+@L.on_device
+def yuv_ingest(frames: torch.Tensor, shape: Tuple[int, int], fmt: str, coef12, siting: str = "left", lr_shape: Optional[Tuple[int, int]] = None,
+               want_hr: bool = False, lr_out: Optional[torch.Tensor] = None):
+    """The low-level call (vsr_yuv_ingest) with any 12 coefficients: uint8 [..., frame_bytes] on the device -> float32 RGB
+    (lr [..., h, w, 3], hr [..., H, W, 3] | None); `lr_shape` = (h, w), default the full size; `lr_out`: write lr there."""
+    fb = yuv_frame_bytes(fmt, int(shape[0]), int(shape[1]))
+    return _ingest("yuv", YUV_FORMATS[fmt], fb, frames, shape, fmt, coef12, siting, lr_shape, want_hr, lr_out)
+
+
+@L.on_device
+def yuv_write(frames: torch.Tensor, fmt: str, coef12, siting: str = "left", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The low-level call (vsr_yuv_write) with any 12 coefficients: float32 [..., H, W, 3] -> uint8 [..., frame_bytes]."""
+    return _write("yuv", YUV_FORMATS, yuv_frame_bytes, frames, fmt, coef12, siting, out)
 
 
 def ingest_item_yuv(frames: torch.Tensor, shape: Tuple[int, int], fmt: str, scale: int = 4, want_hr: bool = True, matrix: str = "bt709",
@@ -163,6 +176,74 @@ def frames_to_yuv(frames: torch.Tensor, fmt: str, matrix: str = "bt709", full_ra
     """float32 HR frames [...,H,W,3] (R'G'B' in 0..255) -> packed 4:2:0 frames uint8 [...,frame_bytes]: values clamped to 0..255, chroma
     from the filtered R'G'B', round half to even, clamped to the code range."""
     return yuv_write(frames, fmt, yuv_coefficients(fmt, matrix, full_range), siting)
+
+
+# ------------------------------------------------------------------------------------------------ every planar layout: 4:2:0, 4:2:2, 4:4:4
+_PIX_NEW = {"yuv422p": 0, "yuv444p": 1, "yuv422p10le": 2, "yuv444p10le": 3}   # the `fmt` codes of include/vsr_hip_pix.h
+PIX_FORMATS = {**YUV_FORMATS, **_PIX_NEW}   # name -> the code in its own library: the four of YUV_FORMATS (libvsr_hip_yuv.so) + libvsr_hip_pix.so's
+
+
+def _pix_depth(fmt: str) -> int:
+    if fmt not in PIX_FORMATS:
+        raise ValueError(f"unknown pixel format {fmt!r} (known: {', '.join(PIX_FORMATS)})")
+    return 10 if fmt.endswith("10le") else 8
+
+
+def pix_chroma(fmt: str) -> str:
+    """"420" | "422" | "444": which axes of `fmt` carry half the chroma samples."""
+    _pix_depth(fmt)
+    return "422" if "422" in fmt else "444" if "444" in fmt else "420"
+
+
+def pix_frame_bytes(fmt: str, H: int, W: int) -> int:
+    """Bytes of one packed frame of any name of `PIX_FORMATS`: 3/2 (4:2:0), 2 (4:2:2) or 3 (4:4:4) samples per pixel, 1 or 2 bytes per
+    sample.  4:2:0 needs even H and W (`yuv_frame_bytes`), 4:2:2 an even W, 4:4:4 nothing but positive sizes."""
+    d = _pix_depth(fmt)
+    if fmt in YUV_FORMATS:
+        return yuv_frame_bytes(fmt, H, W)
+    ss = pix_chroma(fmt)
+    if H <= 0 or W <= 0 or (ss == "422" and W % 2):
+        raise ValueError(f"4:{ss[1:2]}:{ss[2:]} needs positive H and W{' and an even W' if ss == '422' else ''}, got {H} x {W}")
+    return H * W * (2 if ss == "422" else 3) * (2 if d == 10 else 1)
+
+
+def pix_coefficients(fmt: str, matrix: str = "bt709", full_range: bool = False, inverse: bool = False, dtype=np.float32) -> np.ndarray:
+    """`yuv_coefficients` for any name of `PIX_FORMATS`: the 12 values depend on the bit depth alone, not on the chroma layout."""
+    return yuv_coefficients("yuv420p10le" if _pix_depth(fmt) == 10 else "yuv420p", matrix, full_range, inverse, dtype)
+
+
+@L.on_device
+def pix_ingest(frames: torch.Tensor, shape: Tuple[int, int], fmt: str, coef12, siting: str = "left", lr_shape: Optional[Tuple[int, int]] = None,
+               want_hr: bool = False, lr_out: Optional[torch.Tensor] = None):
+    """`yuv_ingest` for any name of `PIX_FORMATS`: a 4:2:0 name goes to vsr_yuv_ingest, a 4:2:2 / 4:4:4 name to vsr_pix_ingest."""
+    fb = pix_frame_bytes(fmt, int(shape[0]), int(shape[1]))
+    side = "yuv" if fmt in YUV_FORMATS else "pix"
+    return _ingest(side, PIX_FORMATS[fmt], fb, frames, shape, fmt, coef12, siting, lr_shape, want_hr, lr_out)
+
+
+@L.on_device
+def pix_write(frames: torch.Tensor, fmt: str, coef12, siting: str = "left", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`yuv_write` for any name of `PIX_FORMATS`: a 4:2:0 name goes to vsr_yuv_write, a 4:2:2 / 4:4:4 name to vsr_pix_write."""
+    _pix_depth(fmt)
+    return _write("yuv" if fmt in YUV_FORMATS else "pix", PIX_FORMATS, pix_frame_bytes, frames, fmt, coef12, siting, out)
+
+
+def ingest_item_pix(frames: torch.Tensor, shape: Tuple[int, int], fmt: str, scale: int = 4, want_hr: bool = True, matrix: str = "bt709",
+                    full_range: bool = False, siting: str = "left"):
+    """`ingest_item_yuv` for any name of `PIX_FORMATS`."""
+    if frames.dim() != 3 or frames.shape[1] != 3:
+        raise ValueError(f"expected uint8 [T,3,frame_bytes], got {frames.dtype} {tuple(frames.shape)}")
+    H, W = shape
+    lr, hr = pix_ingest(frames.contiguous(), shape, fmt, pix_coefficients(fmt, matrix, full_range, inverse=True), siting,
+                        (int(H / scale), int(W / scale)), want_hr)
+    if hr is None:
+        return lr, None, None
+    return lr, hr[:, 1:2].clone(), hr   # (the clone: as in ingest_item)
+
+
+def frames_to_pix(frames: torch.Tensor, fmt: str, matrix: str = "bt709", full_range: bool = False, siting: str = "left") -> torch.Tensor:
+    """`frames_to_yuv` for any name of `PIX_FORMATS`."""
+    return pix_write(frames, fmt, pix_coefficients(fmt, matrix, full_range), siting)
 
 
 # ------------------------------------------------------------------------------------------------ resampling
