@@ -11,12 +11,17 @@ feeds it, on the GPU path and without OpenCV:
                             estimated_image); estimated_image = output` (main.py:196-203) -> HR frames (+ losses)
     frames_to_u8            HR write-out, float32 -> uint8 NHWC on the device (the step after the path; the reference never
                             writes its frames)
+    train_step / train_item the train step of one window (main.py:206-210) and the whole loop body of one dataset item (:196-210): what
+                            `run_c1_train` runs per step on the synthetic clip and `ClipTrainer` per sample of a real one
     save_checkpoint / load_checkpoint   utils/tools.py:68-73 and main.py:108-122,233-237: {'arch','epoch','state_dict':
                             SRmodel.model.state_dict(),'optimizer'} -- files interchange with the reference's
+    run_file_train          `--input clip.y4m --train-steps K`: `ClipTrainer` over a streamed file (patches cut and augmented on the
+                            device: `patch_table` / `patch_gather` / `patch_item` of `frames`), `--save DIR` writes a checkpoint of
+                            tensors and plain containers that `--input ... --checkpoint` takes back
 
 The device bindings for frames in, out, resampled and scored (4:2:0 I/O, the resampler, PSNR / SSIM, MS-SSIM, the warping error) live in
-`frames`, the streamed `ClipRunner` on top of them in `clip_runner`; their public names are imported here, so `driver.frame_metrics`,
-`driver.ClipRunner` and the rest resolve.
+`frames`, the streamed `ClipRunner` on top of them in `clip_runner`, `ClipTrainer` in `clip_trainer`; their public names are imported here,
+so `driver.frame_metrics`, `driver.ClipRunner`, `driver.ClipTrainer` and the rest resolve.
 
 `python -m video_super_resolution_amd.driver` is BASELINE.json's config C1 (3-frame 128x128 LR synthetic clip through the
 main-like plumbing) on the GPU path (`tools/c1_check.py` runs the CPU checker beside it and reports the PSNR between the two:
@@ -37,10 +42,11 @@ import torch
 
 from . import _lib as L
 from .clip_runner import ArraySource, ClipRunner, sums_layout  # noqa: F401
+from .clip_trainer import ClipTrainer  # noqa: F401
 from .frames import (METRIC_CHANNELS, METRIC_WHAT, MSSSIM_BETA, MSSSIM_MIN_SIZE, PIX_FORMATS, RESIZE_KERNELS, RESIZE_MAX_TAPS,  # noqa: F401
-                     SCENE_THRESHOLDS, WARP_OCC, YUV_FORMATS, YUV_SITINGS, FrameResizer, ewarp, frame_metrics, frame_msssim, frames_to_pix,
-                     frames_to_yuv, ingest_item_pix, ingest_item_yuv, msssim, msssim_levels, pix_coefficients, pix_frame_bytes, pix_ingest,
-                     pix_write, psnr_ssim, read_clip_yuv, resize_frames, resize_tables, scene_cuts, scene_flags, scene_sums, scene_window, ssim_window, truth_flows, warp_error,
+                     PATCH_FLAGS, SCENE_THRESHOLDS, WARP_OCC, YUV_FORMATS, YUV_SITINGS, FrameResizer, ewarp, frame_metrics, frame_msssim, frames_to_pix,
+                     frames_to_yuv, ingest_item_pix, ingest_item_yuv, msssim, msssim_levels, patch_gather, patch_item, patch_table,
+                     pix_coefficients, pix_frame_bytes, pix_ingest, pix_write, psnr_ssim, read_clip_yuv, resize_frames, resize_tables, scene_cuts, scene_flags, scene_sums, scene_window, ssim_window, truth_flows, warp_error,
                      yuv_coefficients, yuv_frame_bytes, yuv_ingest, yuv_write)
 from .y4m import RawReader, RawWriter, Y4MReader, Y4MWriter  # noqa: F401
 
@@ -163,6 +169,16 @@ def train_step(model, optimizer, x, y, high_frame, estimated_image, loss_value=N
     loss.backward()
     optimizer.step()
     return output.detach(), loss
+
+
+def train_item(model, optimizer, data, target, high_frames):
+    """main.py:196-210 for one dataset item: the gradients zeroed, the item's windows without gradient (`run_item`: their losses and the
+    estimate), then `train_step` on the last window with the mean of the windows' losses as the loss value.  What `run_c1_train` does
+    per step on the synthetic clip and `ClipTrainer` per sample of a real one.  -> the step's loss (a 0-d tensor where the loss path left it)."""
+    optimizer.zero_grad()
+    _, window_losses, est = run_item(model, data, target, high_frames, train=True)                 # main.py:199-203
+    _, loss = train_step(model, optimizer, data[-1], target[-1], high_frames[-1], est, sum(window_losses) / len(window_losses))
+    return loss.detach()
 
 
 # ------------------------------------------------------------------------------------------------ checkpoints
@@ -385,15 +401,64 @@ def run_c1_train(steps: int, lr: int = 128, frames: int = 3, scale: int = 4, pre
     optimizer = optim.Adam(model.parameters(), lr=learning_rate, max_grad_norm=max_grad_norm)
     losses, norms_sq = [], []
     for _ in range(steps):
-        optimizer.zero_grad()
-        _, window_losses, est = run_item(model, data, target, high_frames, train=True)                 # main.py:199-203
-        _, loss = train_step(model, optimizer, data[-1], target[-1], high_frames[-1], est, sum(window_losses) / len(window_losses))
-        losses.append(loss.detach())
+        losses.append(train_item(model, optimizer, data, target, high_frames))
         if optimizer.last_grad_norm_sq is not None:
             norms_sq.append(optimizer.last_grad_norm_sq.clone())
     line.update(train_steps=steps, learning_rate=learning_rate, max_grad_norm=max_grad_norm, loss_path=loss_path,
                 loss=[round(float(v), 6) for v in torch.stack(losses).cpu()] if losses else [],
                 grad_norm=[round(float(v) ** 0.5, 6) for v in torch.stack(norms_sq).cpu()] if norms_sq else None)
+    return line, model
+
+
+def run_file_train(path: str, steps: int, size: Optional[Tuple[int, int]] = None, pix_fmt: Optional[str] = None, matrix: str = "bt709",
+                   siting: Optional[str] = None, checkpoint: Optional[str] = None, scale: int = 4, precision: str = "fp32", patch: int = 64,
+                   frames_per_sample: int = 3, group: int = 8, seed: int = 0, decimate: str = "nearest",
+                   max_grad_norm: Optional[float] = None, learning_rate: float = 1e-3, loss_path: str = "reference",
+                   save: Optional[str] = None, model=None):
+    """`steps` train steps on patches of a clip file through `ClipTrainer.run_stream`: `path`, `size`, `pix_fmt`, `siting`, `model` as
+    `run_file`'s; `checkpoint`: resume (loaded into the model before the first step).  The file is read once, or until `steps` are done.
+    `save`: a directory; the trained SR net goes to `<save>/VSR_train-checkpoint.pth.tar` as `checkpoint_state` with the optimizer's
+    `state_dict()` under "optimizer_state" and None under "optimizer": tensors and plain containers only, so `load_checkpoint` takes it
+    untrusted (the reference pickles the optimizer OBJECT; files written here do not).  -> (result line, model)."""
+    from . import VSR, optim
+    from .weights import fill_module_
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    if path.endswith(".y4m"):
+        src = Y4MReader(path, siting=siting)
+    else:
+        if size is None or pix_fmt is None:
+            raise ValueError("a headerless clip needs size=(H, W) and pix_fmt")
+        src = RawReader(path, size, pix_fmt, siting or "left")
+    weights = "seeded"
+    if model is None:
+        model = fill_module_(VSR(upscale_factor=scale).eval(), seed=0).to(dev)
+        model.precision = model.model.precision = precision
+    else:
+        weights = "given"
+    if checkpoint is not None:
+        load_checkpoint(model, checkpoint, map_location=dev)
+        weights = checkpoint
+    optimizer = optim.Adam(model.parameters(), lr=learning_rate, max_grad_norm=max_grad_norm)
+    try:
+        trainer = ClipTrainer(model, optimizer, src.shape, src.fmt, patch=patch, frames_per_sample=frames_per_sample, group=group,
+                              seed=seed, decimate=decimate, matrix=matrix, full_range=src.full_range, siting=src.siting, loss_path=loss_path)
+        trainer.run_stream(src, max_steps=steps)
+    finally:
+        src.close()
+    written = None
+    if save is not None:
+        os.makedirs(save, exist_ok=True)
+        state = checkpoint_state(model, epoch=1, optimizer=None)
+        state["optimizer_state"] = optimizer.state_dict()
+        written = save_checkpoint(state, False, save, "VSR", filename="train-checkpoint.pth.tar")
+    line = dict(config=f"train steps on {patch}x{patch} LR patches of a {src.shape[0]}x{src.shape[1]} clip from a file, x{scale}, streamed clip "
+                       f"trainer, GPU path",
+                input=path, frames=trainer.frames_in, pix_fmt_in=src.fmt, precision=precision, weights=weights, train_steps=trainer.steps,
+                patch=patch, frames_per_sample=frames_per_sample, group=group, seed=seed, decimate=decimate, loss_path=loss_path,
+                learning_rate=learning_rate, max_grad_norm=max_grad_norm, frames_skipped=trainer.frames_skipped,
+                loss=[round(float(v), 6) for v in trainer.losses],
+                grad_norm=[round(float(v), 6) for v in trainer.grad_norms] if trainer.grad_norms is not None else None, checkpoint=written)
     return line, model
 
 
@@ -438,7 +503,17 @@ def main(argv=None):
     ap.add_argument("--cut-at", type=int, default=None, metavar="K",
                     help="with --pix-fmt: the synthetic clip's frames from K on come from a second seed (a scene cut before frame K)")
     ap.add_argument("--train-steps", type=int, default=None, metavar="K",
-                    help="after the no-grad windows: K train steps on the last window (optim.Adam); the line carries the loss per step")
+                    help="after the no-grad windows: K train steps on the last window (optim.Adam); the line carries the loss per step; "
+                         "with --input: K train steps on patches of the file (ClipTrainer), read once or until K steps are done")
+    ap.add_argument("--patch", type=int, default=None, metavar="P",
+                    help="with --input and --train-steps: the LR patch edge (default 64; the HR patch is --scale times that)")
+    ap.add_argument("--frames-per-sample", type=int, default=None, metavar="N",
+                    help="with --input and --train-steps: consecutive frames per training sample (default 3: one window)")
+    ap.add_argument("--group", type=int, default=None, metavar="G",
+                    help="with --input and --train-steps: frames resident on the device at a time (default 8)")
+    ap.add_argument("--seed", type=int, default=None, help="with --input and --train-steps: the seed of the patch draws (default 0)")
+    ap.add_argument("--save", default=None, metavar="DIR",
+                    help="with --input and --train-steps: write DIR/VSR_train-checkpoint.pth.tar (tensors and plain containers only)")
     ap.add_argument("--max-grad-norm", type=float, default=None, metavar="X",
                     help="with --train-steps: clip the global gradient norm at X on the device; the line carries the norm per step")
     ap.add_argument("--loss-path", default=None, choices=["reference", "fused"],
@@ -446,13 +521,17 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.loss_path is not None and args.train_steps is None:
         ap.error("--loss-path needs --train-steps")
+    if args.input is None or args.train_steps is None:
+        for name in ("patch", "frames_per_sample", "group", "seed", "save"):
+            if getattr(args, name) is not None:
+                ap.error(f"--{name.replace('_', '-')} needs --input and --train-steps (the streamed clip trainer)")
     if args.input is None:
         for name in ("size", "output", "out_pix_fmt", "siting", "checkpoint", "scale_down"):
             if getattr(args, name) is not None:
                 ap.error(f"--{name.replace('_', '-')} needs --input")
     else:
-        if args.train_steps is not None or args.cut_at is not None:
-            ap.error("--input takes neither --train-steps nor --cut-at")
+        if args.cut_at is not None:
+            ap.error("--input takes no --cut-at (the cut is made in the synthetic clip)")
         if args.input.endswith(".y4m") == (args.size is not None or args.pix_fmt is not None):
             ap.error("--input: a .y4m file carries its size and format (no --size / --pix-fmt); a headerless file needs both")
         if args.size is not None:
@@ -461,6 +540,28 @@ def main(argv=None):
                 assert len(args.size) == 2
             except (ValueError, AssertionError):
                 ap.error("--size is HxW, two integers")
+        if args.train_steps is not None:
+            for name in ("output", "out_pix_fmt", "scale_down", "score", "baseline", "temporal", "scene", "scene_thresholds"):
+                if getattr(args, name) is not None:
+                    ap.error(f"--input with --train-steps trains on the file and writes no frames: it takes no --{name.replace('_', '-')}")
+            if args.multiscale:
+                ap.error("--input with --train-steps trains on the file and writes no frames: it takes no --multiscale")
+            if args.train_steps <= 0:
+                ap.error("--input with --train-steps takes a positive count")
+            patch, n, group = (64 if args.patch is None else args.patch, 3 if args.frames_per_sample is None else args.frames_per_sample,
+                               8 if args.group is None else args.group)
+            if patch <= 0:
+                ap.error("--patch is a positive LR patch edge")
+            if n < 3:
+                ap.error("--frames-per-sample is at least 3 (one window)")
+            if group < n:
+                ap.error("--group must hold a sample: at least --frames-per-sample frames")
+            line, _ = run_file_train(args.input, args.train_steps, size=args.size, pix_fmt=args.pix_fmt, matrix=args.matrix, siting=args.siting,
+                                     checkpoint=args.checkpoint, scale=args.scale, precision=args.precision, patch=patch,
+                                     frames_per_sample=n, group=group, seed=args.seed or 0, decimate=args.decimate,
+                                     max_grad_norm=args.max_grad_norm, loss_path=args.loss_path or "reference", save=args.save)
+            print(json.dumps(line))
+            return
         if args.multiscale and args.score is None:
             ap.error("--multiscale needs --score (it is scored beside the estimate)")
         if (args.baseline is not None or args.temporal is not None) and args.score is None:

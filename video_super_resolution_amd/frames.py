@@ -1,4 +1,5 @@
-"""Frames in, out, resampled, scored and watched for scene cuts on the device: the Python side of six side libraries, one section each.
+"""Frames in, out, resampled, scored, watched for scene cuts and cut into training samples on the device: the Python side of the side
+libraries for frames, one section each.
 
     read_clip_yuv / ingest_item_yuv / frames_to_yuv     ingest, and write-out for what decoders emit: packed Y'CbCr 4:2:0 frames
                             (yuv420p, nv12, yuv420p10le, p010le), converted on the device (include/vsr_hip_yuv.h); the matrix
@@ -20,8 +21,11 @@
 
     pix_ingest / pix_write / ingest_item_pix / frames_to_pix   the same two steps for every planar layout: the four 4:2:0 names through
                             the library above, yuv422p, yuv444p, yuv422p10le and yuv444p10le through include/vsr_hip_pix.h
+    patch_table / patch_gather / patch_item   training samples (include/vsr_hip_patch.h): random crops, the eight symmetries of the
+                            square and time reversal drawn on the host as a table, all samples of a step cut from the resident frames
+                            in one launch with their LR patches, and a sample as the (data, target, high_frames) of the train loop
 
-`clip_runner.ClipRunner` streams a clip through all of them; `driver` imports every public name here, so `driver.frame_metrics` and the
+`clip_runner.ClipRunner` streams a clip through the first six, `clip_trainer.ClipTrainer` trains on patches of one; `driver` imports every public name here, so `driver.frame_metrics` and the
 rest resolve as before.  `y4m` reads and writes the YUV4MPEG2 files a clip arrives in.  Transfer functions stay out.
 """
 from __future__ import annotations
@@ -704,3 +708,105 @@ def scene_cuts(sums, thresholds=None) -> Tuple[np.ndarray, np.ndarray]:
         m_prev = np.concatenate([[0.0], m[:-1]])
         cuts = (m >= t_abs) & (m >= ratio * m_prev)
     return cuts, m
+
+
+# ------------------------------------------------------------------------------------------------ training patches
+PATCH_FLAGS = {"flip_x": 1, "flip_y": 2, "transpose": 4, "reverse": 8}   # the `flags` bits of include/vsr_hip_patch.h
+PATCH_MAX_B = 64                                                          # VSR_PATCH_MAX_B
+
+
+def _patch_shape(patch) -> Tuple[int, int]:
+    """`patch` as (Ph, Pw): one edge for a square patch, or the pair."""
+    if isinstance(patch, (int, np.integer)):
+        return int(patch), int(patch)
+    Ph, Pw = patch
+    return int(Ph), int(Pw)
+
+
+def patch_table(rng, B: int, G: int, n: int, shape: Tuple[int, int], patch, S: int, augment: bool = True,
+                transpose: Optional[bool] = None) -> np.ndarray:
+    """B training samples drawn from `G` resident frames of `shape` = (H, W) as the table vsr_patch_gather takes: int32 [B,4] of
+    {t0, y0, x0, flags}; `patch` = the HR patch (one edge or (Ph, Pw)), `n` the frames per sample, `S` the scale.  Pure host code; `rng`
+    is an `np.random.RandomState`.  The draw order is part of the contract (same seed, same table).  Per row, in this order:
+        1. flags = rng.randint(16)     (not drawn, 0, when `augment` is false; bit 4, the transposition, masked off AFTER the draw when
+                                        Ph != Pw, unless the caller passes transpose=True; transpose=False masks it off always)
+        2. t0 = rng.randint(G - n + 1)
+        3. y0 = rng.randint((H - ch) // S + 1) * S      (ch, cw) = (Pw, Ph) where bit 4 is set, else (Ph, Pw)
+        4. x0 = rng.randint((W - cw) // S + 1) * S
+    Origins are multiples of S, so both LR modes of `patch_gather` accept every row."""
+    Ph, Pw = _patch_shape(patch)
+    H, W = int(shape[0]), int(shape[1])
+    B, G, n, S = int(B), int(G), int(n), int(S)
+    if B <= 0 or n <= 0 or G < n:
+        raise ValueError(f"need B > 0 and 0 < n <= G, got B {B}, n {n}, G {G}")
+    if S <= 0 or Ph <= 0 or Pw <= 0 or Ph % S or Pw % S:
+        raise ValueError(f"the patch of {Ph} x {Pw} must be a positive multiple of S = {S}")
+    may_transpose = (Ph == Pw) if transpose is None else bool(transpose)
+    if Ph > H or Pw > W or (may_transpose and (Pw > H or Ph > W)):
+        raise ValueError(f"the patch of {Ph} x {Pw} does not fit the frames of {H} x {W}")
+    table = np.empty((B, 4), dtype=np.int32)
+    for b in range(B):
+        flags = int(rng.randint(16)) if augment else 0
+        if not may_transpose:
+            flags &= ~PATCH_FLAGS["transpose"]
+        ch, cw = (Pw, Ph) if flags & PATCH_FLAGS["transpose"] else (Ph, Pw)
+        t0 = int(rng.randint(G - n + 1))
+        y0 = int(rng.randint((H - ch) // S + 1)) * S
+        x0 = int(rng.randint((W - cw) // S + 1)) * S
+        table[b] = (t0, y0, x0, flags)
+    return table
+
+
+@L.on_device
+def patch_gather(src: torch.Tensor, table, n: int, patch, S: int, lr_src: Optional[torch.Tensor] = None, want_hr: bool = True,
+                 hr_out: Optional[torch.Tensor] = None, lr_out: Optional[torch.Tensor] = None, want_lr: bool = True):
+    """The samples of `table` (int32 [B,4] on the HOST, as `patch_table` draws them) cut from `src`, float32 RGB [G,H,W,3] on the device,
+    in one launch (vsr_patch_gather, include/vsr_hip_patch.h) -> (hr [B,n,Ph,Pw,3] | None, lr [B,n,Ph/S,Pw/S,3]).  `lr_src` None: lr is
+    the nearest decimation of the augmented patch, lr[i][j] = hr[i S][j S]; `lr_src` [G,H/S,W/S,3]: the frames reduced beforehand, cut and
+    augmented the same way.  `want_hr=False`: only lr; `want_lr=False`: only hr (the other is None).  `hr_out` / `lr_out`: write there.
+    Nothing is synchronised."""
+    import ctypes
+    Ph, Pw = _patch_shape(patch)
+    S, n = int(S), int(n)
+    if src.dim() != 4 or src.shape[-1] != 3:
+        raise ValueError(f"expected float32 [G,H,W,3], got {tuple(src.shape)}")
+    G, H, W = int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
+    t = np.ascontiguousarray(np.asarray(table, dtype=np.int32))
+    if t.ndim != 2 or t.shape[1] != 4 or t.shape[0] == 0:
+        raise ValueError(f"expected a table int32 [B,4] of {{t0, y0, x0, flags}}, got {t.shape}")
+    B = int(t.shape[0])
+    if S <= 0 or Ph % S or Pw % S:
+        raise ValueError(f"the patch of {Ph} x {Pw} must be a multiple of S = {S}")
+    if lr_src is not None and (tuple(lr_src.shape) != (G, H // S, W // S, 3) or H % S or W % S or lr_src.device != src.device):
+        raise ValueError(f"lr_src must be float32 {(G, H // S, W // S, 3)} on {src.device} (frames a multiple of S = {S}), got "
+                         f"{tuple(lr_src.shape)} on {lr_src.device}")
+    M = L.load_patch()
+    ps, pl = L.dptr(src), L.optr(lr_src)   # (raises on CPU tensors, on anything but float32 and on strided views)
+
+    def out(given, shape, name):
+        if given is None:
+            return torch.empty(shape, dtype=torch.float32, device=src.device)
+        if tuple(given.shape) != shape or given.device != src.device:
+            raise ValueError(f"{name} must be float32 {shape} on {src.device}, got {tuple(given.shape)} on {given.device}")
+        return given
+
+    hr = out(hr_out, (B, n, Ph, Pw, 3), "hr_out") if want_hr or hr_out is not None else None
+    lr = out(lr_out, (B, n, Ph // S, Pw // S, 3), "lr_out") if want_lr or lr_out is not None else None
+    if hr is None and lr is None:
+        raise ValueError("nothing is asked for (want_hr and want_lr are both false)")
+    L.check(M.vsr_patch_gather(ps, G, H, W, pl, S, t.ctypes.data_as(ctypes.c_void_p), B, n, Ph, Pw, L.optr(hr), L.optr(lr), L.stream()),
+            "patch_gather", lib=M)
+    return hr, lr
+
+
+def patch_item(hr: torch.Tensor, lr: torch.Tensor, b: int):
+    """Sample `b` of `patch_gather`'s (hr [B,n,Hp,Wp,3], lr [B,n,h,w,3]) as one item of the train loop -> (data [n-2,3,h,w,3], target
+    [n-2,1,Hp,Wp,3], high_frames [n-2,3,Hp,Wp,3]): the overlapping 3-frame windows lr[b, t:t+3] and hr[b, t:t+3], target the middle frame
+    (as `ingest_item`).  `data` is a view; `high_frames` and `target` are their own storage: VSR.forward overwrites high_frames[t][1] in
+    place, and views of one run would hand the next window a frame the previous one has overwritten."""
+    n = int(hr.shape[1])
+    if hr.dim() != 5 or lr.dim() != 5 or n < 3 or lr.shape[1] != n or lr.shape[0] != hr.shape[0]:
+        raise ValueError(f"expected hr [B,n >= 3,Hp,Wp,3] and lr [B,n,h,w,3], got {tuple(hr.shape)} and {tuple(lr.shape)}")
+    data = lr[b].unfold(0, 3, 1).permute(0, 4, 1, 2, 3)            # [n-2,3,h,w,3]: window t is lr[b, t:t+3]
+    high_frames = hr[b].unfold(0, 3, 1).permute(0, 4, 1, 2, 3).contiguous()
+    return data, high_frames[:, 1:2].clone(), high_frames
