@@ -4,7 +4,8 @@ ring, the window formed on the device, the HR frame written out in the output fo
 to a sink from its pinned slot: no host array of the clip's length exists on either side (`run_stream`; `run` is the array form).  What a run scores (`score=`, `baseline=`, `temporal=`) is a list of series, each a range of rows of one
 float64 tensor of sums (`sums_layout`); with `multiscale=True` the frames' multi-scale SSIM sums go into a tensor of their own; with
 `scene="sad"` scene cuts are found and the window composed under them on the device, in
-tensors of their own; `driver` imports `ClipRunner`, so `driver.ClipRunner` resolves as before.
+tensors of their own; with `deinterlace="frame" | "field"` the frames of an interlaced clip are made progressive on the device before
+anything else sees them; `driver` imports `ClipRunner`, so `driver.ClipRunner` resolves as before.
 """
 from __future__ import annotations
 
@@ -14,7 +15,8 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 import torch
 
-from .frames import (METRIC_CHANNELS, MSSSIM_BETA, MSSSIM_MIN_SIZE, FrameResizer, _scene_thresholds, ewarp, frame_metrics, frame_msssim,
+from .frames import (DEINTERLACE, METRIC_CHANNELS, MSSSIM_BETA, MSSSIM_MIN_SIZE, FrameResizer, _scene_thresholds, deint_planes,
+                     deint_schedule, deinterlace, ewarp, frame_metrics, frame_msssim,
                      msssim, pix_coefficients, pix_frame_bytes, pix_ingest, pix_write, psnr_ssim, scene_flags, scene_sums, scene_window,
                      truth_flows, warp_error)
 
@@ -127,17 +129,35 @@ class ClipRunner:
     (t_abs, ratio), default `frames.SCENE_THRESHOLDS`: this project's choice, not validated on real video.  With `temporal="warp"` the
     rows of `ewarp`, `ewarp_truth` and `ewarp_baseline` whose flows cross a cut (row r where `cuts[r + 1]`) are NaN: a warping error
     across a cut measures nothing; `valid_share` stays as computed.  With `scene=None` the launches are the ones described above and
-    `cuts` and `scene_m` are None."""
+    `cuts` and `scene_m` are None.
+
+    `deinterlace="frame" | "field"` (`tff`: the top field is the first in time, default True): the source frames are interlaced and are
+    made progressive on the device by the rule of include/vsr_hip_deint.h before the conversion.  Every uploaded frame goes into a ring of
+    three raw device buffers; progressive frame k is produced into the two buffers the conversion reads (what an uploaded frame is
+    without this option) once its later neighbour i = k + 1 has arrived, the last one at the end of the source, with the neighbours and
+    parities of `frames.deint_schedule` (reflection at both ends).  "frame" keeps the first field in time of every frame: T' = T
+    progressive frames; "field" rebuilds a frame around each field: T' = 2 T, at twice the rate.  From there everything above holds with
+    "source frame" read as "progressive frame": the windows, `scene`, `score` (the truth of output frame j is the DEINTERLACED frame
+    j + 1, not a progressive original, which the runner never sees), `baseline`, `temporal`, `multiscale`, `sums_layout(T')`;
+    `run_stream` gives T' - 2 outputs and returns that number, `run` takes T >= 3 ("frame") or T >= 2 ("field") frames: the output equals
+    `ClipRunner(...).run(frames.deinterlace_clip(frames, shape, fmt_in, mode, tff))` byte for byte.  One launch per progressive frame on
+    the current stream; no upload, download or host wait is added (`h2d_bytes` stays T * in_bytes, `frames_in` T), an event orders every
+    reuse of a raw slot by the upload stream against the launches that read it.  Interlaced 4:2:0 chroma is deinterlaced per plane and
+    then read with the progressive siting: the field-dependent vertical chroma siting is ignored.  The rule is not validated on real
+    video.  `tff` without `deinterlace`, and a layout with a plane of fewer than 2 rows, are refused.  With `deinterlace=None` the
+    launches are the ones described above."""
 
     DECIMATE = ("nearest", "bicubic")
     BASELINE = (None, "bicubic")
     TEMPORAL = (None, "warp")
     SCENE = (None, "sad")
+    DEINTERLACE = DEINTERLACE
 
     def __init__(self, model, shape: Tuple[int, int], fmt_in: str, fmt_out: str, scale_down: int = 1, overlap: bool = True,
                  matrix: str = "bt709", full_range: bool = False, siting: str = "left", score: Optional[str] = None,
                  shave: Optional[int] = None, decimate: str = "nearest", baseline: Optional[str] = None, temporal: Optional[str] = None,
-                 occ=None, scene: Optional[str] = None, scene_thresholds=None, multiscale: bool = False):
+                 occ=None, scene: Optional[str] = None, scene_thresholds=None, multiscale: bool = False,
+                 deinterlace: Optional[str] = None, tff: Optional[bool] = None):
         if decimate not in self.DECIMATE:
             raise ValueError(f"decimate must be 'nearest' or 'bicubic', got {decimate!r}")
         if baseline not in self.BASELINE:
@@ -154,6 +174,11 @@ class ClipRunner:
             raise ValueError(f"scene must be None or 'sad', got {scene!r}")
         if scene_thresholds is not None and scene is None:
             raise ValueError("scene_thresholds is given but no scene detection is asked for (scene=None)")
+        if deinterlace not in self.DEINTERLACE:
+            raise ValueError(f"deinterlace must be None, 'frame' or 'field', got {deinterlace!r}")
+        if tff is not None and deinterlace is None:
+            raise ValueError("tff is given but the frames are not deinterlaced (deinterlace=None)")
+        self.deinterlace, self.tff = deinterlace, (None if deinterlace is None else True if tff is None else bool(tff))
         self.decimate, self.baseline, self.temporal, self.occ = decimate, baseline, temporal, occ
         self.scene, self.scene_thresholds = scene, (_scene_thresholds(scene_thresholds) if scene is not None else None)
         self.cuts = self.scene_m = None   # of the last run(): bool [T-1], float64 [T-1] with scene="sad"
@@ -193,6 +218,12 @@ class ClipRunner:
         self._pin_out = [torch.empty(self.out_bytes, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
         self._dev_in = [torch.empty(self.in_bytes, dtype=torch.uint8, device=dev) for _ in range(2)]
         self._dev_out = [torch.empty(self.out_bytes, dtype=torch.uint8, device=dev) for _ in range(2)]
+        self._raw = None
+        if deinterlace is not None:   # the interlaced frames as uploaded: frame i in slot i % 3, its neighbours in the other two
+            rows = min(p[1] for p in deint_planes(fmt_in, H, W)[0])
+            if rows < 2:
+                raise ValueError(f"deinterlace={deinterlace!r}: {fmt_in} {H}x{W} has a plane of {rows} row(s), which holds no two fields")
+            self._raw = [torch.empty(self.in_bytes, dtype=torch.uint8, device=dev) for _ in range(3)]
         self._ring = [torch.empty(self.lr_shape + (3,), dtype=torch.float32, device=dev) for _ in range(3)]
         self._truth = torch.empty(self.shape + (3,), dtype=torch.float32, device=dev) if score is not None else None
         if temporal is not None:   # the truth frame of the previous window stays: two alternating buffers
@@ -221,9 +252,10 @@ class ClipRunner:
 
     def run(self, frames: np.ndarray) -> np.ndarray:
         frames = np.asarray(frames)
-        if frames.dtype != np.uint8 or frames.ndim != 2 or frames.shape[1] != self.in_bytes or frames.shape[0] < 3:
-            raise ValueError(f"expected uint8 [T >= 3, {self.in_bytes}], got {frames.dtype} {frames.shape}")
-        out = np.empty((frames.shape[0] - 2, self.out_bytes), dtype=np.uint8)
+        least = 2 if self.deinterlace == "field" else 3
+        if frames.dtype != np.uint8 or frames.ndim != 2 or frames.shape[1] != self.in_bytes or frames.shape[0] < least:
+            raise ValueError(f"expected uint8 [T >= {least}, {self.in_bytes}], got {frames.dtype} {frames.shape}")
+        out = np.empty((self.progressive_frames(frames.shape[0]) - 2, self.out_bytes), dtype=np.uint8)
 
         def collect(j, frame):
             out[j] = frame
@@ -231,30 +263,62 @@ class ClipRunner:
         self.run_stream(ArraySource(frames), collect)
         return out
 
+    def progressive_frames(self, T: int) -> int:
+        """T': the frames the windows are formed over for `T` source frames (2 T with deinterlace="field", else T)."""
+        return 2 * T if self.deinterlace == "field" else T
+
     def run_stream(self, source, sink, frames: Optional[int] = None) -> int:
-        """`source` -> `sink`, frame by frame (the class docstring); returns the number of output frames, T - 2."""
+        """`source` -> `sink`, frame by frame (the class docstring); returns the number of output frames, T' - 2 (T' = T without
+        `deinterlace`)."""
         T = len(source) if frames is None else int(frames)
-        if T < 3:
-            raise ValueError(f"a run needs at least 3 source frames (one window), got {T}")
+        Tp = self.progressive_frames(T)
+        if Tp < 3:
+            raise ValueError(f"a run needs at least 3 {'progressive' if self.deinterlace else 'source'} frames (one window), got {Tp}")
         self.h2d_bytes = self.d2h_bytes = self.frames_in = self.frames_out = 0
         self.metrics = self.cuts = self.scene_m = None
         with torch.cuda.device(self.device), torch.no_grad():
-            st = self._begin(T)
+            st = self._begin(Tp)
             st.sink, st.T = sink, T
-            for i in range(T):
-                self._upload(st, i, source)
-                if i < 2:
-                    continue
-                self._forward(st, i)
-                if st.layout is not None:
-                    self._score(st, i - 2)
-                self._write_out(st, i - 2)
+            if self.deinterlace is None:
+                for i in range(T):
+                    self._upload(st, i, source)
+                    self._window(st, i)
+            else:
+                self._run_interlaced(st, T, source)
             self._drain(st)
             if st.scene_buf is not None:
-                self._collect_scene(st, T)
+                self._collect_scene(st, Tp)
             if st.layout is not None:
                 self.metrics = self._collect(st)
-        return T - 2
+        return Tp - 2
+
+    def _window(self, st, i: int) -> None:
+        """Once frame `i` >= 2 is in the ring: the window of frames i - 2 .. i, its scores and its output frame i - 2."""
+        if i < 2:
+            return
+        self._forward(st, i)
+        if st.layout is not None:
+            self._score(st, i - 2)
+        self._write_out(st, i - 2)
+
+    def _run_interlaced(self, st, T: int, source) -> None:
+        """`deinterlace`: raw frame i uploaded into slot i % 3 of the raw ring; the entries of `deint_schedule` whose three frames have
+        arrived (those of frame k when frame k + 1 is in; the last frame's with the last frame itself, the end of the source: its later
+        neighbour is the earlier one) produced into `_dev_in[q % 2]` on the current stream, progressive frame q then converted and its
+        window run as an uploaded frame's is."""
+        sched = deint_schedule(T, self.deinterlace, self.tff)
+        q = 0
+        for i in range(T):
+            self._fetch(st, i, source, self._raw[i % 3], st.deinterlaced)
+            while q < len(sched) and max(sched[q][:3]) <= i:
+                p, c, n, keep, kept_first = sched[q]
+                # (`_dev_in[q % 2]` was last read by progressive frame q - 2's conversion and by the truth of window q - 3, on this stream)
+                deinterlace(self._raw[p % 3], self._raw[c % 3], self._raw[n % 3], self.shape, self.fmt_in, keep, kept_first, out=self._dev_in[q % 2])
+                st.deinterlaced = torch.cuda.Event()   # the raw slots are free once this launch has read them
+                st.deinterlaced.record(st.main)
+                self._convert(st, q)
+                self._window(st, q)
+                q += 1
 
     def _begin(self, T: int):
         """The state of one run: the sink, the one tensor of sums, the streams and the events that order every reuse of a slot."""
@@ -278,6 +342,7 @@ class ClipRunner:
             sink=None, layout=layout,
             sums=None if layout is None else torch.empty((rows, 4), dtype=torch.float64, device=self.device),
             main=main, s_in=s_in, s_out=s_out, est=None, prev_est=None,
+            deinterlaced=None,        # deinterlace: the last launch that read the raw ring has finished (event on main)
             uploaded=[None, None],    # per input slot: the upload from its pinned buffer has finished (event on s_in)
             converted=[None, None],   # per input slot: the conversion has read its device buffer (event on main)
             copied=[None, None])      # per output slot: (frame index, event on s_out: the copy into its pinned buffer has finished)
@@ -285,20 +350,31 @@ class ClipRunner:
     def _upload(self, st, i: int, source) -> None:
         """Source frame `i`: read into its pinned slot, from there to the device on the copy-in stream, converted into ring slot i % 3 on
         the current one."""
+        self._fetch(st, i, source, self._dev_in[i % 2], st.converted[i % 2])
+        self._convert(st, i)
+
+    def _fetch(self, st, i: int, source, dst: torch.Tensor, free) -> None:
+        """Source frame `i`: read into pinned slot i % 2, from there into the device buffer `dst` on the copy-in stream once `free` (an
+        event on the current stream, or None: what last read `dst` has finished); the current stream then waits for the upload."""
         a = i % 2
         if st.uploaded[a] is not None:
             st.uploaded[a].synchronize()   # the pinned slot is free again (host wait on one event)
         if not source.read_into(self._pin_in[a].numpy()):   # (straight into the pinned slot: no temporary in between)
             raise ValueError(f"the source ended before frame {i} of the {st.T} asked for")
-        if st.converted[a] is not None:
-            st.s_in.wait_event(st.converted[a])
+        if free is not None:
+            st.s_in.wait_event(free)
         with torch.cuda.stream(st.s_in):
-            self._dev_in[a].copy_(self._pin_in[a], non_blocking=True)
+            dst.copy_(self._pin_in[a], non_blocking=True)
             st.uploaded[a] = torch.cuda.Event()
             st.uploaded[a].record(st.s_in)
         self.h2d_bytes += self.in_bytes
         self.frames_in += 1
         st.main.wait_event(st.uploaded[a])
+
+    def _convert(self, st, i: int) -> None:
+        """The frame in `_dev_in[i % 2]` (source frame `i`, or progressive frame `i` with `deinterlace`) converted into ring slot i % 3
+        on the current stream, and with `scene` the pair (i - 1, i) summed and flagged."""
+        a = i % 2
         # (ring slot i % 3 was last read by the window of frames i-3 .. i-1, stacked on this stream)
         if self._down is None:
             pix_ingest(self._dev_in[a], self.shape, self.fmt_in, self.coef_in, self.siting, self.lr_shape, lr_out=self._ring[i % 3])

@@ -28,7 +28,8 @@ main-like plumbing) on the GPU path (`tools/c1_check.py` runs the CPU checker be
 the package itself never touches the checker).
 Decoding compressed video (cv2.VideoCapture, video_utils.py:17-23) is out of scope: a clip enters as a uint8 RGB array
 (`.npy`, raw rgb24, or synthetic) or as planar Y'CbCr frames, 4:2:0, 4:2:2 or 4:4:4, in a `.y4m` file or headerless (`ffmpeg -f rawvideo`):
-`--input` streams such a file through `ClipRunner.run_stream` (`run_file`); transfer functions stay out.
+`--input` streams such a file through `ClipRunner.run_stream` (`run_file`), an interlaced one made progressive on the device first
+(`--deinterlace frame|field`, `frames.deinterlace`); transfer functions stay out.
 """
 from __future__ import annotations
 
@@ -43,9 +44,10 @@ import torch
 from . import _lib as L
 from .clip_runner import ArraySource, ClipRunner, sums_layout  # noqa: F401
 from .clip_trainer import ClipTrainer  # noqa: F401
-from .frames import (METRIC_CHANNELS, METRIC_WHAT, MSSSIM_BETA, MSSSIM_MIN_SIZE, PIX_FORMATS, RESIZE_KERNELS, RESIZE_MAX_TAPS,  # noqa: F401
+from .frames import (DEINTERLACE, METRIC_CHANNELS, METRIC_WHAT, MSSSIM_BETA, MSSSIM_MIN_SIZE, PIX_FORMATS, RESIZE_KERNELS, RESIZE_MAX_TAPS,  # noqa: F401
                      PATCH_FLAGS, SCENE_THRESHOLDS, WARP_OCC, YUV_FORMATS, YUV_SITINGS, FrameResizer, ewarp, frame_metrics, frame_msssim, frames_to_pix,
                      frames_to_yuv, ingest_item_pix, ingest_item_yuv, msssim, msssim_levels, patch_gather, patch_item, patch_table,
+                     deint_planes, deint_schedule, deinterlace, deinterlace_clip, deinterlace_planes,
                      pix_coefficients, pix_frame_bytes, pix_ingest, pix_write, psnr_ssim, read_clip_yuv, resize_frames, resize_tables, scene_cuts, scene_flags, scene_sums, scene_window, ssim_window, truth_flows, warp_error,
                      yuv_coefficients, yuv_frame_bytes, yuv_ingest, yuv_write)
 from .y4m import RawReader, RawWriter, Y4MReader, Y4MWriter  # noqa: F401
@@ -326,25 +328,45 @@ def run_file(path: str, output: Optional[str] = None, size: Optional[Tuple[int, 
              out_pix_fmt: Optional[str] = None, matrix: str = "bt709", siting: Optional[str] = None, checkpoint: Optional[str] = None,
              scale_down: Optional[int] = None, frames: Optional[int] = None, scale: int = 4, precision: str = "fp32",
              score: Optional[str] = None, decimate: str = "nearest", baseline: Optional[str] = None, temporal: Optional[str] = None,
-             scene: Optional[str] = None, scene_thresholds=None, multiscale: bool = False, model=None) -> dict:
+             scene: Optional[str] = None, scene_thresholds=None, multiscale: bool = False, model=None,
+             deinterlace: Optional[str] = None, field_order: Optional[str] = None) -> dict:
     """A clip file streamed through `ClipRunner.run_stream`: `path` a `.y4m` file (size, rate, format, siting and range from its header)
     or a headerless one (`size` = (H, W) and `pix_fmt` required); `output`: the output frames as `out_pix_fmt` (default: the input's),
     with a header when it ends in `.y4m` (S x the LR size, the input's F and A), raw otherwise, or None: the frames are dropped.  The file
     is decimated by `scale_down` (default 1; with `score`: `scale`, the file is the ground truth) and super-resolved by `scale`.  `siting`
     overrides the file's; `checkpoint`: `load_checkpoint` into the seeded model (`model`: use this one instead).  Host memory does not
-    depend on the clip's length.  -> the result line."""
+    depend on the clip's length.  `deinterlace` ("frame" | "field"): the file is interlaced and is made progressive on the device first
+    (`ClipRunner(deinterlace=...)`); the field order is the header's (It / Ib) unless `field_order` ("tff" | "bff") names it, which a
+    headerless file and a header without a field order need; an interlaced header without `deinterlace` is refused.  The output is
+    progressive; with "field" it has twice the input's frame rate.  -> the result line."""
     import time
     from . import VSR
     from .weights import fill_module_
-    dev = torch.device("cuda", 0)
-    torch.cuda.set_device(dev)
     S = scale
+    if field_order not in (None, "tff", "bff"):
+        raise ValueError(f"field_order must be None, 'tff' or 'bff', got {field_order!r}")
+    if field_order is not None and deinterlace is None:
+        raise ValueError("field_order is given but the clip is not deinterlaced (deinterlace=None)")
     if path.endswith(".y4m"):
-        src = Y4MReader(path, siting=siting)
+        src = Y4MReader(path, siting=siting, interlaced=True)
     else:
         if size is None or pix_fmt is None:
             raise ValueError("a headerless clip needs size=(H, W) and pix_fmt")
         src = RawReader(path, size, pix_fmt, siting or "left")
+    tff = None
+    if deinterlace is None:
+        if src.tff is not None:
+            src.close()
+            raise ValueError(f"{path}: the header says the clip is interlaced (I{'t' if src.tff else 'b'}): pass --deinterlace frame|field "
+                             f"(deinterlace=) to make it progressive on the device")
+    else:
+        tff = src.tff if field_order is None else field_order == "tff"
+        if tff is None:
+            src.close()
+            raise ValueError(f"{path}: nothing says which field comes first (a headerless file, or a header without It / Ib): "
+                             f"--deinterlace needs --field-order tff|bff (field_order=)")
+    dev = torch.device("cuda", 0)   # (after the refusals above: they need no device)
+    torch.cuda.set_device(dev)
     fmt_in, fmt_out = src.fmt, (out_pix_fmt or src.fmt)
     weights = "seeded"
     if model is None:
@@ -359,12 +381,15 @@ def run_file(path: str, output: Optional[str] = None, size: Optional[Tuple[int, 
         scale_down = S if score is not None else 1
     runner = ClipRunner(model, src.shape, fmt_in, fmt_out, scale_down=scale_down, matrix=matrix, full_range=src.full_range,
                         siting=src.siting, score=score, decimate=decimate, baseline=baseline, temporal=temporal, scene=scene,
-                        scene_thresholds=scene_thresholds, multiscale=multiscale)
+                        scene_thresholds=scene_thresholds, multiscale=multiscale, deinterlace=deinterlace, tff=tff)
     T = len(src) if frames is None else int(frames)
+    fps = src.fps or (25, 1)   # (a headerless input has no rate: 25:1, and A0:0 = unknown)
+    if deinterlace == "field":   # a frame per field: twice the rate
+        fps = (2 * fps[0], fps[1])
     if output is None:
         sink = lambda j, frame: None   # noqa: E731
     elif output.endswith(".y4m"):
-        sink = Y4MWriter(output, runner.out_shape, fmt_out, src.fps or (25, 1), src.siting, src.full_range, src.aspect)   # (a headerless input has no rate: 25:1, and A0:0 = unknown)
+        sink = Y4MWriter(output, runner.out_shape, fmt_out, fps, src.siting, src.full_range, src.aspect)
     else:
         sink = RawWriter(output, runner.out_bytes)
     t0 = time.perf_counter()
@@ -381,6 +406,8 @@ def run_file(path: str, output: Optional[str] = None, size: Optional[Tuple[int, 
                 siting=src.siting, full_range=bool(src.full_range), weights=weights, fps=list(src.fps) if src.fps else None,
                 h2d_bytes_per_frame=runner.in_bytes, d2h_bytes_per_frame=runner.out_bytes)
     _score_fields(line, runner, score, baseline, temporal, scene, multiscale, decimate)
+    if deinterlace is not None:
+        line.update(deinterlace=deinterlace, tff=bool(tff), frames_out=n)
     if scene is not None:
         line.update(scene=scene, scene_thresholds=list(runner.scene_thresholds), cuts=[int(i) for i in np.flatnonzero(runner.cuts)],
                     scene_m=[round(float(v), 4) for v in runner.scene_m])
@@ -500,6 +527,12 @@ def main(argv=None):
     ap.add_argument("--scene-thresholds", type=float, nargs=2, default=None, metavar=("T_ABS", "RATIO"),
                     help="with --scene: a pair is a cut where its mean difference reaches T_ABS (0..255 luma scale) and RATIO times the "
                          "previous pair's (default 15 2; not validated on real video)")
+    ap.add_argument("--deinterlace", default=None, choices=["frame", "field"],
+                    help="with --input: the file is interlaced; make it progressive on the device before anything else (frame: one frame "
+                         "per interlaced frame, its first field kept; field: one per field, twice the rate); not validated on real video")
+    ap.add_argument("--field-order", default=None, choices=["tff", "bff"],
+                    help="with --deinterlace: which field comes first in time (overrides the .y4m header's It / Ib; required for a "
+                         "headerless file)")
     ap.add_argument("--cut-at", type=int, default=None, metavar="K",
                     help="with --pix-fmt: the synthetic clip's frames from K on come from a second seed (a scene cut before frame K)")
     ap.add_argument("--train-steps", type=int, default=None, metavar="K",
@@ -525,8 +558,10 @@ def main(argv=None):
         for name in ("patch", "frames_per_sample", "group", "seed", "save"):
             if getattr(args, name) is not None:
                 ap.error(f"--{name.replace('_', '-')} needs --input and --train-steps (the streamed clip trainer)")
+    if args.field_order is not None and args.deinterlace is None:
+        ap.error("--field-order needs --deinterlace")
     if args.input is None:
-        for name in ("size", "output", "out_pix_fmt", "siting", "checkpoint", "scale_down"):
+        for name in ("size", "output", "out_pix_fmt", "siting", "checkpoint", "scale_down", "deinterlace"):
             if getattr(args, name) is not None:
                 ap.error(f"--{name.replace('_', '-')} needs --input")
     else:
@@ -540,7 +575,11 @@ def main(argv=None):
                 assert len(args.size) == 2
             except (ValueError, AssertionError):
                 ap.error("--size is HxW, two integers")
+        if args.deinterlace is not None and not args.input.endswith(".y4m") and args.field_order is None:
+            ap.error("--deinterlace on a headerless file needs --field-order tff|bff")
         if args.train_steps is not None:
+            if args.deinterlace is not None:
+                ap.error("--input with --train-steps takes no --deinterlace (the streamed clip trainer reads progressive frames)")
             for name in ("output", "out_pix_fmt", "scale_down", "score", "baseline", "temporal", "scene", "scene_thresholds"):
                 if getattr(args, name) is not None:
                     ap.error(f"--input with --train-steps trains on the file and writes no frames: it takes no --{name.replace('_', '-')}")
@@ -571,7 +610,8 @@ def main(argv=None):
         line = run_file(args.input, args.output, size=args.size, pix_fmt=args.pix_fmt, out_pix_fmt=args.out_pix_fmt, matrix=args.matrix,
                         siting=args.siting, checkpoint=args.checkpoint, scale_down=args.scale_down, frames=None, scale=args.scale,
                         precision=args.precision, score=args.score, decimate=args.decimate, baseline=args.baseline, temporal=args.temporal,
-                        scene=args.scene, scene_thresholds=args.scene_thresholds, multiscale=args.multiscale)
+                        scene=args.scene, scene_thresholds=args.scene_thresholds, multiscale=args.multiscale,
+                        deinterlace=args.deinterlace, field_order=args.field_order)
         print(json.dumps(line))
         return
     if args.score is not None and args.pix_fmt is None:

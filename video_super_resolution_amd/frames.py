@@ -21,6 +21,10 @@ libraries for frames, one section each.
 
     pix_ingest / pix_write / ingest_item_pix / frames_to_pix   the same two steps for every planar layout: the four 4:2:0 names through
                             the library above, yuv422p, yuv444p, yuv422p10le and yuv444p10le through include/vsr_hip_pix.h
+    deint_planes / deinterlace / deint_schedule / deinterlace_clip   interlaced frames made progressive on the packed bytes, before the
+                            conversion (include/vsr_hip_deint.h): the planes of every layout, one frame rebuilt from itself and its two
+                            neighbours in one launch, the neighbours and field parities of a whole clip, and the clip deinterlaced frame
+                            by frame (what `ClipRunner(deinterlace=...)` must equal)
     patch_table / patch_gather / patch_item   training samples (include/vsr_hip_patch.h): random crops, the eight symmetries of the
                             square and time reversal drawn on the host as a table, all samples of a step cut from the resident frames
                             in one launch with their LR patches, and a sample as the (data, target, high_frames) of the train loop
@@ -248,6 +252,107 @@ def ingest_item_pix(frames: torch.Tensor, shape: Tuple[int, int], fmt: str, scal
 def frames_to_pix(frames: torch.Tensor, fmt: str, matrix: str = "bt709", full_range: bool = False, siting: str = "left") -> torch.Tensor:
     """`frames_to_yuv` for any name of `PIX_FORMATS`."""
     return pix_write(frames, fmt, pix_coefficients(fmt, matrix, full_range), siting)
+
+
+# ------------------------------------------------------------------------------------------------ deinterlacing
+DEINTERLACE = (None, "frame", "field")   # "frame": one progressive frame per interlaced frame; "field": one per field (twice the rate)
+
+
+def deint_planes(fmt: str, H: int, W: int):
+    """The planes of one packed frame of any name of `PIX_FORMATS` as vsr_deint_frame takes them -> (planes, sample_bytes, shift):
+    `planes` a list of (offset in bytes, rows, cols, comps) that tiles the `pix_frame_bytes(fmt, H, W)` bytes with no gap, in the file's
+    order; nv12 / p010le carry Cb and Cr as ONE plane of comps = 2; `shift` is 6 for p010le (the value in the high 10 bits), else 0."""
+    fb = pix_frame_bytes(fmt, H, W)   # (raises on an unknown name and on a shape the layout cannot hold)
+    sb = 2 if _pix_depth(fmt) == 10 else 1
+    ss = pix_chroma(fmt)
+    ch, cw = (H // 2 if ss == "420" else H), (W if ss == "444" else W // 2)
+    luma = H * W * sb
+    if fmt in ("nv12", "p010le"):
+        planes = [(0, H, W, 1), (luma, ch, cw, 2)]
+    else:
+        planes = [(0, H, W, 1), (luma, ch, cw, 1), (luma + ch * cw * sb, ch, cw, 1)]
+    assert planes[-1][0] + planes[-1][1] * planes[-1][2] * planes[-1][3] * sb == fb
+    return planes, sb, (6 if fmt == "p010le" else 0)
+
+
+def _deint_mode(mode) -> str:
+    if mode not in DEINTERLACE or mode is None:
+        raise ValueError(f"deinterlace mode must be 'frame' or 'field', got {mode!r}")
+    return mode
+
+
+@L.on_device
+def deinterlace_planes(prev: torch.Tensor, cur: torch.Tensor, next: torch.Tensor, planes, sample_bytes: int, shift: int, keep: int,
+                       kept_first: int, out: torch.Tensor) -> torch.Tensor:
+    """The low-level call (vsr_deint_frame) with any planes: four dense uint8 tensors on the device (`prev`, `cur` and `next` may be one
+    another; `out` none of them), `planes` a list of (offset, rows, cols, comps) inside them.  The caller answers for the planes lying
+    inside all four tensors.  Nothing is synchronised."""
+    planes = [tuple(int(v) for v in p) for p in planes]
+    arr = (L.DeintPlane * max(len(planes), 1))(*[L.DeintPlane(*p) for p in planes])
+    D = L.load_deint()
+    L.check(D.vsr_deint_frame(L.dptr(prev, torch.uint8), L.dptr(cur, torch.uint8), L.dptr(next, torch.uint8), L.dptr(out, torch.uint8), arr,
+                              len(planes), int(sample_bytes), int(shift), int(keep), int(kept_first), L.stream()), "deint_frame", lib=D)
+    return out
+
+
+def deinterlace(prev: torch.Tensor, cur: torch.Tensor, next: torch.Tensor, shape: Tuple[int, int], fmt: str, keep: int, kept_first: int,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One interlaced frame `cur` of `fmt` (any name of `PIX_FORMATS`) and `shape` = (H, W) made progressive by the rule of
+    include/vsr_hip_deint.h: uint8 device tensors of `pix_frame_bytes` bytes each -> a uint8 tensor of as many (`out`: write there).
+    The rows of parity `keep` are copies of `cur`'s, the others rebuilt from `cur` and the neighbouring frames `prev` and `next`
+    (at a clip end pass the other neighbour, `deint_schedule`); `kept_first`: the kept field is the first of `cur`'s two in time.  One
+    launch, nothing is synchronised."""
+    H, W = int(shape[0]), int(shape[1])
+    planes, sb, shift = deint_planes(fmt, H, W)
+    fb = pix_frame_bytes(fmt, H, W)
+    for name, t in (("prev", prev), ("cur", cur), ("next", next)) + ((("out", out),) if out is not None else ()):
+        if t.dtype != torch.uint8 or t.numel() != fb or t.device != cur.device:
+            raise ValueError(f"{name} must be uint8 of {fb} bytes ({fmt} {H}x{W}) on {cur.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    if min(p[1] for p in planes) < 2:
+        raise ValueError(f"{fmt} {H}x{W}: a plane of {min(p[1] for p in planes)} row(s) holds no two fields")
+    if out is None:
+        out = torch.empty(fb, dtype=torch.uint8, device=cur.device)
+    return deinterlace_planes(prev, cur, next, planes, sb, shift, keep, kept_first, out)
+
+
+def deint_schedule(T: int, mode: str, tff: bool = True) -> list:
+    """The progressive frames of a clip of `T` interlaced frames, in time order, as (prev, cur, next, keep, kept_first): the indices of
+    the three frames `deinterlace` takes and its two flags.  Pure host code.  The neighbours of frame i are i - 1 and i + 1; at a clip
+    end the missing neighbour is the OTHER neighbour (reflection: the frame itself there would blind td0 and td1 of the rule), and for
+    T = 1 both are the frame itself.  "frame": per interlaced frame one entry that keeps its first field in time (keep = 0 if `tff` else
+    1, kept_first = 1); "field": that entry, then the second field's (keep flipped, kept_first = 0): 2 T entries."""
+    _deint_mode(mode)
+    T = int(T)
+    if T <= 0:
+        raise ValueError(f"a clip has at least one frame, got {T}")
+    first = 0 if tff else 1
+    out = []
+    for i in range(T):
+        p, n = i - 1, i + 1
+        if p < 0:
+            p = n if n < T else i
+        if n >= T:
+            n = p
+        out.append((p, i, n, first, 1))
+        if mode == "field":
+            out.append((p, i, n, 1 - first, 0))
+    return out
+
+
+def deinterlace_clip(frames_u8, shape: Tuple[int, int], fmt: str, mode: str, tff: bool = True, device="cuda") -> np.ndarray:
+    """A whole clip deinterlaced on the device, frame by frame: uint8 [T, frame_bytes] (a host array or a tensor) -> a host array
+    [T, frame_bytes] ("frame") or [2 T, frame_bytes] ("field"), the entries of `deint_schedule` in order.  The definition of what
+    `ClipRunner(deinterlace=mode, tff=tff)` feeds its windows; a clip's length of device memory, so a tool for tests and short clips."""
+    t = frames_u8 if isinstance(frames_u8, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(frames_u8)))
+    fb = pix_frame_bytes(fmt, int(shape[0]), int(shape[1]))
+    if t.dtype != torch.uint8 or t.dim() != 2 or t.shape[1] != fb or t.shape[0] < 1:
+        raise ValueError(f"expected uint8 [T >= 1, {fb}] ({fmt} {shape[0]}x{shape[1]}), got {t.dtype} {tuple(t.shape)}")
+    sched = deint_schedule(int(t.shape[0]), mode, tff)
+    src = t.to(device).contiguous()
+    out = torch.empty((len(sched), fb), dtype=torch.uint8, device=src.device)
+    for q, (p, i, n, keep, kept_first) in enumerate(sched):
+        deinterlace(src[p], src[i], src[n], shape, fmt, keep, kept_first, out=out[q])
+    return out.cpu().numpy()
 
 
 # ------------------------------------------------------------------------------------------------ resampling

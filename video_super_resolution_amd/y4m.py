@@ -13,8 +13,10 @@ C<colour space> X<anything>.  Every frame is `FRAME\\n` plus the frame's bytes, 
     C422        yuv422p      "left"                                         C422p10   yuv422p10le   "left"
     C444        yuv444p      (no siting: "left" is reported)                C444p10   yuv444p10le
 
-`XCOLORRANGE=FULL | LIMITED` (ffmpeg's extension) gives the range, limited when absent; other X tokens are kept and ignored.  Out of
-scope, and refused by name: interlaced clips (It, Ib, Im), Cmono, C411, C444alpha, depths other than 8 and 10, FRAME lines with
+`XCOLORRANGE=FULL | LIMITED` (ffmpeg's extension) gives the range, limited when absent; other X tokens are kept and ignored.
+Interlaced clips (It: top field first, Ib: bottom field first) are refused by name unless the caller passes `interlaced=True`, which
+says it will deinterlace them (`ClipRunner(deinterlace=...)`); the field order is then reported as `tff`.  The frames are read as they
+lie in the file either way, and the writer always writes Ip.  Out of scope, and refused by name: mixed interlacing (Im), Cmono, C411, C444alpha, depths other than 8 and 10, FRAME lines with
 parameters, pipes (the frame count comes from the file's size).
 """
 from __future__ import annotations
@@ -47,9 +49,10 @@ def _ratio(token: str, what: str) -> Tuple[int, int]:
     return a, b
 
 
-def parse_header(line: bytes, siting: Optional[str] = None) -> dict:
-    """The header line (without its newline) -> {shape (H, W), fmt, siting, full_range, fps, aspect, extra}.  `siting`: use this one
-    whatever the colour tag says (the only way to read a C420paldv file)."""
+def parse_header(line: bytes, siting: Optional[str] = None, interlaced: bool = False) -> dict:
+    """The header line (without its newline) -> {shape (H, W), fmt, siting, full_range, fps, aspect, extra, tff}.  `siting`: use this one
+    whatever the colour tag says (the only way to read a C420paldv file).  `interlaced`: accept It / Ib; `tff` is then True / False, and
+    None for Ip or no I token (Im, mixed, stays refused)."""
     try:
         tokens = line.decode("ascii").split(" ")
     except UnicodeDecodeError:
@@ -61,7 +64,7 @@ def parse_header(line: bytes, siting: Optional[str] = None) -> dict:
     W = H = None
     fps = None
     aspect = (0, 0)
-    tag, full_range, extra = "420", False, []
+    tag, full_range, extra, tff = "420", False, [], None
     for t in tokens[1:]:
         if not t:
             continue
@@ -78,7 +81,11 @@ def parse_header(line: bytes, siting: Optional[str] = None) -> dict:
         elif k == "A":
             aspect = _ratio(t, "aspect")
         elif k == "I":
-            if v != "p":
+            if interlaced and v in ("t", "b"):
+                tff = v == "t"
+            elif interlaced and v == "m":
+                raise ValueError(f"Y4M header: {t!r}: mixed interlacing is out of scope (Ip, It, Ib, or no I token)")
+            elif v != "p":
                 raise ValueError(f"Y4M header: {t!r}: interlaced clips are out of scope (only Ip, or no I token)")
         elif k == "C":
             tag = v
@@ -105,16 +112,16 @@ def parse_header(line: bytes, siting: Optional[str] = None) -> dict:
                              f"siting='left' or 'center' to read it with that one")
         siting = tag_siting
     pix_frame_bytes(fmt, H, W)   # (raises on a shape the layout cannot hold: an odd size)
-    return dict(shape=(H, W), fmt=fmt, siting=siting, full_range=full_range, fps=fps, aspect=aspect, extra=extra)
+    return dict(shape=(H, W), fmt=fmt, siting=siting, full_range=full_range, fps=fps, aspect=aspect, extra=extra, tff=tff)
 
 
 class Y4MReader:
     """A `.y4m` file frame by frame.  Attributes: `shape` (H, W), `fmt` (a planar name of `frames.PIX_FORMATS`), `siting`, `full_range`,
-    `fps` (num, den) or None, `aspect` (num, den), `extra` (the X tokens, verbatim), `frame_bytes`; `len(reader)` is the frame count, from
+    `fps` (num, den) or None, `aspect` (num, den), `extra` (the X tokens, verbatim), `tff` (with `interlaced=True`: True for It, False for Ib, None for progressive), `frame_bytes`; `len(reader)` is the frame count, from
     the file's size.  `read_into(buf)`: the next frame into a uint8 array of `frame_bytes` elements, False at the end; `read()`: a new
     array or None; iterating yields arrays; `rewind()` starts over."""
 
-    def __init__(self, path: str, siting: Optional[str] = None):
+    def __init__(self, path: str, siting: Optional[str] = None, interlaced: bool = False):
         self.path = path
         self._f = open(path, "rb")
         try:
@@ -122,9 +129,9 @@ class Y4MReader:
             nl = head.find(b"\n")
             if not head.startswith(MAGIC) or nl < 0:
                 raise ValueError(f"{path}: not a YUV4MPEG2 file (no header line in the first {_MAX_HEADER} bytes)")
-            info = parse_header(head[:nl], siting)
+            info = parse_header(head[:nl], siting, interlaced)
             self.shape, self.fmt, self.siting, self.full_range = info["shape"], info["fmt"], info["siting"], info["full_range"]
-            self.fps, self.aspect, self.extra = info["fps"], info["aspect"], info["extra"]
+            self.fps, self.aspect, self.extra, self.tff = info["fps"], info["aspect"], info["extra"], info["tff"]
             self.frame_bytes = pix_frame_bytes(self.fmt, *self.shape)
             self._start = nl + 1
             self._check_marker(head[self._start:self._start + len(FRAME) + 1], 0)
@@ -259,7 +266,7 @@ class RawReader:
 
     def __init__(self, path: str, shape: Tuple[int, int], fmt: str, siting: str = "left", full_range: bool = False):
         self.path, self.shape, self.fmt, self.siting, self.full_range = path, (int(shape[0]), int(shape[1])), fmt, siting, full_range
-        self.fps, self.aspect, self.extra = None, (0, 0), []
+        self.fps, self.aspect, self.extra, self.tff = None, (0, 0), [], None
         self.frame_bytes = pix_frame_bytes(fmt, *self.shape)
         size = os.path.getsize(path)
         if size == 0 or size % self.frame_bytes:
