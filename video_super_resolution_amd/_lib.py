@@ -11,8 +11,8 @@ consecutive HR frames), of libvsr_hip_scene.so (include/vsr_hip_scene.h: scene c
 device), of libvsr_hip_hgi.so (include/vsr_hip_hgi.h: an inception block of the hourglass's inner levels in one launch), of
 libvsr_hip_msssim.so (include/vsr_hip_msssim.h: the float64 sums behind multi-scale SSIM of HR frames), of libvsr_hip_pix.so
 (include/vsr_hip_pix.h: planar Y'CbCr 4:2:2 and 4:4:4 frames in and out), of libvsr_hip_patch.so (include/vsr_hip_patch.h: training
-samples cut and augmented from frames on the device) and of libvsr_hip_deint.so (include/vsr_hip_deint.h: motion-adaptive deinterlacing
-of packed frames).
+samples cut and augmented from frames on the device), of libvsr_hip_deint.so (include/vsr_hip_deint.h: motion-adaptive deinterlacing
+of packed frames) and of libvsr_hip_cell.so (include/vsr_hip_cell.h: a resident group of frames measured per cell and frame).
 
 There is deliberately no CPU or eager-PyTorch fallback behind these entry points: if the
 shared library is missing, or an operator is handed a non-CUDA tensor, the call raises.
@@ -56,20 +56,22 @@ def _side(name: str, prefix: str, abi: int, has_query: bool) -> tuple:
 # pix: planar Y'CbCr 4:2:2 and 4:4:4 frames to the model's float32 RGB and back (csrc/clip_pix.hip); patch: runs of HR frames cropped,
 # flipped, transposed and reversed in time into training samples, with their LR patches, in one launch (csrc/train_patch.hip); deint: the
 # rows of one field of a packed interlaced frame kept, the rows of the other rebuilt from the fields either side in time, all planes in one
-# launch (csrc/clip_deint.hip)
+# launch (csrc/clip_deint.hip); cell: the spatial activity of every 16 x 16 cell of every frame of a resident group and its absolute luma
+# difference against the frame before, in one launch that reads each frame once (csrc/clip_cell_stats.hip)
 _SIDE = {"grad": _side("grad", "vsr_grad", 1, False), "s3": _side("s3", "vsr_s3", 1, True), "s3t": _side("s3t", "vsr_s3t", 1, True),
          "s3p": _side("s3p", "vsr_s3p", 1, True), "s3f": _side("s3f", "vsr_s3f", 1, True), "yuv": _side("yuv", "vsr_yuv", 1, False),
          "metric": _side("metric", "vsr_metric", 1, False), "opt": _side("opt", "vsr_opt", 1, False), "loss": _side("loss", "vsr_loss", 1, False),
          "resize": _side("resize", "vsr_resize", 1, False), "warp": _side("warp", "vsr_warp", 1, False),
          "scene": _side("scene", "vsr_scene", 1, False), "hgi": _side("hgi", "vsr_hgi", 1, False),
          "msssim": _side("msssim", "vsr_msssim", 1, False), "pix": _side("pix", "vsr_pix", 1, False),
-         "patch": _side("patch", "vsr_patch", 1, False), "deint": _side("deint", "vsr_deint", 1, False)}
+         "patch": _side("patch", "vsr_patch", 1, False), "deint": _side("deint", "vsr_deint", 1, False),
+         "cell": _side("cell", "vsr_cell", 1, False)}
 (GLIB_PATH, GHEADER_PATH), (S3LIB_PATH, S3HEADER_PATH), (S3TLIB_PATH, S3THEADER_PATH), (S3PLIB_PATH, S3PHEADER_PATH), \
     (S3FLIB_PATH, S3FHEADER_PATH), (YUVLIB_PATH, YUVHEADER_PATH), (METRICLIB_PATH, METRICHEADER_PATH), (OPTLIB_PATH, OPTHEADER_PATH), \
     (LOSSLIB_PATH, LOSSHEADER_PATH), (RESIZELIB_PATH, RESIZEHEADER_PATH), (WARPLIB_PATH, WARPHEADER_PATH), (SCENELIB_PATH, SCENEHEADER_PATH), \
     (HGILIB_PATH, HGIHEADER_PATH), (MSSSIMLIB_PATH, MSSSIMHEADER_PATH), (PIXLIB_PATH, PIXHEADER_PATH), (PATCHLIB_PATH, PATCHHEADER_PATH), \
-    (DEINTLIB_PATH, DEINTHEADER_PATH) = (row[:2] for row in _SIDE.values())
-_gradlib = _s3lib = _s3tlib = _s3plib = _s3flib = _yuvlib = _metriclib = _optlib = _losslib = _resizelib = _warplib = _scenelib = _hgilib = _msssimlib = _pixlib = _patchlib = _deintlib = None   # `_<name>lib`: the loaded side library (None: this process has not asked for it)
+    (DEINTLIB_PATH, DEINTHEADER_PATH), (CELLLIB_PATH, CELLHEADER_PATH) = (row[:2] for row in _SIDE.values())
+_gradlib = _s3lib = _s3tlib = _s3plib = _s3flib = _yuvlib = _metriclib = _optlib = _losslib = _resizelib = _warplib = _scenelib = _hgilib = _msssimlib = _pixlib = _patchlib = _deintlib = _celllib = None   # `_<name>lib`: the loaded side library (None: this process has not asked for it)
 # the cross-check library instead of the shipping one for every call (set by `xcheck()`; the environment switch serves the
 # measurement tools, whose VSR_TUNING codes only that library understands)
 _use_x = os.environ.get("VSR_USE_XCHECK", "0") == "1" or bool(os.environ.get("VSR_TUNING", "").strip())
@@ -83,7 +85,7 @@ def build(verbose: bool = False) -> str:
     """Compile every HIP source for gfx950 into the in-tree libvsr_hip.so, libvsr_hip_xcheck.so, libvsr_hip_grad.so,
     libvsr_hip_s3.so, libvsr_hip_s3t.so, libvsr_hip_s3p.so, libvsr_hip_s3f.so, libvsr_hip_yuv.so, libvsr_hip_metric.so,
     libvsr_hip_opt.so, libvsr_hip_loss.so, libvsr_hip_resize.so, libvsr_hip_warp.so, libvsr_hip_scene.so, libvsr_hip_hgi.so,
-    libvsr_hip_msssim.so, libvsr_hip_pix.so, libvsr_hip_patch.so and libvsr_hip_deint.so (hipcc cross-compiles without a GPU)."""
+    libvsr_hip_msssim.so, libvsr_hip_pix.so, libvsr_hip_patch.so, libvsr_hip_deint.so and libvsr_hip_cell.so (hipcc cross-compiles without a GPU)."""
     cmd = ["make", "-j4", "-C", os.path.join(_PKG, "csrc")]
     if not verbose:
         cmd.insert(1, "-s")
@@ -94,15 +96,15 @@ def build(verbose: bool = False) -> str:
 def declared_symbols(xcheck: bool = False, grad: bool = False, s3: bool = False, s3t: bool = False, s3p: bool = False, s3f: bool = False,
                      yuv: bool = False, metric: bool = False, opt: bool = False, loss: bool = False, resize: bool = False,
                      warp: bool = False, scene: bool = False, hgi: bool = False, msssim: bool = False, pix: bool = False,
-                     patch: bool = False, deint: bool = False) -> list:
+                     patch: bool = False, deint: bool = False, cell: bool = False) -> list:
     """Entry points include/vsr_hip.h declares (xcheck: the ones include/vsr_hip_xcheck.h adds; grad / s3 / s3t / s3p / s3f / yuv / metric /
-    opt / loss / resize / warp / scene / hgi / msssim / pix / patch / deint: the ones of include/vsr_hip_grad.h / include/vsr_hip_s3.h / include/vsr_hip_s3t.h / include/vsr_hip_s3p.h / include/vsr_hip_s3f.h /
+    opt / loss / resize / warp / scene / hgi / msssim / pix / patch / deint / cell: the ones of include/vsr_hip_grad.h / include/vsr_hip_s3.h / include/vsr_hip_s3t.h / include/vsr_hip_s3p.h / include/vsr_hip_s3f.h /
     include/vsr_hip_yuv.h / include/vsr_hip_metric.h / include/vsr_hip_opt.h / include/vsr_hip_loss.h / include/vsr_hip_resize.h /
     include/vsr_hip_warp.h / include/vsr_hip_scene.h / include/vsr_hip_hgi.h / include/vsr_hip_msssim.h / include/vsr_hip_pix.h / include/vsr_hip_patch.h /
-    include/vsr_hip_deint.h, libraries of their own)."""
+    include/vsr_hip_deint.h / include/vsr_hip_cell.h, libraries of their own)."""
     side = [name for name, on in (("grad", grad), ("s3", s3), ("s3t", s3t), ("s3p", s3p), ("s3f", s3f), ("yuv", yuv), ("metric", metric),
                                   ("opt", opt), ("loss", loss), ("resize", resize), ("warp", warp), ("scene", scene), ("hgi", hgi),
-                                  ("msssim", msssim), ("pix", pix), ("patch", patch), ("deint", deint)) if on]
+                                  ("msssim", msssim), ("pix", pix), ("patch", patch), ("deint", deint), ("cell", cell)) if on]
     with open(_SIDE[side[-1]][1] if side else XHEADER_PATH if xcheck else HEADER_PATH) as f:
         text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
     return sorted(set(re.findall(r"\b(vsr_[a-z0-9_]+)\s*\(", text)))
@@ -288,6 +290,13 @@ def load_deint() -> ctypes.CDLL:
     """libvsr_hip_deint.so (include/vsr_hip_deint.h)."""
     lib = _load_side("deint")
     lib.vsr_deint_frame.argtypes = [ctypes.c_void_p] * 4 + [ctypes.POINTER(DeintPlane)] + [ctypes.c_int] * 5 + [ctypes.c_void_p]
+    return lib
+
+
+def load_cell() -> ctypes.CDLL:
+    """libvsr_hip_cell.so (include/vsr_hip_cell.h)."""
+    lib = _load_side("cell")
+    lib.vsr_cell_stats.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 3
     return lib
 
 

@@ -11,7 +11,8 @@ import numpy as np
 import torch
 
 from .clip_runner import ArraySource
-from .frames import FrameResizer, patch_gather, patch_item, patch_table, pix_coefficients, pix_frame_bytes, pix_ingest
+from .frames import (FrameResizer, _scene_thresholds, cell_cuts, cell_stats, patch_gather, patch_item, patch_table, patch_table_select,
+                     pix_coefficients, pix_frame_bytes, pix_ingest)
 
 
 class ClipTrainer:
@@ -39,13 +40,34 @@ class ClipTrainer:
     After a run: `steps`, `losses` (float64 [steps]), `grad_norms` (float64 [steps] when the optimizer clips, else None), `tables` (every
     table drawn, in order), `frames_in`, `frames_skipped`, `h2d_bytes`.
 
-    Known limit: scene cuts are not looked for; a sample may straddle one."""
+    Where the samples are cut (both off by default: then no launch, copy or wait is added, `patch_table` is called as before and tables,
+    losses and weights are bit for bit what they were):
+        avoid_cuts=True   no sample spans a scene cut.  `cut_thresholds`: (t_abs, ratio), default `frames.SCENE_THRESHOLDS`, applied here
+                          to FULL-SIZE frames where `ClipRunner` applies it to LR frames; the measure is a mean per pixel, so the scale is
+                          the same.  The rule and its defaults are NOT validated on real video.  A group's first pair has no pair before
+                          it (`frames.cell_cuts`), and the pair between two groups is not scored: samples never span groups.
+        act_min=X         patches with detail are preferred: up to `tries` candidates are drawn per sample, the first whose
+                          `frames.patch_score` (mean |dx| + |dy| of the 8-bit luma code per pixel) reaches X is taken, else the most
+                          active one.  There is no default: any value is the caller's choice and unvalidated (`driver.synthetic_video`
+                          has 3.4 to 10.7 per cell; a constant region has 0).
+    With either, per full group: one `frames.cell_stats` over the resident frames (one launch, every frame read once), one device-to-host
+    copy of the small map and its wait (2 MB for eight 2160 x 3840 frames, against seconds of training), then `frames.cell_cuts` and
+    `frames.patch_table_select` on the host.  A group in which no run of n frames is free of cuts trains nothing; its samples are counted
+    in `samples_skipped`.  `cut_thresholds` without `avoid_cuts`, a `tries` other than the default without `act_min` and `tries` < 1
+    are refused.  After a run also: `cuts` (the source-frame indices i whose pair (i, i + 1) was flagged), `cut_m` (float64, the mean
+    absolute luma difference of those pairs), `scores` (float64 [steps], NaN without `act_min`), `tried` (int32 [steps]) and
+    `samples_skipped`.
+
+    Known limit: a cut is looked for between frames of one group only, and only by the mean absolute luma difference: a dissolve or a
+    fade is not a cut to this rule, and a sample may run through one."""
 
     DECIMATE = ("nearest", "bicubic")
+    TRIES = 8
 
     def __init__(self, model, optimizer, shape: Tuple[int, int], fmt_in: str, patch: int = 64, frames_per_sample: int = 3, group: int = 8,
                  samples_per_group: int = 4, seed: int = 0, augment: bool = True, decimate: str = "nearest", matrix: str = "bt709",
-                 full_range: bool = False, siting: str = "left", loss_path: Optional[str] = None):
+                 full_range: bool = False, siting: str = "left", loss_path: Optional[str] = None, avoid_cuts: bool = False, cut_thresholds=None,
+                 act_min: Optional[float] = None, tries: int = 8):
         H, W = int(shape[0]), int(shape[1])
         S = int(model.model.upscale_factor)
         self.model, self.optimizer, self.shape, self.fmt_in, self.siting, self.S = model, optimizer, (H, W), fmt_in, siting, S
@@ -64,6 +86,16 @@ class ClipTrainer:
             raise ValueError(f"samples_per_group must be positive, got {self.samples_per_group}")
         if decimate == "bicubic" and (H % S or W % S):
             raise ValueError(f"decimate='bicubic' needs frames that are a multiple of S = {S}, got {H} x {W}")
+        if cut_thresholds is not None and not avoid_cuts:
+            raise ValueError("cut_thresholds is given but cuts are not avoided (avoid_cuts=False)")
+        if int(tries) < 1:
+            raise ValueError(f"tries must be at least 1, got {tries}")
+        if int(tries) != self.TRIES and act_min is None:
+            raise ValueError(f"tries = {tries} is given but no activity bar is set (act_min=None)")
+        if act_min is not None and (not np.isfinite(act_min) or self.hr_patch < 31):
+            raise ValueError(f"act_min must be finite, and the HR patch of {self.hr_patch} at least 31 (one whole cell inside any crop)")
+        self.avoid_cuts, self.cut_thresholds = bool(avoid_cuts), (_scene_thresholds(cut_thresholds) if avoid_cuts else None)
+        self.act_min, self.tries = (None if act_min is None else float(act_min)), int(tries)
         if loss_path is not None:
             model.loss_path = loss_path
         self.decimate, self.augment, self.seed = decimate, bool(augment), int(seed)
@@ -85,6 +117,8 @@ class ClipTrainer:
         self.steps = self.frames_in = self.frames_skipped = self.h2d_bytes = 0
         self.losses = self.grad_norms = None
         self.tables = []
+        self.samples_skipped = 0
+        self.cuts, self.cut_m, self.scores, self.tried = [], [], [], []
 
     def run(self, frames: np.ndarray, max_steps: Optional[int] = None) -> int:
         frames = np.asarray(frames)
@@ -118,6 +152,8 @@ class ClipTrainer:
             host = torch.stack(dev).cpu().numpy() if dev else np.zeros(0)
             self.losses = host[:len(losses)]
             self.grad_norms = np.sqrt(host[len(losses):]) if norms_sq else None
+        self.cut_m, self.scores = np.asarray(self.cut_m, dtype=np.float64), np.asarray(self.scores, dtype=np.float64)
+        self.tried = np.asarray(self.tried, dtype=np.int32)
         return self.steps
 
     def _upload(self, i: int, g: int, source, uploaded, T: int) -> None:
@@ -139,8 +175,15 @@ class ClipTrainer:
     def _train_group(self, G: int, losses, norms_sq, max_steps) -> None:
         """The samples of a group of `G` resident frames: one table, one gather, a `train_item` per sample."""
         from .driver import train_item
-        table = patch_table(self.rng, self.samples_per_group, G, self.n, self.shape, self.hr_patch, self.S, self.augment)
+        scores = tried = None
+        if self.avoid_cuts or self.act_min is not None:
+            table, scores, tried = self._select(G)
+        else:
+            table = patch_table(self.rng, self.samples_per_group, G, self.n, self.shape, self.hr_patch, self.S, self.augment)
         self.tables.append(table)
+        if table.shape[0] == 0:
+            self.samples_skipped += self.samples_per_group
+            return
         if self.gather_events is not None:
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             ev[0].record()
@@ -158,3 +201,18 @@ class ClipTrainer:
             if norm_sq is not None:
                 norms_sq.append(norm_sq.clone())
             self.steps += 1
+            if scores is not None:
+                self.scores.append(scores[b])
+                self.tried.append(tried[b])
+
+    def _select(self, G: int):
+        """The table of a group of `G` resident frames under `avoid_cuts` / `act_min`: the map, its one copy to the host, the two host steps."""
+        stats = cell_stats(self._frames[:G]).cpu().numpy()   # the one copy and its wait
+        cuts = None
+        if self.avoid_cuts:
+            cuts, m = cell_cuts(stats, self.shape, self.cut_thresholds)
+            first = self.frames_in - G   # the source index of the group's first frame
+            self.cuts.extend(first + int(p) for p in np.flatnonzero(cuts))
+            self.cut_m.extend(float(v) for v in m[cuts])
+        return patch_table_select(self.rng, self.samples_per_group, G, self.n, self.shape, self.hr_patch, self.S, self.augment, cuts=cuts,
+                                  stats=stats if self.act_min is not None else None, act_min=self.act_min, tries=self.tries)

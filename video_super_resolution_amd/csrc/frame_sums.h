@@ -1,8 +1,8 @@
 // frame_sums.h -- the device helpers the float64-sum kernels share: quantisation as write-out does it, the luma of "y" mode, the
 // fixed-order tree, and the two halves of "one pair of doubles per workgroup, then a finish kernel adds the partials".
 //
-// For frame_metric.hip, frame_msssim.hip (both also through frame_ssim.h), frame_warp_error.hip, frame_resize.hip, train_update.hip and
-// clip_scene.hip ONLY: the sources compiled with -ffp-contract=off (Makefile) that state the pragma themselves, whose results the tests
+// For frame_metric.hip, frame_msssim.hip (both also through frame_ssim.h), frame_warp_error.hip, frame_resize.hip, train_update.hip,
+// clip_scene.hip and clip_cell_stats.hip ONLY: the sources compiled with -ffp-contract=off (Makefile) that state the pragma themselves, whose results the tests
 // pin bit for bit.  Every operation below rounds once, in the order written, as it did when each of those sources held its own copy; no
 // source built with contraction includes this header.
 #pragma once

@@ -17,7 +17,9 @@ feeds it, on the GPU path and without OpenCV:
                             SRmodel.model.state_dict(),'optimizer'} -- files interchange with the reference's
     run_file_train          `--input clip.y4m --train-steps K`: `ClipTrainer` over a streamed file (patches cut and augmented on the
                             device: `patch_table` / `patch_gather` / `patch_item` of `frames`), `--save DIR` writes a checkpoint of
-                            tensors and plain containers that `--input ... --checkpoint` takes back
+                            tensors and plain containers that `--input ... --checkpoint` takes back; `--avoid-cuts` / `--act-min X`
+                            keep the samples off scene cuts and prefer patches with detail (`cell_stats` / `cell_cuts` /
+                            `patch_table_select` of `frames`)
 
 The device bindings for frames in, out, resampled and scored (4:2:0 I/O, the resampler, PSNR / SSIM, MS-SSIM, the warping error) live in
 `frames`, the streamed `ClipRunner` on top of them in `clip_runner`, `ClipTrainer` in `clip_trainer`; their public names are imported here,
@@ -45,8 +47,9 @@ from . import _lib as L
 from .clip_runner import ArraySource, ClipRunner, sums_layout  # noqa: F401
 from .clip_trainer import ClipTrainer  # noqa: F401
 from .frames import (DEINTERLACE, METRIC_CHANNELS, METRIC_WHAT, MSSSIM_BETA, MSSSIM_MIN_SIZE, PIX_FORMATS, RESIZE_KERNELS, RESIZE_MAX_TAPS,  # noqa: F401
-                     PATCH_FLAGS, SCENE_THRESHOLDS, WARP_OCC, YUV_FORMATS, YUV_SITINGS, FrameResizer, ewarp, frame_metrics, frame_msssim, frames_to_pix,
+                     CELL, PATCH_FLAGS, SCENE_THRESHOLDS, WARP_OCC, YUV_FORMATS, YUV_SITINGS, FrameResizer, ewarp, frame_metrics, frame_msssim, frames_to_pix,
                      frames_to_yuv, ingest_item_pix, ingest_item_yuv, msssim, msssim_levels, patch_gather, patch_item, patch_table,
+                     cell_cuts, cell_shape, cell_stats, patch_score, patch_table_select,
                      deint_planes, deint_schedule, deinterlace, deinterlace_clip, deinterlace_planes,
                      pix_coefficients, pix_frame_bytes, pix_ingest, pix_write, psnr_ssim, read_clip_yuv, resize_frames, resize_tables, scene_cuts, scene_flags, scene_sums, scene_window, ssim_window, truth_flows, warp_error,
                      yuv_coefficients, yuv_frame_bytes, yuv_ingest, yuv_write)
@@ -441,12 +444,16 @@ def run_file_train(path: str, steps: int, size: Optional[Tuple[int, int]] = None
                    siting: Optional[str] = None, checkpoint: Optional[str] = None, scale: int = 4, precision: str = "fp32", patch: int = 64,
                    frames_per_sample: int = 3, group: int = 8, seed: int = 0, decimate: str = "nearest",
                    max_grad_norm: Optional[float] = None, learning_rate: float = 1e-3, loss_path: str = "reference",
-                   save: Optional[str] = None, model=None):
+                   save: Optional[str] = None, model=None, avoid_cuts: bool = False, cut_thresholds=None, act_min: Optional[float] = None,
+                   tries: Optional[int] = None):
     """`steps` train steps on patches of a clip file through `ClipTrainer.run_stream`: `path`, `size`, `pix_fmt`, `siting`, `model` as
     `run_file`'s; `checkpoint`: resume (loaded into the model before the first step).  The file is read once, or until `steps` are done.
     `save`: a directory; the trained SR net goes to `<save>/VSR_train-checkpoint.pth.tar` as `checkpoint_state` with the optimizer's
     `state_dict()` under "optimizer_state" and None under "optimizer": tensors and plain containers only, so `load_checkpoint` takes it
-    untrusted (the reference pickles the optimizer OBJECT; files written here do not).  -> (result line, model)."""
+    untrusted (the reference pickles the optimizer OBJECT; files written here do not).  `avoid_cuts`, `cut_thresholds`, `act_min`, `tries`:
+    `ClipTrainer`'s; when one of them is given the line gains `avoid_cuts`, `cut_thresholds`, `act_min`, `tries`, `cuts` (the source-frame
+    indices i whose pair (i, i + 1) was flagged), `samples_skipped` and `act_mean` (the mean `patch_score` of the steps' samples; None
+    without `act_min`), and without them it has exactly the keys it had.  -> (result line, model)."""
     from . import VSR, optim
     from .weights import fill_module_
     dev = torch.device("cuda", 0)
@@ -469,7 +476,8 @@ def run_file_train(path: str, steps: int, size: Optional[Tuple[int, int]] = None
     optimizer = optim.Adam(model.parameters(), lr=learning_rate, max_grad_norm=max_grad_norm)
     try:
         trainer = ClipTrainer(model, optimizer, src.shape, src.fmt, patch=patch, frames_per_sample=frames_per_sample, group=group,
-                              seed=seed, decimate=decimate, matrix=matrix, full_range=src.full_range, siting=src.siting, loss_path=loss_path)
+                              seed=seed, decimate=decimate, matrix=matrix, full_range=src.full_range, siting=src.siting, loss_path=loss_path,
+                              avoid_cuts=avoid_cuts, cut_thresholds=cut_thresholds, act_min=act_min, **({} if tries is None else {"tries": tries}))
         trainer.run_stream(src, max_steps=steps)
     finally:
         src.close()
@@ -486,6 +494,11 @@ def run_file_train(path: str, steps: int, size: Optional[Tuple[int, int]] = None
                 learning_rate=learning_rate, max_grad_norm=max_grad_norm, frames_skipped=trainer.frames_skipped,
                 loss=[round(float(v), 6) for v in trainer.losses],
                 grad_norm=[round(float(v), 6) for v in trainer.grad_norms] if trainer.grad_norms is not None else None, checkpoint=written)
+    if avoid_cuts or cut_thresholds is not None or act_min is not None or tries is not None:
+        line.update(avoid_cuts=trainer.avoid_cuts, cut_thresholds=list(trainer.cut_thresholds) if trainer.avoid_cuts else None,
+                    act_min=trainer.act_min, tries=trainer.tries, cuts=[int(i) for i in trainer.cuts],
+                    samples_skipped=trainer.samples_skipped,
+                    act_mean=round(float(np.mean(trainer.scores)), 6) if trainer.act_min is not None and len(trainer.scores) else None)
     return line, model
 
 
@@ -547,6 +560,16 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=None, help="with --input and --train-steps: the seed of the patch draws (default 0)")
     ap.add_argument("--save", default=None, metavar="DIR",
                     help="with --input and --train-steps: write DIR/VSR_train-checkpoint.pth.tar (tensors and plain containers only)")
+    ap.add_argument("--avoid-cuts", action="store_true", default=None,
+                    help="with --input and --train-steps: find scene cuts in every resident group on the device and draw no sample across "
+                         "one; the line carries the cuts found")
+    ap.add_argument("--cut-thresholds", type=float, nargs=2, default=None, metavar=("T_ABS", "RATIO"),
+                    help="with --avoid-cuts: as --scene-thresholds, on the full-size frames (default 15 2; not validated on real video)")
+    ap.add_argument("--act-min", type=float, default=None, metavar="X",
+                    help="with --input and --train-steps: prefer patches whose mean |dx| + |dy| of the luma code per pixel reaches X (no "
+                         "default: any value is the caller's choice and unvalidated)")
+    ap.add_argument("--tries", type=int, default=None, metavar="N",
+                    help="with --act-min: candidates drawn per sample before the most active one is taken (default 8)")
     ap.add_argument("--max-grad-norm", type=float, default=None, metavar="X",
                     help="with --train-steps: clip the global gradient norm at X on the device; the line carries the norm per step")
     ap.add_argument("--loss-path", default=None, choices=["reference", "fused"],
@@ -555,7 +578,7 @@ def main(argv=None):
     if args.loss_path is not None and args.train_steps is None:
         ap.error("--loss-path needs --train-steps")
     if args.input is None or args.train_steps is None:
-        for name in ("patch", "frames_per_sample", "group", "seed", "save"):
+        for name in ("patch", "frames_per_sample", "group", "seed", "save", "avoid_cuts", "cut_thresholds", "act_min", "tries"):
             if getattr(args, name) is not None:
                 ap.error(f"--{name.replace('_', '-')} needs --input and --train-steps (the streamed clip trainer)")
     if args.field_order is not None and args.deinterlace is None:
@@ -595,10 +618,17 @@ def main(argv=None):
                 ap.error("--frames-per-sample is at least 3 (one window)")
             if group < n:
                 ap.error("--group must hold a sample: at least --frames-per-sample frames")
+            if args.cut_thresholds is not None and not args.avoid_cuts:
+                ap.error("--cut-thresholds needs --avoid-cuts")
+            if args.tries is not None and args.act_min is None:
+                ap.error("--tries needs --act-min")
+            if args.tries is not None and args.tries < 1:
+                ap.error("--tries is at least 1")
             line, _ = run_file_train(args.input, args.train_steps, size=args.size, pix_fmt=args.pix_fmt, matrix=args.matrix, siting=args.siting,
                                      checkpoint=args.checkpoint, scale=args.scale, precision=args.precision, patch=patch,
                                      frames_per_sample=n, group=group, seed=args.seed or 0, decimate=args.decimate,
-                                     max_grad_norm=args.max_grad_norm, loss_path=args.loss_path or "reference", save=args.save)
+                                     max_grad_norm=args.max_grad_norm, loss_path=args.loss_path or "reference", save=args.save,
+                                     avoid_cuts=bool(args.avoid_cuts), cut_thresholds=args.cut_thresholds, act_min=args.act_min, tries=args.tries)
             print(json.dumps(line))
             return
         if args.multiscale and args.score is None:

@@ -28,6 +28,10 @@ libraries for frames, one section each.
     patch_table / patch_gather / patch_item   training samples (include/vsr_hip_patch.h): random crops, the eight symmetries of the
                             square and time reversal drawn on the host as a table, all samples of a step cut from the resident frames
                             in one launch with their LR patches, and a sample as the (data, target, high_frames) of the train loop
+    cell_stats / cell_cuts / patch_score / patch_table_select   where to cut them (include/vsr_hip_cell.h): the spatial activity and the
+                            temporal difference of every 16 x 16 cell of every resident frame in one launch, the cut rule of `scene_cuts`
+                            on the map's sums, the activity of a table row's crop, and a table whose rows straddle no cut and prefer
+                            patches with detail
 
 `clip_runner.ClipRunner` streams a clip through the first six, `clip_trainer.ClipTrainer` trains on patches of one; `driver` imports every public name here, so `driver.frame_metrics` and the
 rest resolve as before.  `y4m` reads and writes the YUV4MPEG2 files a clip arrives in.  Transfer functions stay out.
@@ -915,3 +919,156 @@ def patch_item(hr: torch.Tensor, lr: torch.Tensor, b: int):
     data = lr[b].unfold(0, 3, 1).permute(0, 4, 1, 2, 3)            # [n-2,3,h,w,3]: window t is lr[b, t:t+3]
     high_frames = hr[b].unfold(0, 3, 1).permute(0, 4, 1, 2, 3).contiguous()
     return data, high_frames[:, 1:2].clone(), high_frames
+
+
+# ------------------------------------------------------------------------------------------------ where to cut training patches
+CELL = 16   # VSR_CELL of include/vsr_hip_cell.h
+
+
+def cell_shape(shape: Tuple[int, int]) -> Tuple[int, int]:
+    """(Ch, Cw) = (ceil(H / CELL), ceil(W / CELL)): the cells of a frame of `shape` = (H, W)."""
+    return -(-int(shape[0]) // CELL), -(-int(shape[1]) // CELL)
+
+
+@L.on_device
+def cell_stats(frames: torch.Tensor, luma4=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """float32 RGB `frames` [G,H,W,3] (0..255) on the device -> the device tensor int32 [G,Ch,Cw,2] of vsr_cell_stats
+    (include/vsr_hip_cell.h), (Ch, Cw) = `cell_shape`: per frame and cell of CELL x CELL pixels, channel 0 the sum of |dx| + |dy| of the
+    8-bit luma code over the cell's pixels (neighbours inside the frame only), channel 1 the sum of its absolute difference against the
+    frame before (0 for the first frame).  One launch; every frame is read once.  Nothing is synchronised; `cell_cuts`, `patch_score` and
+    `patch_table_select` are the host steps on the map.  `luma4`: four float32 {a0, a1, a2, o}, default the BT.601 luma of `scene_sums`;
+    `out`: write the map there (int32 of that shape, part of a larger tensor will do)."""
+    import ctypes
+    if frames.dim() != 4 or frames.shape[-1] != 3:
+        raise ValueError(f"expected float32 [G,H,W,3], got {tuple(frames.shape)}")
+    G, H, W = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+    luma4 = _luma4("y", "bt601", False) if luma4 is None else np.ascontiguousarray(np.asarray(luma4, dtype=np.float32).reshape(4))
+    M = L.load_cell()
+    pf = L.dptr(frames)   # (raises on CPU tensors, on anything but float32 and on strided views)
+    shape = (G,) + cell_shape((H, W)) + (2,)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.int32, device=frames.device)
+    elif tuple(out.shape) != shape or out.device != frames.device:
+        raise ValueError(f"out must be int32 {shape} on {frames.device}, got {tuple(out.shape)} on {out.device}")
+    L.check(M.vsr_cell_stats(pf, G, H, W, luma4.ctypes.data_as(ctypes.c_void_p), L.dptr(out, torch.int32), L.stream()), "cell_stats", lib=M)
+    return out
+
+
+def _stats_array(stats) -> np.ndarray:
+    """The map [G,Ch,Cw,2] (a tensor, copied to the host here, or an array) as an int64 array."""
+    s = stats.detach().cpu().numpy() if isinstance(stats, torch.Tensor) else np.asarray(stats)
+    if s.ndim != 4 or s.shape[-1] != 2:
+        raise ValueError(f"expected the map int32 [G,Ch,Cw,2] of cell_stats, got {s.shape}")
+    return s.astype(np.int64)
+
+
+def cell_cuts(stats, shape: Tuple[int, int], thresholds=None) -> Tuple[np.ndarray, np.ndarray]:
+    """The host step after `cell_stats`: the map of ONE group of G frames of `shape` = (H, W) -> (cuts bool [G-1], m float64 [G-1]).
+    Pair p = (p, p + 1) has sad = stats[p+1, :, :, 1].sum() in int64 and n = H * W; the rest is `scene_cuts` on those rows, unchanged:
+    m = sad / n, cut_p = m_p >= t_abs and m_p >= ratio * m_{p-1}, with m_{-1} = 0 AT THE START OF EVERY GROUP: the pair between two groups
+    is not scored, because samples never span groups, so a group's first pair is judged on t_abs alone.  The m are, bit for bit, those of
+    `scene_sums` / `scene_cuts` on the same consecutive frames.  `thresholds`: (t_abs, ratio), default `SCENE_THRESHOLDS`."""
+    s = _stats_array(stats)
+    H, W = int(shape[0]), int(shape[1])
+    if tuple(s.shape[1:3]) != cell_shape((H, W)):
+        raise ValueError(f"the map of {s.shape[1]} x {s.shape[2]} cells is not that of frames of {H} x {W}")
+    _scene_thresholds(thresholds)
+    if s.shape[0] < 2:
+        return np.zeros(0, dtype=bool), np.zeros(0, dtype=np.float64)
+    sums = np.empty((s.shape[0] - 1, 2), dtype=np.float64)
+    sums[:, 0] = s[1:, :, :, 1].sum(axis=(1, 2))
+    sums[:, 1] = float(H * W)
+    return scene_cuts(sums, thresholds)
+
+
+def _crop_cells(row, patch) -> Tuple[int, int, int, int]:
+    """(i0, i1, j0, j1): the cells wholly inside the crop of table row `row`, i in [i0, i1), j in [j0, j1)."""
+    Ph, Pw = _patch_shape(patch)
+    _, y0, x0, flags = (int(v) for v in row)
+    ch, cw = (Pw, Ph) if flags & PATCH_FLAGS["transpose"] else (Ph, Pw)
+    return -(-y0 // CELL), (y0 + ch) // CELL, -(-x0 // CELL), (x0 + cw) // CELL
+
+
+def patch_score(stats, row, n: int, patch) -> float:
+    """The activity of the sample of table row `row` = {t0, y0, x0, flags} (`patch_table`) on the map `stats` [G,Ch,Cw,2] of `cell_stats`:
+    the mean |dx| + |dy| in luma codes per pixel, float64.  (ch, cw) is the crop of the row, (Pw, Ph) under the transposition bit; the
+    counted cells are those wholly inside the crop, i in [ceil(y0 / CELL), floor((y0 + ch) / CELL)), j likewise (so a ragged cell of the
+    frame's edge is never counted); the score is the sum of stats[t, i, j, 0] over them and t in [t0, t0 + n), divided once in double by
+    n * cells * CELL * CELL.  A crop with no whole cell inside is refused (every crop of at least 2 * CELL - 1 each way has one)."""
+    s = stats if isinstance(stats, np.ndarray) and stats.dtype == np.int64 and stats.ndim == 4 else _stats_array(stats)
+    i0, i1, j0, j1 = _crop_cells(row, patch)
+    t0, n = int(row[0]), int(n)
+    if i1 <= i0 or j1 <= j0:
+        raise ValueError(f"the crop of row {tuple(int(v) for v in row)} holds no whole cell of {CELL} x {CELL}")
+    if t0 < 0 or n <= 0 or t0 + n > s.shape[0] or i0 < 0 or j0 < 0 or i1 > s.shape[1] or j1 > s.shape[2]:
+        raise ValueError(f"row {tuple(int(v) for v in row)} with n = {n} leaves the map of {tuple(s.shape[:3])}")
+    total = int(s[t0:t0 + n, i0:i1, j0:j1, 0].sum())
+    return float(np.float64(total) / np.float64(n * (i1 - i0) * (j1 - j0) * CELL * CELL))
+
+
+def patch_table_select(rng, B: int, G: int, n: int, shape: Tuple[int, int], patch, S: int, augment: bool = True,
+                       transpose: Optional[bool] = None, cuts=None, stats=None, act_min: Optional[float] = None, tries: int = 8):
+    """`patch_table` with two rules on top -> (table int32 [B',4], scores float64 [B'], tried int32 [B']).  Pure host code.
+        cuts     bool [G-1] (`cell_cuts`): pair p set means frames p and p + 1 belong to two shots.  valid = the t0 of range(G - n + 1) with
+                 no set pair among cuts[t0 : t0 + n - 1]; all of them without `cuts`.  No valid t0: B' = 0 and NOTHING is drawn from `rng`.
+        act_min  with `stats` (the map of `cell_stats`, on the host): a candidate qualifies where `patch_score` >= act_min.
+    A candidate is drawn exactly as a row of `patch_table`, in its order: flags (if `augment`), t0 = valid[rng.randint(len(valid))], y0,
+    x0.  Without `act_min` the first candidate is the row (score NaN, tried 1).  With it, up to `tries` candidates are drawn: the first
+    that qualifies is the row (tried = its number, from 1); if none does, the one with the largest score, the first among equals
+    (tried = tries).  The draw order is part of the contract: with no cut set and no `act_min`, the table AND the state of `rng`
+    afterwards are `patch_table`'s for the same seed.  B' is B or 0."""
+    Ph, Pw = _patch_shape(patch)
+    H, W = int(shape[0]), int(shape[1])
+    B, G, n, S, tries = int(B), int(G), int(n), int(S), int(tries)
+    if B <= 0 or n <= 0 or G < n:
+        raise ValueError(f"need B > 0 and 0 < n <= G, got B {B}, n {n}, G {G}")
+    if S <= 0 or Ph <= 0 or Pw <= 0 or Ph % S or Pw % S:
+        raise ValueError(f"the patch of {Ph} x {Pw} must be a positive multiple of S = {S}")
+    may_transpose = (Ph == Pw) if transpose is None else bool(transpose)
+    if Ph > H or Pw > W or (may_transpose and (Pw > H or Ph > W)):
+        raise ValueError(f"the patch of {Ph} x {Pw} does not fit the frames of {H} x {W}")
+    if tries < 1:
+        raise ValueError(f"tries must be at least 1, got {tries}")
+    if act_min is not None:
+        if stats is None:
+            raise ValueError("act_min needs stats (the map of cell_stats)")
+        stats = _stats_array(stats)
+        if stats.shape[0] != G or tuple(stats.shape[1:3]) != cell_shape((H, W)):
+            raise ValueError(f"the map {tuple(stats.shape)} is not that of {G} frames of {H} x {W}")
+        act_min = float(act_min)
+    valid = list(range(G - n + 1))
+    if cuts is not None:
+        c = np.asarray(cuts, dtype=bool).reshape(-1)
+        if c.size != G - 1:
+            raise ValueError(f"cuts must hold the G - 1 = {G - 1} pairs of the group, got {c.size}")
+        valid = [t0 for t0 in valid if not c[t0:t0 + n - 1].any()]
+    if not valid:
+        return np.zeros((0, 4), dtype=np.int32), np.zeros(0, dtype=np.float64), np.zeros(0, dtype=np.int32)
+
+    def draw():
+        flags = int(rng.randint(16)) if augment else 0
+        if not may_transpose:
+            flags &= ~PATCH_FLAGS["transpose"]
+        ch, cw = (Pw, Ph) if flags & PATCH_FLAGS["transpose"] else (Ph, Pw)
+        t0 = valid[int(rng.randint(len(valid)))]
+        y0 = int(rng.randint((H - ch) // S + 1)) * S
+        x0 = int(rng.randint((W - cw) // S + 1)) * S
+        return (t0, y0, x0, flags)
+
+    table = np.empty((B, 4), dtype=np.int32)
+    scores, tried = np.full(B, np.nan, dtype=np.float64), np.ones(B, dtype=np.int32)
+    for b in range(B):
+        if act_min is None:
+            table[b] = draw()
+            continue
+        best = None
+        for k in range(1, tries + 1):
+            row = draw()
+            score = patch_score(stats, row, n, (Ph, Pw))
+            if best is None or score > best[1]:
+                best = (row, score)
+            if score >= act_min:
+                best = (row, score)
+                break
+        table[b], scores[b], tried[b] = best[0], best[1], k
+    return table, scores, tried
